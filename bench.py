@@ -26,6 +26,25 @@ the neighbouring bands) moves by grouped ncclSend/ncclRecv on the handle's strea
 frame, no host wait (pathtracerdemo_amd/csrc/ptx_comm.cpp).  `--weak` keeps the per-GPU frame
 fixed instead (rank r renders rows [r*H, (r+1)*H) of a W x (H*N) frame).  Timing: barrier +
 max-reduce of the elapsed time.
+
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure needs and no more:
+scene and handle set-up, W untimed frames, the K timed frames, `--dump-outputs` if asked, the
+result line (metric, value, unit, higher_is_better, dtype, ms_per_step, the frame's kernel time).
+Set-up includes a throwaway handle that renders the pipeline's first two frames (first_frames:
+what the process pays once is paid there, not in the W or K frames, so a short probe such as
+`--steps 1 --warmup 0` reads a step time of the same order as a long run:
+profiles/plain_full/).  The timed handle still allocates its own buffers in its first two
+frames, one set per frame in flight: steady-state figures want W >= 3, the default.
+`--full` adds everything else the line can carry, each in runs of its own after the timed region:
+the work census and the roofline (launch-timed second region, in-run PMC passes), the C and JS CPU
+baselines with the oracle parity check, and configs[3]'s 4K frame on this one GPU.
+
+`--dump-outputs DIR` writes what the timed handle holds after its last timed frame -- what a caller
+of Render() reads back: the accumulated radiance (`image.npy`, float32) and, for reuse / GI, the
+spatial-output reservoirs (`reservoirs.npy`, the raw 32-bit words as float64: packed float and
+integer fields, to be compared for equality, not by relative difference) -- at most 64 MB (larger
+outputs: a fixed seeded sample of pixels).  The scene, camera (path) and frame indices depend only
+on the arguments, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -101,8 +120,20 @@ def parse():
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one GPU each; default 1, or WORLD_SIZE under torchrun); spawned by bench.py "
                          "itself unless run under torchrun")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=20, help="timed frames")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed frames of the timed handle before them (what the process pays once is paid "
+                                                               "in set-up whatever this is; the handle allocates in its first two frames, so "
+                                                               "steady-state figures want 3 or more)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: work census + roofline (a second, launch-timed region and in-run "
+                         "PMC passes), the CPU baselines with the oracle parity check, configs[3] on one GPU "
+                         "(each takes runs of its own; the options below that skip one of them apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write the timed handle's outputs to DIR/<name>.npy: image "
+                         "(accumulated radiance, float32: the array to compare numerically) and, for reuse / gi, "
+                         "reservoirs (the spatial output's raw 32-bit words -- packed float and integer fields -- "
+                         "as float64: for exact equality only, a relative difference of bit patterns means "
+                         "nothing); at most 64 MB, larger outputs as a fixed seeded pixel sample")
     ap.add_argument("--workload", choices=["reuse", "restir", "mcpt", "gi"], default="reuse")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -182,6 +213,24 @@ def census(cs, W, H, pipeline, device, passes):
     return out
 
 
+def first_frames(cs, W, H, pipeline, device):
+    """Set-up of a run without --full: a throwaway handle of the same pipeline renders its first
+    two frames (the second with its history) and closes, untimed, so what the process pays once
+    (the first launches of every kernel, their scratch, the streams) is not in the timed
+    handle's frames; that handle is created afterwards and starts from its own frame 1.  The
+    throwaway frame is the timed one capped at 1920x1080: measured on MI355X, closing a handle of
+    a 3840x2160 frame just before the timed one leaves the timed handle's first frame at 2.7 s
+    (its GBs of queues and reservoirs freed and allocated again), which a 1920x1080 one does not."""
+    from pathtracerdemo_amd.renderer import Renderer
+    r = Renderer(min(W, 1920), min(H, 1080), device=device, pipeline=pipeline)
+    r.Initialize(cs)
+    for _ in range(2):
+        r.Update()
+        r.Render()
+    r.synchronize()
+    r.close()
+
+
 def calibrate_band(cs, W, H, pipeline, device, row_begin, row_end, passes, frames=4, overlap=False):
     """ms per frame of rows [row_begin, row_end) rendered alone on this rank's GPU: the band
     handle renders its frames exactly as a rank does (pipelined band frames, same launches) but
@@ -225,7 +274,7 @@ def pmc_traffic(args, W, H):
         return None, "rocprofv3 is not on PATH"
     child = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--scene", args.scene,
              "--frame", f"{W}x{H}", "--variant", args.variant, "--profile-region", "--steps", "5", "--warmup", "1",
-             "--no-pmc-traffic"] + (["--camera-path"] if args.camera_path else [])
+             "--full", "--no-pmc-traffic"] + (["--camera-path"] if args.camera_path else [])
     tmp = tempfile.mkdtemp(prefix="ptx_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
     vals = {}
@@ -260,6 +309,131 @@ def band_work(tile_census: np.ndarray, row_begin: int, row_end: int) -> dict:
     tot = frac @ tile_census
     keys = ("rays", "instance_xforms", "aabb_tests", "tri_tests", "hits")
     return {k: int(round(v)) for k, v in zip(keys, tot)}
+
+
+# --dump-outputs: bytes per file (64 MB in all, shared by the ranks of a multi-GPU run); a
+# 1920x1080 image (33 MB of float32) fits whole
+DUMP_CAP = {"image": 36 << 20, "reservoirs": 24 << 20}
+
+
+def dump_outputs(d: str, arrays: dict, rank: int = 0, world: int = 1) -> dict:
+    """`--dump-outputs`: every (rows, W, C) array as d/<name>.npy (d/<name>_rank<r>.npy with
+    several ranks, each its band) -- float32 as it is, 32-bit words as float64 (exact).  An
+    array over its share of DUMP_CAP is written as a (n, C) sample of its pixels instead:
+    sorted flat pixel indices from a fixed seed, a function of the array's shape alone.
+    Returns {file: shape}."""
+    os.makedirs(d, exist_ok=True)
+    done = {}
+    for name, a in arrays.items():
+        dt = np.float32 if a.dtype == np.float32 else np.float64
+        px_bytes = a.shape[-1] * np.dtype(dt).itemsize
+        npx = a.shape[0] * a.shape[1]
+        keep = (DUMP_CAP[name] // world) // px_bytes
+        if npx > keep:
+            idx = np.sort(np.random.default_rng(0x5EED).choice(npx, size=keep, replace=False))
+            a = a.reshape(npx, a.shape[-1])[idx]
+        fn = name + (f"_rank{rank}" if world > 1 else "") + ".npy"
+        np.save(os.path.join(d, fn), np.ascontiguousarray(a, dtype=dt))
+        done[fn] = list(a.shape)
+    return done
+
+
+def roofline(args, N, cen, passes, pipeline, W, Hb, row_begin, row_end, world, kms, st_k) -> dict:
+    """`--full`: the line's roofline field, from the work census `cen` of the frame, the headline
+    region's kernel times `kms` and the launch-timed region's stats `st_k` (None: --variant simple)."""
+    counts = {p: band_work(cen[p], row_begin, row_end) for p in passes}
+    px = W * Hb
+    pio = PASS_IO_GI if pipeline == "gi" else PASS_IO
+    alg_bytes = {p: ray_bytes(counts[p]) + pio[p] * px for p in passes}
+    # frame-level figure of SURVEY.md §8d: algorithmic bytes of the frame / kernel time
+    frame_bytes = sum(alg_bytes.values())
+    frame_kernel_s = sum(v for k, v in kms.items() if k != "frame_event_span") * 1e-3
+    n_trace = st_k["kernel_launches"][N.PTX_STAT_WAVE_TRACE] if st_k else 0
+    if n_trace:
+        # wavefront: the dominant kernel is trace_queue (every trace round of every pass).
+        # Its algorithmic bytes per launch = the frame's traversal bytes (+ 32 B ray record
+        # read and 32 B hit record written per query) / trace launches per frame; its
+        # duration is the HIP-event average over the timed region.
+        dom = "trace_queue"
+        traced = [p for p in passes if p != "gbuffer"]
+        if st_k["kernel_launches"][N.PTX_STAT_FINAL_FUSED]:
+            # the library reports that the reuse pipeline's PT_4 walked its replays inside its one
+            # logic kernel (wfinal_one): none of its queries reached trace_queue
+            traced = [p for p in traced if p != "final"]
+        work = {k: sum(counts[p][k] for p in traced) for k in counts[traced[0]]}
+        per_frame = n_trace / args.steps
+        # SURVEY §8(d)'s B_ray only (layout-neutral); the queue's 64 B per query beside it
+        dom_bytes = ray_bytes(work) / per_frame
+        queue_io = QUEUE_IO_PER_RAY * work["rays"] / per_frame
+        dom_ms = st_k["kernel_ms_total"][N.PTX_STAT_WAVE_TRACE] / n_trace
+        logic_ms = (st_k["kernel_ms_total"][N.PTX_STAT_WAVE_LOGIC]
+                    / max(1, st_k["kernel_launches"][N.PTX_STAT_WAVE_LOGIC]))
+        extra = {"launches_per_frame": per_frame, "logic_kernel_avg_ms": round(logic_ms, 4),
+                 "queue_io_bytes_per_launch": int(queue_io),
+                 "frac_with_queue_io": round((dom_bytes + queue_io) / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                 "bytes_note": "alg_bytes_per_launch = SURVEY §8(d) B_ray (32 per AABB test + 36 per triangle test "
+                               "+ 48 per instance transform + 48 per hit reconstruction) / trace launches per frame; "
+                               "the wavefront queue's own ray / hit records (64 B per query) are NOT counted in frac"}
+    else:
+        dom = max(kms, key=lambda p: kms[p])
+        work = counts[dom]
+        dom_bytes = alg_bytes[dom]
+        dom_ms = kms[dom]
+        extra = {}
+    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
+    traffic = None
+    limiters = None
+    # profiles/hbm_traffic.json and profiles/limiters.json: an earlier profile's figures, by key
+    key = f"{pipeline}:{args.scene}:{dom}:{W}x{Hb}"
+    prof = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+    traffic_source = None
+    if os.path.exists(prof):
+        try:
+            entry = json.load(open(prof)).get(key)
+            traffic = entry["bytes_per_launch"] if isinstance(entry, dict) else entry
+            if traffic:
+                traffic_source = ("profiles/hbm_traffic.json (" + (entry.get("source", "?") if isinstance(entry, dict)
+                                                                   else "?") + "): an earlier run's PMC passes")
+        except Exception:
+            traffic = None
+    # measured in this run where the machine allows it (one GPU, the timed traversal symbol)
+    if (world == 1 and n_trace and args.variant == "wave" and not args.profile_region
+            and not args.no_pmc_traffic):
+        measured, info = pmc_traffic(args, W, Hb)
+        if measured is not None:
+            traffic = int(round(measured))
+            traffic_source = (f"measured in this run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (child "
+                              f"processes, launch-timed region, {info} dispatches), 2*FETCH_SIZE + WRITE_SIZE per "
+                              f"launch of {TIMED_SYMBOL}>")
+        elif traffic_source:
+            traffic_source += f"; in-run PMC unavailable: {info}"
+        else:
+            traffic_source = f"in-run PMC unavailable: {info}"
+    lim = os.path.join(ROOT, "profiles", "limiters.json")
+    if os.path.exists(lim) and n_trace:
+        try:
+            entry = json.load(open(lim)).get(key)
+        except Exception:
+            entry = None
+        if entry:
+            # what bounds the kernel (DESIGN §4.2): the L2's request bytes against its peak, and the
+            # lanes the traversal's node loop keeps busy (the simd_util build)
+            limiters = dict(entry)
+            l2 = entry.get("l2_bytes_per_launch")
+            if l2:
+                limiters["l2_achieved_gbs"] = round(l2 / (dom_ms * 1e-3) / 1e9, 1)
+                limiters["l2_peak_gbs"] = L2_PEAK_GBS
+                limiters["l2_frac"] = round(l2 / (dom_ms * 1e-3) / 1e9 / L2_PEAK_GBS, 4)
+            if traffic:
+                limiters["hbm_traffic_frac"] = round(traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+    return {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+            "traffic_source": traffic_source,
+            "avg_launch_ms": round(dom_ms, 4), "alg_bytes_per_launch": int(dom_bytes),
+            "work_per_frame": work, **extra, "limiters": limiters,
+            "frame": {"alg_bytes": int(frame_bytes), "alg_bytes_per_sample": round(frame_bytes / px, 1),
+                      "kernel_ms": round(frame_kernel_s * 1e3, 4),
+                      "frac": round(frame_bytes / frame_kernel_s / (HBM_PEAK_GBS * 1e9), 4)}}
 
 
 def main():
@@ -299,9 +473,17 @@ def main():
         W, H = (int(v) for v in args.frame.lower().split("x"))
     else:  # weak scaling: rank r renders rows [r*Hb, (r+1)*Hb) of a W x (Hb*N) frame
         W, H = args.width, args.height * world
-    # work census of the exact frame (counting build, untimed): algorithmic bytes, and the
-    # cost-balanced bands of a strong-scaled frame
-    cen = census(cs, W, H, pipeline, device, passes)
+    # work census of the exact frame (counting build, untimed): algorithmic bytes (--full), and
+    # the cost-balanced bands of a strong-scaled frame
+    if args.full or (strong and world > 1):
+        cen = census(cs, W, H, pipeline, device, passes)
+    else:
+        # no census: its handle was also the first of the process to render, and so took what
+        # that costs once (every kernel's first launch, its scratch, the streams) before the timed
+        # handle existed.  A run without it pays the same in set-up -- never in --warmup or
+        # --steps, whatever they are
+        cen = None
+        first_frames(cs, W, H, pipeline, device)
     radius = 30
     calib = None
     if strong and world > 1:
@@ -398,18 +580,14 @@ def main():
     from pathtracerdemo_amd import _native as N
     pid = {"gbuffer": N.PTX_PASS_GBUFFER, "init": N.PTX_PASS_INIT, "final": N.PTX_PASS_FINAL,
            "mcpt": N.PTX_PASS_MCPT, "temporal": N.PTX_PASS_TEMPORAL, "spatial": N.PTX_PASS_SPATIAL}
-    counts = {p: band_work(cen[p], row_begin, row_end) for p in passes}
-    px = W * Hb
-    pio = PASS_IO_GI if pipeline == "gi" else PASS_IO
-    alg_bytes = {p: ray_bytes(counts[p]) + pio[p] * px for p in passes}
 
     def barrier():
         if dist is not None:
             dist.barrier()
 
-    def timed(rr, drv):
-        """W untimed warmup frames, then K frames between barriers + synchronize: seconds."""
-        for _ in range(args.warmup):
+    def timed(rr, drv, warmup):
+        """`warmup` untimed frames, then --steps frames between barriers + synchronize: seconds."""
+        for _ in range(warmup):
             frame(rr, drv)
         rr.synchronize()
         rr.reset_stats()
@@ -425,8 +603,17 @@ def main():
     band_digest = comm = None
     motion_clips = None
     frames_rendered = args.warmup + args.steps
+    dumped = None
+
+    def dump(rr, image):
+        """--dump-outputs: what a caller of the timed handle reads back after the last timed frame."""
+        arrays = {"image": image}
+        if reuse:
+            arrays["reservoirs"] = rr.read_history()
+        return dump_outputs(args.dump_outputs, arrays, rank, world)
+
     if r is not None:
-        elapsed = timed(r, band_drv)
+        elapsed = timed(r, band_drv, args.warmup)
         own_elapsed = elapsed
         if dist is not None:
             import torch
@@ -436,6 +623,8 @@ def main():
         st = r.stats()
         img = r.read_image()
         nonfinite = int((~np.isfinite(img[..., :3])).sum())
+        if args.dump_outputs:
+            dumped = dump(r, img)
         if args.camera_path and reuse:
             # pixels of the timed frames whose reprojection fell outside the rows the handle holds
             # (the global motion row rule: more than reuse_radius rows from the pixel's own row)
@@ -456,16 +645,17 @@ def main():
     # kernels share the GPU and a launch's duration measures the share, not the kernel;
     # the overlap's gain is in `value` and in roofline.frame.
     st_k = None
-    if args.variant == "wave":
+    if args.variant == "wave" and (args.full or args.profile_region):
         rk, drv_k = make(time_launches=True, single_stream=True)
-        args.warmup = max(1, args.warmup)
-        el_k = timed(rk, drv_k)
+        el_k = timed(rk, drv_k, max(1, args.warmup))
         st_k = rk.stats()
         if r is None:  # --profile-region: this region is the run
             elapsed = own_elapsed = el_k
             st = st_k
             img = rk.read_image()
             nonfinite = int((~np.isfinite(img[..., :3])).sum())
+            if args.dump_outputs:
+                dumped = dump(rk, img)
         rk.close()
 
     # per-rank band times, communicators and band digests (rank 0 reports them all)
@@ -504,98 +694,20 @@ def main():
         kms = {"pass_groups": st["kernel_ms_total"][N.PTX_STAT_PASS_GROUP] / args.steps}
     else:
         kms = {p: st["kernel_ms_total"][pid[p]] / max(1, st["kernel_launches"][pid[p]]) for p in passes}
-    # frame-level figure of SURVEY.md §8d: algorithmic bytes of the frame / kernel time
-    frame_bytes = sum(alg_bytes.values())
-    frame_kernel_s = sum(v for k, v in kms.items() if k != "frame_event_span") * 1e-3
-    n_trace = st_k["kernel_launches"][N.PTX_STAT_WAVE_TRACE] if st_k else 0
-    if n_trace:
-        # wavefront: the dominant kernel is trace_queue (every trace round of every pass).
-        # Its algorithmic bytes per launch = the frame's traversal bytes (+ 32 B ray record
-        # read and 32 B hit record written per query) / trace launches per frame; its
-        # duration is the HIP-event average over the timed region.
-        dom = "trace_queue"
-        traced = [p for p in passes if p != "gbuffer"]
-        if st_k["kernel_launches"][N.PTX_STAT_FINAL_FUSED]:
-            # the library reports that the reuse pipeline's PT_4 walked its replays inside its one
-            # logic kernel (wfinal_one): none of its queries reached trace_queue
-            traced = [p for p in traced if p != "final"]
-        work = {k: sum(counts[p][k] for p in traced) for k in counts[traced[0]]}
-        per_frame = n_trace / args.steps
-        # SURVEY §8(d)'s B_ray only (layout-neutral); the queue's 64 B per query beside it
-        dom_bytes = ray_bytes(work) / per_frame
-        queue_io = QUEUE_IO_PER_RAY * work["rays"] / per_frame
-        dom_ms = st_k["kernel_ms_total"][N.PTX_STAT_WAVE_TRACE] / n_trace
-        logic_ms = (st_k["kernel_ms_total"][N.PTX_STAT_WAVE_LOGIC]
-                    / max(1, st_k["kernel_launches"][N.PTX_STAT_WAVE_LOGIC]))
-        extra = {"launches_per_frame": per_frame, "logic_kernel_avg_ms": round(logic_ms, 4),
-                 "queue_io_bytes_per_launch": int(queue_io),
-                 "frac_with_queue_io": round((dom_bytes + queue_io) / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                 "bytes_note": "alg_bytes_per_launch = SURVEY §8(d) B_ray (32 per AABB test + 36 per triangle test "
-                               "+ 48 per instance transform + 48 per hit reconstruction) / trace launches per frame; "
-                               "the wavefront queue's own ray / hit records (64 B per query) are NOT counted in frac"}
-    else:
-        dom = max(kms, key=lambda p: kms[p])
-        work = counts[dom]
-        dom_bytes = alg_bytes[dom]
-        dom_ms = kms[dom]
-        extra = {}
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-    traffic = None
-    limiters = None
-    # (profiles/hbm_traffic.json and profiles/limiters.json travel to the GPU box: .gpurunignore
-    # excludes only the per-round profile directories)
-    key = f"{pipeline}:{args.scene}:{dom}:{W}x{Hb}"
-    prof = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    traffic_source = None
-    if os.path.exists(prof):
-        try:
-            entry = json.load(open(prof)).get(key)
-            traffic = entry["bytes_per_launch"] if isinstance(entry, dict) else entry
-            if traffic:
-                traffic_source = ("profiles/hbm_traffic.json (" + (entry.get("source", "?") if isinstance(entry, dict)
-                                                                   else "?") + "): an earlier run's PMC passes")
-        except Exception:
-            traffic = None
-    # measured in this run where the box allows it (one GPU, the timed traversal symbol)
-    if (world == 1 and n_trace and args.variant == "wave" and not args.profile_region
-            and not args.no_pmc_traffic):
-        measured, info = pmc_traffic(args, W, Hb)
-        if measured is not None:
-            traffic = int(round(measured))
-            traffic_source = (f"measured in this run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (child "
-                              f"processes, launch-timed region, {info} dispatches), 2*FETCH_SIZE + WRITE_SIZE per "
-                              f"launch of {TIMED_SYMBOL}>")
-        elif traffic_source:
-            traffic_source += f"; in-run PMC unavailable: {info}"
-        else:
-            traffic_source = f"in-run PMC unavailable: {info}"
-    lim = os.path.join(ROOT, "profiles", "limiters.json")
-    if os.path.exists(lim) and n_trace:
-        try:
-            entry = json.load(open(lim)).get(key)
-        except Exception:
-            entry = None
-        if entry:
-            # what bounds the kernel: the L2's request bytes against its peak, and the
-            # lanes the traversal's node loop keeps busy (the simd_util build)
-            limiters = dict(entry)
-            l2 = entry.get("l2_bytes_per_launch")
-            if l2:
-                limiters["l2_achieved_gbs"] = round(l2 / (dom_ms * 1e-3) / 1e9, 1)
-                limiters["l2_peak_gbs"] = L2_PEAK_GBS
-                limiters["l2_frac"] = round(l2 / (dom_ms * 1e-3) / 1e9 / L2_PEAK_GBS, 4)
-            if traffic:
-                limiters["hbm_traffic_frac"] = round(traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+    roof = None
+    if args.full:
+        roof = roofline(args, N, cen, passes, pipeline, W, Hb, row_begin, row_end, world, kms, st_k)
     cpu = ts_cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(cs, W, Hb, pipeline, args.cpu_threads or usable_cpus(), device=device,
                            camera_path=args.camera_path)
         ts_cpu = ts_cpu_baseline(cs, args.scene, W, Hb, args.cpu_threads or usable_cpus(), rows=Hb)
     # configs[3]'s 3840x2160 frame on this one GPU: the single-GPU reference of the strong
     # split the N > 1 lines run (their per-GPU efficiency is value_N / (N x this value))
     one_gpu_4k = None
-    if world == 1 and pipeline == "reuse" and (W, H) == (1920, 1080) and args.variant == "wave" and not args.no_configs3:
-        one_gpu_4k = one_gpu_rate(cs, 3840, 2160, pipeline, device, max(5, args.steps // 2), args.warmup)
+    if (args.full and world == 1 and pipeline == "reuse" and (W, H) == (1920, 1080) and args.variant == "wave"
+            and not args.no_configs3):
+        one_gpu_4k = one_gpu_rate(cs, 3840, 2160, pipeline, device, max(5, args.steps // 2), max(1, args.warmup))
     if world > 1:
         workload = (f"{args.scene} {pipeline} {W}x{H} split over {world} GPUs, 1 spp/frame (configs[3])"
                     if strong else f"{args.scene} {pipeline} {W}x{Hb} per GPU, 1 spp/frame")
@@ -624,17 +736,12 @@ def main():
                        if reuse and world > 1 else "")},
         "kernel_ms": {p: round(v, 4) for p, v in kms.items()},
         "nonfinite_px": nonfinite,
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "traffic_source": traffic_source,
-                     "avg_launch_ms": round(dom_ms, 4), "alg_bytes_per_launch": int(dom_bytes),
-                     "work_per_frame": work, **extra, "limiters": limiters,
-                     "frame": {"alg_bytes": int(frame_bytes), "alg_bytes_per_sample": round(frame_bytes / px, 1),
-                               "kernel_ms": round(frame_kernel_s * 1e3, 4),
-                               "frac": round(frame_bytes / frame_kernel_s / (HBM_PEAK_GBS * 1e9), 4)}},
-        "cpu_baseline": cpu,
-        "ts_cpu_baseline": ts_cpu,
+        "full": args.full,
     }
+    if args.full:
+        line.update({"roofline": roof, "cpu_baseline": cpu, "ts_cpu_baseline": ts_cpu})
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     if cpu is not None and "parity" in cpu:
         line["parity"] = cpu.pop("parity")
     if motion_clips is not None:

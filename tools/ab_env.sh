@@ -11,7 +11,7 @@ for rep in $(seq 1 ${REPS:-1}); do
 while IFS= read -r line; do
   [ -z "$line" ] && continue
   i=$((i+1))
-  env $line timeout -k 10 200 python3 bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/run_$i.log" 2>&1 || { echo "[$line] failed rc=$?"; tail -n 5 "$OUT/run_$i.log"; exit 1; }
+  env $line timeout -k 10 200 python3 bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/run_$i.log" 2>&1 || { echo "[$line] failed rc=$?"; tail -n 5 "$OUT/run_$i.log"; exit 1; }
   v=$(grep '^{' "$OUT/run_$i.log" | tail -n 1 | python3 -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["frac"])')
   echo "rep $rep [$line] value ms frac: $v"
 done <<< "$AB"

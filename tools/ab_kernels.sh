@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for L in $LIBS; do
   PTX_LIB_PATH=$P/$L PTX_AB=PIPELINE_FRAMES=0${EXTRA_AB:+,$EXTRA_AB} timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/$L" -o run --output-format csv -- \
-      python3 "$R/bench.py" --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/$L.log" 2>&1 || { echo "$L rc=$?"; tail -5 "$OUT/$L.log"; exit 1; }
+      python3 "$R/bench.py" --full --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/$L.log" 2>&1 || { echo "$L rc=$?"; tail -5 "$OUT/$L.log"; exit 1; }
 done
 python3 - "$OUT" $LIBS <<'PY'
 import csv, glob, sys

@@ -15,6 +15,8 @@ declare -A SCENE=([reuse]=c3_interior_32 [gi]=c3_interior_32 [restir]=dummy_scen
 for WL in ${WORKLOADS:-reuse restir mcpt gi}; do
   if [ -n "${SRC:-}" ]; then src=$SRC/prof_$WL; line=$SRC/$WL.json; simd=$SRC/simd_$WL.txt
   else src=gpurun_out/prof_${ROUND}_$WL; line=gpurun_out/bench_${ROUND}_$WL.log; simd=; fi
+  # (tools/round_evidence.sh writes its bench line's log under $OUT, default build/evidence)
+  [ -n "${SRC:-}" ] || line="${OUT:-build/evidence}/bench_${ROUND}_$WL.log"
   [ -d "$src" ] || { echo "skip $WL (no $src)"; continue; }
   dst=profiles/$ROUND/$WL
   mkdir -p "$dst"

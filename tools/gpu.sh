@@ -37,7 +37,7 @@ smoke)
 bench)
     name=$1
     shift
-    timeout -k 10 600 python -u bench.py "$@" > "$O/$name.log" 2>&1 || { echo "bench $name failed"; tail -20 "$O/$name.log"; exit 1; }
+    timeout -k 10 600 python -u bench.py --full "$@" > "$O/$name.log" 2>&1 || { echo "bench $name failed"; tail -20 "$O/$name.log"; exit 1; }
     grep '^{' "$O/$name.log" | tail -n 1 > "$O/$name.json"
     python3 - "$O/$name.json" <<'EOF'
 import json, sys
@@ -54,14 +54,14 @@ profile)
     P="$R/$O"
     unset PTX_AB PTX_LIB_PATH
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$P/trace" -o run --output-format csv -- \
-        python3 "$R/bench.py" --profile-region --steps 20 --warmup 3 "$@" > "$P/bench_trace.log" 2>&1 \
+        python3 "$R/bench.py" --full --profile-region --steps 20 --warmup 3 "$@" > "$P/bench_trace.log" 2>&1 \
         || { echo "trace rc=$?"; tail -5 "$P/bench_trace.log"; exit 1; }
     grep '^{' "$P/bench_trace.log" | tail -n 1 > "$P/bench_line_profile_region.json"
     echo "trace ok"
     for C in FETCH_SIZE WRITE_SIZE "TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum"; do
         tag=$(echo "$C" | cut -d' ' -f1)
         timeout -s KILL 120 rocprofv3 --pmc $C -d "$P/pmc_$tag" -o run --output-format csv -- \
-            python3 "$R/bench.py" --profile-region --steps 5 --warmup 1 "$@" > "$P/bench_$tag.log" 2>&1 \
+            python3 "$R/bench.py" --full --profile-region --steps 5 --warmup 1 "$@" > "$P/bench_$tag.log" 2>&1 \
             || { echo "pmc $tag rc=$?"; tail -5 "$P/bench_$tag.log"; exit 1; }
         echo "pmc $tag ok"
     done
@@ -73,7 +73,7 @@ kstats)  # rocprofv3 --kernel-trace --stats of the profile region only, on the l
     cd /tmp && export TMPDIR=/tmp
     P="$R/$O"
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$P/trace" -o run --output-format csv -- \
-        python3 "$R/bench.py" --profile-region --steps 20 --warmup 3 "$@" > "$P/bench_trace.log" 2>&1 \
+        python3 "$R/bench.py" --full --profile-region --steps 20 --warmup 3 "$@" > "$P/bench_trace.log" 2>&1 \
         || { echo "kstats rc=$?"; tail -5 "$P/bench_trace.log"; exit 1; }
     python3 "$R/tools/kstats.py" "$P/trace/run_kernel_stats.csv" ;;
 sq)  # one --pmc pass of 8 SQ counters over the profile region (wave cycles: parked / issue-stalled /
@@ -83,7 +83,7 @@ sq)  # one --pmc pass of 8 SQ counters over the profile region (wave cycles: par
     unset PTX_AB PTX_LIB_PATH
     timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
         SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR -d "$P/pmc_sq" -o run --output-format csv -- \
-        python3 "$R/bench.py" --profile-region --steps 5 --warmup 1 "$@" > "$P/bench_sq.log" 2>&1 \
+        python3 "$R/bench.py" --full --profile-region --steps 5 --warmup 1 "$@" > "$P/bench_sq.log" 2>&1 \
         || { echo "pmc sq rc=$?"; tail -5 "$P/bench_sq.log"; exit 1; }
     echo "pmc sq ok" ;;
 bands)

@@ -13,6 +13,6 @@ while IFS= read -r G; do
   [ -z "$G" ] && continue
   i=$((i+1))
   timeout -k 10 240 rocprofv3 --pmc $G -d "$OUT/g$i" -o run --output-format csv -- \
-      python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline $ARGS > "$OUT/g$i.log" 2>&1 || { echo "group $i rc=$?"; exit 1; }
+      python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline $ARGS > "$OUT/g$i.log" 2>&1 || { echo "group $i rc=$?"; exit 1; }
   echo "group $i ok: $G"
 done < "${GROUPS_FILE:-$R/tools/pmc_groups.txt}"

@@ -10,7 +10,10 @@ for WL in ${WORKLOADS:-reuse restir mcpt}; do
   # (every whole-image pipeline runs static trace slots since late round 5, as the profile's
   # one-frame-in-flight region does: no TRACE_DYN override)
   TAG=${ROUND}_$WL BENCH_ARGS="--workload $WL" bash tools/profile.sh || { echo "profile $WL failed"; exit 1; }
-  timeout -k 10 400 python3 bench.py --workload "$WL" --steps 20 --warmup 3 > "gpurun_out/bench_${ROUND}_$WL.log" 2>&1 \
+  # the bench line's log: under $OUT (default build/evidence, which git ignores)
+  LOG="${OUT:-build/evidence}/bench_${ROUND}_$WL.log"
+  mkdir -p "$(dirname "$LOG")"
+  timeout -k 10 400 python3 bench.py --full --workload "$WL" --steps 20 --warmup 3 > "$LOG" 2>&1 \
     || { echo "bench $WL failed"; exit 1; }
-  echo "$WL: $(tail -n 1 gpurun_out/bench_${ROUND}_$WL.log | cut -c1-200)"
+  echo "$WL: $(tail -n 1 "$LOG" | cut -c1-200)"
 done
