@@ -214,6 +214,15 @@ __device__ __forceinline__ uint4 rc_next(const uint4 *rv, uint32_t w20) {
 // path_label).  Called by every lane of the wave; `emit` selects the lanes with a live job.
 // Returns whether the job continues (else its result is out).
 // seed0: word 0 of the sample's reservoir (its first replayed draw's seed), read when s.i == 1.
+// KIND: a fresh shift job (i == 1, shift) takes one of three disjoint paths, known from its
+// sample's length and k alone (job_kind): JK_L the light segment, JK_C the hybrid connection,
+// JK_B a regenerated BSDF ray.  A caller whose lanes all hold one kind (wspatial_start's drains)
+// names it, and the other paths fold away; JK_ANY decides per lane.
+enum : int { JK_ANY = -1, JK_L = 0, JK_C = 1, JK_B = 2 };
+__device__ __forceinline__ int job_kind(uint32_t length, uint32_t k) {
+    return length <= 2u ? JK_L : (k == 2u ? JK_C : JK_B);
+}
+template <int KIND = JK_ANY>
 __device__ __forceinline__ bool job_emit(const Scene &sc, const Seg &g, const ReuseArgs &A, bool emit, Job &s,
                                          uint32_t jid, uint32_t seed0) {
     bool ray = false, vis = false, go = false;
@@ -224,12 +233,12 @@ __device__ __forceinline__ bool job_emit(const Scene &sc, const Seg &g, const Re
         const f3 V = normalize(s.prev - s.cur.pos);
         const bool hyb = job_hyb(s);
         bool ok = true;
-        if (s.i + 1u < s.length) {
+        if (KIND == JK_ANY ? s.i + 1u < s.length : KIND != JK_L) {
             // the direction out of the current vertex: to the stored x_k from y_{k-1} (conn, the
             // connection ray follows), to the kept x_{k+1} from x_k (fixd, no ray: the next step
             // takes the vertex), or a regenerated BSDF sample
-            const bool conn = s.shift && hyb && s.i + 1u == s.k;
-            const bool fixd = s.shift && hyb && s.i == s.k;  // (then k + 1 < length)
+            const bool conn = KIND == JK_ANY ? s.shift && hyb && s.i + 1u == s.k : KIND == JK_C;
+            const bool fixd = KIND == JK_ANY && s.shift && hyb && s.i == s.k;  // (then k + 1 < length)
             f3 dir;
             uint32_t lobe = LOBE_LAMBERT;
             if (conn || fixd) {
@@ -837,47 +846,97 @@ hipError_t wave_surface(const Scene &sc, const WaveBufs &w, const uint4 *gbuf, h
 // One thread per (pixel, kind): the forward shifts (slots 2m: neighbour m's sample in this
 // pixel's domain) share the pixel's camera point and hit surface, the backward ones (2m+1:
 // this pixel's sample in neighbour m's domain) its reservoir; the neighbour offsets come
-// from one pass over the pixel's salted stream.  A workgroup walks its segment kind by kind
-// and neighbour by neighbour, so a wave emits one 8x8 tile's jobs of one slot at a time.
+// from one pass over the pixel's salted stream.  A workgroup walks its segment direction by
+// direction and neighbour by neighbour, a wave one 8x8 tile and one slot at a time -- but that
+// walk only DECIDES: per pixel the neighbour draws, the 16-byte summary (forward) or surface
+// word (backward), want / act and the zero result of a wanted job that cannot run.  An active
+// job becomes a 16-byte descriptor in one of the wave's three LDS bins, chosen by the path its
+// first emit takes (job_kind: L / C / B).  Whenever a bin holds 64 descriptors the wave RUNS
+// them: each lane takes one, gathers the domain's surface record and camera point and the
+// sample's two seeds, and the wave executes job_init, job_emit<kind> and job_finish on 64 jobs
+// of one kind -- not on a tile's mixture of kinds, one path after the other with part of the
+// lanes idle.  Partly filled bins carry over from tile to tile and from the forward to the
+// backward direction; only the segment's last drains run partly filled.  The bins are
+// wave-local (no barrier: a wave's LDS accesses complete in order), so every drain's trip
+// count is wave-uniform, as job_emit / job_keep / wave_alloc need.  Job ids, jres / jstate
+// slots and each job's arithmetic are those of the per-tile form; the lane that runs a job,
+// the segment's ray order and its active lists' order differ (results never depend on them).
 constexpr uint32_t kMaxPrefetch = 3u;  // neighbours whose data wspatial_start gathers up front
 #ifndef SPATIAL_START_WAVES
-#define SPATIAL_START_WAVES 3  // the shared surface + one job: 128 VGPRs spill 108 B/lane
+// The binned kernel: 128 VGPRs, no scratch, 4 waves per SIMD under a floor of 3 (the per-tile
+// form: 168 VGPRs + 44 B/lane, 3 waves).  A floor of 4 gives 125 VGPRs + 20 B/lane and the same
+// speed (551.8-553.5 Msamples/s against 551.6-552.4, same box, 4 runs each); 5 gives 96 VGPRs +
+// 144 B/lane and loses 2 % (539.6-547.7 against 551.9-553.8): profiles/spatial_bins/.
+#define SPATIAL_START_WAVES 3
 #endif
+// A bin holds < 64 descriptors between pushes and a push adds <= 64: 128 entries.  24 KiB per
+// workgroup (4 waves x 3 bins x 128 x 16 B), whatever seg_px is: 4 workgroups per CU, all that
+// a 4-wave register budget admits, take 96 of the CU's 160 KiB.
+constexpr uint32_t kBinCap = 128u;
+// descriptor: {domain pixel, sample ref (band indices), domain x | y << 16, length | k << 8 | slot << 16}
+__device__ __forceinline__ uint32_t bin_push(uint4 *bin, uint32_t cnt, bool p, uint4 d) {
+    const unsigned long long m = __ballot(p);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (p) bin[cnt + rank] = d;  // (cnt < 64, rank < 64)
+    return cnt + (uint32_t)__popcll(m);
+}
+// Run descriptors bin[first .. first + n) (n <= 64, wave-uniform), one per lane.
+template <int KIND>
+__device__ __forceinline__ void spatial_drain(const Scene &sc, const Seg &g, const JobLists &JL, const ReuseArgs &A,
+                                              const uint4 *bin, uint32_t first, uint32_t n) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool act = lane < n;
+    uint32_t jid = 0u, s0 = 0u;
+    Job s;
+    if (act) {
+        const uint4 d = bin[first + lane];
+        const int32_t dom = (int32_t)d.x, ref = (int32_t)d.y;
+        const uint32_t slot = d.w >> 16;
+        jid = job_id(A, (slot & 1u) ? d.y : d.x, slot);  // (the job's pixel: the domain forward, the sample backward)
+        Surface X1{};
+        uint32_t mref = 0u;
+        (void)surf_load(sc, A.surf, dom, X1, mref);  // (a job exists only where the domain has a hit)
+        const uint4 b = res_at(A.cur, ref)[0];
+        job_init(s, x0_of(sc, d.z & 0xffffu, d.z >> 16), X1, mref, ref, d.w & 0xffu, b.y, dom, (d.w >> 8) & 0xffu, true);
+        s0 = b.x;
+    }
+    const bool live = job_emit<KIND>(sc, g, A, act, s, jid, s0);
+    job_finish(g, JL, A, live, s, jid);
+}
 __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(SPATIAL_START_WAVES, 8)))
 void wspatial_start(Scene sc, WaveBufs w, ReuseArgs A) {
     PTX_WAVE_TIMER(sc, KID_SPAT_START | (w.seg_base ? 0x80u : 0u));
     __shared__ uint32_t lds[3];
+    __shared__ uint4 bins[(WB / 64u) * 3u * kBinCap];
     const JobLists JL = job_lists(w, lds);
     const Seg g = seg_begin(w, 0u, lds);
     const uint32_t np = padded_pixels(sc), M = A.neighbors;
-    for (uint32_t base = 0; base < w.seg_px * 2u; base += WB) {  // workgroup-uniform
+    uint4 *const binL = bins + (threadIdx.x >> 6) * (3u * kBinCap), *const binC = binL + kBinCap,
+                *const binB = binC + kBinCap;
+    uint32_t cntL = 0u, cntC = 0u, cntB = 0u;  // wave-uniform
+    // one more trip than the segment's two directions: it decides nothing and empties the bins
+    for (uint32_t base = 0; base <= w.seg_px * 2u; base += WB) {  // workgroup-uniform
+        const bool flush = base >= w.seg_px * 2u;
         const bool backward = base >= w.seg_px;
-        const uint32_t q = seg_pixel(w, g.j, base % w.seg_px);
-        uint32_t x = 0u, y = 0u, pix = 0u, seed = 0u, mref = 0u;
+        const uint32_t q = flush ? np : seg_pixel(w, g.j, base % w.seg_px);
+        uint32_t x = 0u, y = 0u, pix = 0u, seed = 0u;
         bool valid = false, canon = false;
-        Surface X1{};
-        f3 x0{};
-        uint4 c0 = make_uint4(0u, 0u, 0u, 0u);
-        uint32_t clen = 0u, ck = 0u;
+        uint32_t clk = 0u;  // backward: this pixel's sample's length | k << 8
         if (q < np && tile_xy(sc, q, x, y)) {
             pix = (y - sc.row_begin) * sc.width + x;
             seed = reuse_seed(sc, x, y, SALT_SPATIAL);
-            if (!backward) {
-                valid = surf_load(sc, A.surf, pix, X1, mref);
-                if (valid) x0 = x0_of(sc, x, y);
-            } else {
-                valid = A.surf[2u * (size_t)pix].w != kNoSurface;
+            valid = A.surf[2u * (size_t)pix].w != kNoSurface;
+            if (backward) {
                 const uint4 *rc = A.cur + 8u * (size_t)pix;  // this pixel's sample, shifted to each neighbour
                 const uint4 r5 = rc[5];
                 canon = valid && rc[7].y != 0u && r5.w >= 2u && asf(rc[6].x) > 0.0f;
-                if (canon) { c0 = rc[0]; clen = r5.w; ck = r5.x & 0xffu; }
+                if (canon) clk = (r5.w & 0xffu) | ((r5.x & 0xffu) << 8);
             }
         }
-        // every neighbour's offset first, then its summary + seeds (forward) or surface record
-        // (backward) for all of them in one round trip, then the jobs one by one
-        uint32_t nxy[kMaxPrefetch];
+        // every neighbour's offset first, then its summary (forward) or surface word (backward)
+        // for all of them in one round trip, then the descriptors one neighbour at a time
+        uint32_t nxy[kMaxPrefetch], pw[kMaxPrefetch], pp[kMaxPrefetch];
         int32_t nidx[kMaxPrefetch];
-        uint4 pa[kMaxPrefetch], pb[kMaxPrefetch];
         const uint32_t MP = M < kMaxPrefetch ? M : kMaxPrefetch;
 #pragma unroll
         for (uint32_t m = 0; m < kMaxPrefetch; ++m) {
@@ -888,57 +947,69 @@ void wspatial_start(Scene sc, WaveBufs w, ReuseArgs A) {
         }
 #pragma unroll
         for (uint32_t m = 0; m < kMaxPrefetch; ++m) {
-            pa[m] = make_uint4(0u, 0u, 0u, kNoSurface);
-            pb[m] = make_uint4(0u, 0u, 0u, 0u);
+            pw[m] = kNoSurface;
+            pp[m] = 0u;
             if (nxy[m] != 0xffffffffu) {
-                if (!backward) { pa[m] = A.nbr[nidx[m]]; pb[m] = A.cur[8 * (ptrdiff_t)nidx[m]]; }
-                else if (canon) { pa[m] = A.surf[2 * (ptrdiff_t)nidx[m]]; pb[m] = A.surf[2 * (ptrdiff_t)nidx[m] + 1]; }
+                if (!backward) { const uint4 a = A.nbr[nidx[m]]; pp[m] = a.x; pw[m] = a.w; }
+                else if (canon) pw[m] = A.surf[2 * (ptrdiff_t)nidx[m]].w;
             }
         }
-        for (uint32_t m = 0; m < M; ++m) {  // uniform
-            const uint32_t jid = job_id(A, pix, 2u * m + (backward ? 1u : 0u));
+        const uint32_t trips = flush ? 1u : M, full = flush ? 1u : 64u;
+        for (uint32_t m = 0; m < trips; ++m) {  // uniform
             bool act = false;
-            uint32_t s0 = 0u;
-            Job s;
+            uint4 d = make_uint4(0u, 0u, 0u, 0u);
             if (valid) {
-                uint32_t nx = 0u, ny = 0u, pxy = 0xffffffffu;
+                const uint32_t slot = 2u * m + (backward ? 1u : 0u);
+                uint32_t pxy = 0xffffffffu, aw = kNoSurface, ap = 0u;
                 int32_t ni = 0;
-                uint4 a = make_uint4(0u, 0u, 0u, kNoSurface), b = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
                 for (uint32_t k = 0; k < kMaxPrefetch; ++k)
-                    if (k == m) { pxy = nxy[k]; ni = nidx[k]; a = pa[k]; b = pb[k]; }
+                    if (k == m) { pxy = nxy[k]; ni = nidx[k]; aw = pw[k]; ap = pp[k]; }
                 if (m >= kMaxPrefetch) {  // (more neighbours than prefetched: this one's draws now)
                     uint32_t sm = reuse_seed(sc, x, y, SALT_SPATIAL) + 2u * m;  // draws 2m, 2m + 1
+                    uint32_t nx = 0u, ny = 0u;
                     if (spatial_neighbor(sm, A.radius, x, y, sc.width, sc.height, nx, ny)) {
                         pxy = nx | (ny << 16);
                         ni = band_index(sc, nx, ny);
-                        if (!backward) { a = A.nbr[ni]; b = A.cur[8 * (ptrdiff_t)ni]; }
-                        else if (canon) { a = A.surf[2 * (ptrdiff_t)ni]; b = A.surf[2 * (ptrdiff_t)ni + 1]; }
+                        if (!backward) { const uint4 a = A.nbr[ni]; ap = a.x; aw = a.w; }
+                        else if (canon) aw = A.surf[2 * (ptrdiff_t)ni].w;
                     }
                 }
                 const bool present = pxy != 0xffffffffu;
-                nx = pxy & 0xffffu; ny = pxy >> 16;
                 bool want = false;
                 if (present && !backward) {  // the neighbour's sample in this pixel's domain
-                    const Nbr nb = a.w != kNbrEscape ? nbr_unpack(a) : nbr_at(A, ni);
+                    const Nbr nb = aw != kNbrEscape ? nbr_unpack(make_uint4(ap, 0u, 0u, aw)) : nbr_at(A, ni);
                     want = nb.valid && nb.length >= 2u && nb.p > 0.0f;
                     act = want && nb.C != 0u;
-                    if (act) { job_init(s, x0, X1, mref, ni, nb.length, b.y, (int32_t)pix, nb.k, true); s0 = b.x; }
+                    d = make_uint4(pix, (uint32_t)ni, x | (y << 16),
+                                   (nb.length & 0xffu) | ((nb.k & 0xffu) << 8) | (slot << 16));
                 } else if (present && canon) {  // this pixel's sample in the neighbour's domain
-                    want = act = a.w != kNoSurface;
-                    if (act) {
-                        Surface Xn;
-                        Xn.pos = mk(asf(a.x), asf(a.y), asf(a.z));
-                        Xn.nrm = mk(asf(b.x), asf(b.y), asf(b.z));
-                        Xn.mat = material_at(sc, a.w);
-                        job_init(s, x0_of(sc, nx, ny), Xn, a.w, (int32_t)pix, clen, c0.y, ni, ck, true);
-                        s0 = c0.x;
-                    }
+                    want = act = aw != kNoSurface;
+                    d = make_uint4((uint32_t)ni, pix, pxy, clk | (slot << 16));
                 }
-                if (want && !act) A.jres[jid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (want && !act) A.jres[job_id(A, pix, slot)] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
-            const bool live = job_emit(sc, g, A, act, s, jid, s0);
-            job_finish(g, JL, A, live, s, jid);
+            const int kind = job_kind(d.w & 0xffu, (d.w >> 8) & 0xffu);
+            cntL = bin_push(binL, cntL, act && kind == JK_L, d);
+            cntC = bin_push(binC, cntC, act && kind == JK_C, d);
+            cntB = bin_push(binB, cntB, act && kind == JK_B, d);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the pushes before the drains' reads
+            if (cntL >= full) {
+                const uint32_t n = min(cntL, 64u);
+                cntL -= n;
+                spatial_drain<JK_L>(sc, g, JL, A, binL, cntL, n);
+            }
+            if (cntC >= full) {
+                const uint32_t n = min(cntC, 64u);
+                cntC -= n;
+                spatial_drain<JK_C>(sc, g, JL, A, binC, cntC, n);
+            }
+            if (cntB >= full) {
+                const uint32_t n = min(cntB, 64u);
+                cntB -= n;
+                spatial_drain<JK_B>(sc, g, JL, A, binB, cntB, n);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the drains' reads before the next pushes
         }
     }
     job_seg_end(w, g, JL);
