@@ -143,7 +143,11 @@ int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const
                      size_t n_geometry, const uint32_t *accel, size_t n_accel);
 int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]);
 /* Run the configured pipeline for the current frame; if rgba_out != NULL copy the band's
- * accumulated RGBA f32 image (band_h * W * 4) into it (blocking). Otherwise asynchronous. */
+ * accumulated RGBA f32 image (band_h * W * 4) into it (blocking). Otherwise asynchronous.
+ * While camera (uniform words 0, 1, 4..22), layout key, band and scene are the ones a frame
+ * context's G-buffer was traced for, a frame keeps that G-buffer instead of tracing the primary
+ * rays again (same bits: PT_01 reads no frame word); ptx_run_pass / ptx_run_passes always run
+ * the G-buffer pass they are given. */
 int ptx_render(ptx_handle *h, float *rgba_out);
 /* (reuse pipeline: whole-image handles only -- a band needs the halo exchange between its
  *  passes, see ptx_halo_*) */
@@ -201,12 +205,15 @@ int ptx_synchronize(ptx_handle *h);
 int ptx_get_stats(ptx_handle *h, ptx_stats *out);
 int ptx_reset_stats(ptx_handle *h);
 int ptx_read_buffer(ptx_handle *h, int which, void *host_dst, size_t bytes);
+/* A G-buffer written by the host is overwritten by the next frame on that frame context exactly
+ * as before (the write drops the kept G-buffer); an unchanged camera alone no longer re-traces it. */
 int ptx_write_buffer(ptx_handle *h, int which, const void *host_src, size_t bytes);
 /* A buffer's device address.  On a handle whose frames are pipelined (whole-image reuse
  * pipeline on its own stream: two frames in flight) the G-buffer and
  * reservoir buffers alternate between two allocations frame by frame: the pointer returned
  * for PTX_BUF_GBUFFER / PTX_BUF_RESERVOIR is valid until the next ptx_render.  Accumulation,
- * history and counters never move. */
+ * history and counters never move.  After the G-buffer's pointer was handed out the handle
+ * traces the G-buffer every frame again (the caller may write it at any time). */
 int ptx_device_pointer(ptx_handle *h, int which, void **dev_ptr, size_t *bytes);
 /* The reference's render pass (Renderer_TEST.Render, GC/Renderer_TEST.ts:233-255: a fullscreen
  * quad, SH/VertexShader.wgsl + SH/FragmentShader.wgsl:7-10) onto a canvas_w x canvas_h canvas:

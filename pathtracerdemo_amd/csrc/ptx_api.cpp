@@ -84,8 +84,33 @@ int fail(ptx_handle *h, int code, const char *fmt, ...) {
         vsnprintf(buf, sizeof buf, fmt, ap);
         va_end(ap);
         h->err = buf;
+        gbuf_key_drop_all(h);  // (a failed enqueue may have left any context's G-buffer half written)
     }
     return code;
+}
+// The G-buffer key: what PT_01's output depends on besides the scene arrays (whose upload drops
+// every key) -- uniform words 0, 1 (resolution) and 4..22 (the camera words hist_camera compares:
+// VP^-1 and the camera position), the layout key (words 24..31) and the band.
+void gbuf_key_of(const ptx_handle *h, uint32_t *key) {
+    static_assert(ptx_handle::kGbufKeyWords == 2 + 19 + 8 + 3, "G-buffer key words");
+    key[0] = h->uniform[0];
+    key[1] = h->uniform[1];
+    std::memcpy(key + 2, h->uniform + 4, 19 * sizeof(uint32_t));
+    std::memcpy(key + 21, h->uniform + 24, 8 * sizeof(uint32_t));
+    key[29] = h->cfg.row_begin;
+    key[30] = h->band_h;
+    key[31] = h->halo_top;
+}
+void gbuf_key_drop(ptx_handle *h) { h->gbuf_key_valid = false; }
+void gbuf_key_drop_all(ptx_handle *h) { h->gbuf_key_valid = h->alt.gbuf_key_valid = h->alt2.gbuf_key_valid = false; }
+// whether a frame with the handle's uniform may keep the current context's G-buffer
+// (PTX_AB=GBUF_KEEP=0: every frame traces it, A/B)
+static bool gbuf_kept(const ptx_handle *h) {
+    static const bool keep_on = ab_knob("GBUF_KEEP", 1) != 0;
+    if (!keep_on || !h->gbuf_key_valid || h->gbuf_exposed) return false;
+    uint32_t key[ptx_handle::kGbufKeyWords];
+    gbuf_key_of(h, key);
+    return std::memcmp(key, h->gbuf_key, sizeof key) == 0;
 }
 void free_buf(DevBuf &b) {
     if (b.p) (void)hipFree(b.p);
@@ -134,6 +159,10 @@ int read_to_host(ptx_handle *h, void *dst, const void *src, size_t bytes) {
 
 int alloc_buf(ptx_handle *h, DevBuf &b, size_t bytes) {
     if (b.bytes == bytes && b.p) return PTX_OK;
+    // a G-buffer in new storage holds nothing a frame could keep
+    if (h && &b == &h->d_gbuf) h->gbuf_key_valid = false;
+    else if (h && &b == &h->alt.gbuf) h->alt.gbuf_key_valid = false;
+    else if (h && &b == &h->alt2.gbuf) h->alt2.gbuf_key_valid = false;
     free_buf(b);
     if (bytes == 0) return PTX_OK;
     hipError_t e = hipMalloc(&b.p, bytes);
@@ -428,6 +457,7 @@ int build_layout(ptx_handle *h) {
         return fail(h, PTX_E_SCENE, "BLAS depth %u needs more LDS than a CU has", max_depth);
     h->layout_valid = true;
     h->surf_valid = h->alt.surf_valid = h->alt2.surf_valid = false;  // the surface records name the old layout's materials
+    gbuf_key_drop_all(h);  // (the G-buffers hold hits in the old layout)
     return PTX_OK;
 }
 
@@ -933,7 +963,7 @@ static hipError_t spatial_overlap_seq(ptx_handle *h, const Scene &sc, const Wave
 }
 
 hipError_t launch_wave_parts(ptx_handle *h, const Scene &sc, const WaveBufs &w, const int *passes, int npasses,
-                             bool summaries, const WaveBufs *then, hipEvent_t then_wait) {
+                             bool summaries, const WaveBufs *then, hipEvent_t then_wait, bool keep_gbuf) {
     // (PTX_AB=OVERLAP_START=0: the overlapped band pass as two whole sequences, one per tile set)
     static const bool overlap_start = ab_knob("OVERLAP_START", 1) != 0;
     if (then && overlap_start && npasses == 2 && passes[0] == PTX_PASS_SPATIAL && passes[1] == PTX_PASS_FINAL &&
@@ -972,12 +1002,20 @@ hipError_t launch_wave_parts(ptx_handle *h, const Scene &sc, const WaveBufs &w, 
     k = std::max(1, std::min<int>(k, ptx_handle::kMaxSplit));
     if ((uint32_t)k > std::max(w.nseg, then ? then->nseg : 0u)) k = (int)std::max(w.nseg, then ? then->nseg : 0u);
     hipError_t e = hipSuccess;
+    // a frame whose G-buffer key (camera, layout, band) is the one this context's G-buffer was
+    // traced for keeps it: the G-buffer entry enqueues nothing, on any part
+    bool has_gbuf = false;
+    for (int i = 0; i < npasses; ++i) has_gbuf |= passes[i] == PTX_PASS_GBUFFER;
+    const bool skip_gbuf = has_gbuf && keep_gbuf && gbuf_kept(h);
+    if (has_gbuf && !skip_gbuf) h->gbuf_key_valid = false;  // (set again once every part is enqueued)
     // the spatial pass gathers neighbours (halo rows included) through their summaries: the
     // temporal pass wrote the band's; halo rows (just received) or a band whose buffers were
     // written since get them here
     for (int i = 0; i < npasses; ++i) {
         if (passes[i] == PTX_PASS_SPATIAL) {
             if (summaries && (e = spatial_summaries(h, h->stream)) != hipSuccess) return e;
+        } else if (passes[i] == PTX_PASS_GBUFFER && skip_gbuf) {
+            continue;  // (nothing rewritten)
         } else if (passes[i] != PTX_PASS_FINAL && passes[i] != PTX_PASS_TEMPORAL && passes[i] != kPassTemporalJobs &&
                    passes[i] != kPassTemporalCombine && !is_motion_pass(passes[i])) {
             h->nbr_valid = false;  // G-buffer / PT_1 / MCPT rewrite what the summaries describe
@@ -988,7 +1026,7 @@ hipError_t launch_wave_parts(ptx_handle *h, const Scene &sc, const WaveBufs &w, 
     bool need_surf[8] = {false};
     bool surf_ok = h->surf_valid;
     for (int i = 0; i < npasses && i < 8; ++i) {
-        if (passes[i] == PTX_PASS_GBUFFER) surf_ok = false;
+        if (passes[i] == PTX_PASS_GBUFFER) surf_ok = surf_ok && skip_gbuf;  // (a kept G-buffer keeps its records)
         else if (passes[i] == PTX_PASS_INIT && w.surf) surf_ok = true;
         else if ((passes[i] == PTX_PASS_TEMPORAL || passes[i] == kPassTemporalJobs || passes[i] == PTX_PASS_SPATIAL ||
                   is_motion_pass(passes[i])) &&
@@ -1032,6 +1070,7 @@ hipError_t launch_wave_parts(ptx_handle *h, const Scene &sc, const WaveBufs &w, 
             if (!part.seg_count) continue;
             for (int i = 0; i < npasses; ++i) {
                 if (passes[i] == PTX_PASS_GBUFFER) {
+                    if (skip_gbuf) continue;
                     TimedLaunch *t = event_begin(h, PTX_PASS_GBUFFER, st);
                     e = wave_gbuffer(sc, part, gbuf_band(h), h->stack_depth, st);
                     h->init_state_valid = false;  // PT_1's state described the previous G-buffer
@@ -1052,6 +1091,10 @@ hipError_t launch_wave_parts(ptx_handle *h, const Scene &sc, const WaveBufs &w, 
     for (int q = 1; q < k; ++q) {
         if ((e = hipEventRecord(h->ev_join[q], h->sub[q])) != hipSuccess) return e;
         if ((e = hipStreamWaitEvent(h->stream, h->ev_join[q], 0)) != hipSuccess) return e;
+    }
+    if (has_gbuf && !skip_gbuf) {  // every part's G-buffer launch is enqueued
+        gbuf_key_of(h, h->gbuf_key);
+        h->gbuf_key_valid = true;
     }
     // the temporal pass rewrote the reservoirs PT_1's state describes, and summarised them
     for (int i = 0; i < npasses; ++i)
@@ -1208,6 +1251,8 @@ static void swap_two(ptx_handle *h) {
     std::swap(h->init_state_valid, a.init_state_valid);
     std::swap(h->nbr_valid, a.nbr_valid);
     std::swap(h->surf_valid, a.surf_valid);
+    std::swap(h->gbuf_key_valid, a.gbuf_key_valid);
+    std::swap_ranges(h->gbuf_key, h->gbuf_key + ptx_handle::kGbufKeyWords, a.gbuf_key);
 }
 // the second context's G-buffer, reservoirs and stream (its queues, wave state and summaries
 // are allocated by wave_buffers / reuse_buffers on its first frame)
@@ -1311,7 +1356,7 @@ static int timed_wave_frame(ptx_handle *h) {
         // ReSTIR: G-buffer + PT_1 of this frame overlap the previous frame's PT_4, whose
         // accumulation this frame's PT_4 follows (ev_prev)
         static const int front[2] = {PTX_PASS_GBUFFER, PTX_PASS_INIT}, back[1] = {PTX_PASS_FINAL};
-        e = launch_wave_parts(h, sc, w, front, 2);
+        e = launch_wave_parts(h, sc, w, front, 2, true, nullptr, nullptr, true);
         if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_prev, 0);
         if (e == hipSuccess) e = launch_wave_parts(h, sc, w, back, 1);
     } else if (pipe) {
@@ -1330,7 +1375,7 @@ static int timed_wave_frame(ptx_handle *h) {
         static const int temporal[1] = {PTX_PASS_TEMPORAL}, temporal_b[1] = {kPassTemporalCombine};
         static const int temporal_m[1] = {kPassTemporalMotion};
         static const int back[2] = {PTX_PASS_SPATIAL, PTX_PASS_FINAL};
-        e = launch_wave_parts(h, sc, w, front, 2);
+        e = launch_wave_parts(h, sc, w, front, 2, true, nullptr, nullptr, true);
         if (e == hipSuccess && split && !moved) e = launch_wave_parts(h, sc, w, jobs, 1);
         if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_prev, 0);
         if (e == hipSuccess)
@@ -1344,12 +1389,12 @@ static int timed_wave_frame(ptx_handle *h) {
         static const int front[3] = {PTX_PASS_GBUFFER, PTX_PASS_INIT, PTX_PASS_TEMPORAL};
         static const int front_m[3] = {PTX_PASS_GBUFFER, PTX_PASS_INIT, kPassTemporalMotion};
         static const int back[2] = {PTX_PASS_SPATIAL, PTX_PASS_FINAL};
-        e = launch_wave_parts(h, sc, w, moved ? front_m : front, 3);
+        e = launch_wave_parts(h, sc, w, moved ? front_m : front, 3, true, nullptr, nullptr, true);
         if (e == hipSuccess) e = launch_wave_parts(h, sc, w, back, 2);
         if (e == hipSuccess) mark_history(h);
     } else {
         static const int passes[3] = {PTX_PASS_GBUFFER, PTX_PASS_INIT, PTX_PASS_FINAL};
-        e = launch_wave_parts(h, sc, w, passes, 3);
+        e = launch_wave_parts(h, sc, w, passes, 3, true, nullptr, nullptr, true);
     }
     if (e != hipSuccess) return fail(h, PTX_E_HIP, "wavefront frame launch: %s", hipGetErrorString(e));
     HIP_CHECK(h, hipEventRecord(t.stop, h->stream));
@@ -1404,6 +1449,10 @@ static int timed_launch(ptx_handle *h, int pass) {
         h->init_state_valid = false;
         h->nbr_valid = false;
         h->surf_valid = false;
+        // an explicit pass always runs; it leaves the G-buffer of the uniform it ran with (the
+        // one-thread-per-pixel and counting handles never keep one)
+        h->gbuf_key_valid = e == hipSuccess && !(fl & (PTX_FLAG_SIMPLE_KERNELS | PTX_FLAG_COUNT_WORK));
+        if (h->gbuf_key_valid) gbuf_key_of(h, h->gbuf_key);
         break;
     case PTX_PASS_INIT:
         e = launch_init(sc, gb, res, d, h->stream);
@@ -1573,6 +1622,7 @@ int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const
     h->init_state_valid = false;
     h->nbr_valid = false;
     h->surf_valid = h->alt.surf_valid = h->alt2.surf_valid = false;
+    gbuf_key_drop_all(h);  // (hits in the old scene)
     if (h->frame_set) return build_layout(h);
     return PTX_OK;
 }
@@ -1588,6 +1638,7 @@ int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]) {
     if (std::memcmp(key, h->layout_key, sizeof key) != 0) {
         std::memcpy(h->layout_key, key, sizeof key);
         h->layout_valid = false;
+        gbuf_key_drop_all(h);
     }
     std::memcpy(h->uniform, uniform, sizeof h->uniform);
     h->frame_set = true;
@@ -1680,6 +1731,7 @@ static int halo_copy(ptx_handle *h, uint32_t r0, uint32_t rows, void *msg, bool 
         HIP_CHECK(h, hipMemcpyAsync(m, g, gb, hipMemcpyDefault, h->stream));
         HIP_CHECK(h, hipMemcpyAsync(m + gb, r, rb, hipMemcpyDefault, h->stream));
     } else {
+        gbuf_key_drop(h);  // (rows of the G-buffer written from outside the frame path)
         HIP_CHECK(h, hipMemcpyAsync(g, m, gb, hipMemcpyDefault, h->stream));
         HIP_CHECK(h, hipMemcpyAsync(r, m + gb, rb, hipMemcpyDefault, h->stream));
     }
@@ -1848,6 +1900,7 @@ int ptx_write_buffer(ptx_handle *h, int which, const void *host_src, size_t byte
     h->init_state_valid = false;  // the wave state no longer matches the buffers
     h->nbr_valid = false;
     h->surf_valid = false;  // (a G-buffer write: the surface records describe the old one)
+    if (which == PTX_BUF_GBUFFER) gbuf_key_drop(h);  // the next frame on this context traces it again
     return PTX_OK;
 }
 
@@ -1857,6 +1910,10 @@ int ptx_device_pointer(ptx_handle *h, int which, void **dev_ptr, size_t *bytes) 
     if (!buffer_view(h, which, b)) return fail(h, PTX_E_INVALID, "unknown buffer %d", which);
     *dev_ptr = b.p;
     if (bytes) *bytes = b.bytes;
+    if (which == PTX_BUF_GBUFFER) {  // the caller may write it whenever it likes: nothing is kept
+        h->gbuf_exposed = true;
+        gbuf_key_drop_all(h);
+    }
     return PTX_OK;
 }
 
@@ -1962,6 +2019,7 @@ int ptx_set_stream(ptx_handle *h, void *hip_stream) {
     if (!h) return PTX_E_INVALID;
     if (int rc = leave_alt(h)) return rc;
     h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
+    gbuf_key_drop_all(h);  // (the orders of two streams are not related)
     return PTX_OK;
 }
 

@@ -284,7 +284,8 @@ int band_front(ptx_handle *h, const Scene &sc, const WaveBufs &w, TimedLaunch *&
     static const int front[3] = {PTX_PASS_GBUFFER, PTX_PASS_INIT, PTX_PASS_TEMPORAL};
     static const int front_split[3] = {PTX_PASS_GBUFFER, PTX_PASS_INIT, kPassTemporalJobs};
     // (the temporal jobs before the wait, the temporal combine after: timed_wave_frame)
-    const hipError_t e = launch_wave_parts(h, sc, w, pipe ? front_split : front, moved ? 2 : 3);
+    const hipError_t e = launch_wave_parts(h, sc, w, pipe ? front_split : front, moved ? 2 : 3, true, nullptr, nullptr,
+                                           true);
     if (e != hipSuccess) return fail(h, PTX_E_HIP, "band front passes: %s", hipGetErrorString(e));
     if (pipe) HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_prev, 0));
     return PTX_OK;
