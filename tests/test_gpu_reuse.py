@@ -340,6 +340,38 @@ def test_pipelined_frames_interleaved_with_host_ops(scene3, oracle_mod, native):
     r.close()
 
 
+def test_set_stream_between_pipelined_frames(scene3, oracle_mod):
+    """ptx_set_stream on a handle whose current frame context is not the first (an odd number of
+    pipelined frames): the handle goes back to its first context, which then runs on the
+    handle's own stream, on a caller's stream (one frame at a time) and on its own again; every
+    frame still follows the one before it."""
+    import torch
+    O, W, H = oracle_mod, 96, 64
+    fr = oracle_frame(O, scene3, W, H)
+    r = reuse_renderer(scene3, W, H)
+    stream = torch.cuda.Stream()
+
+    def frames(*fs):
+        for f in fs:
+            fr.set_frame_index(f)
+            fr.run_reuse_frame(threads=8)
+            r.Update()
+            r.Render()
+
+    frames(1, 2, 3)  # (the second context is current)
+    r.set_stream(None)
+    frames(4, 5)
+    r.synchronize()  # the caller orders its stream after the handle's: ptx_set_stream relates no two streams
+    r.set_stream(stream.cuda_stream)
+    frames(6)
+    stream.synchronize()
+    r.set_stream(None)
+    frames(7)
+    assert_same(r.read_history(), fr.res_hist, "spatial output")
+    assert_same(r.read_image(), fr.accum, "accumulated radiance")
+    r.close()
+
+
 def test_pipelined_frames_beside_another_handle(scene1, scene3, oracle_mod):
     """A reuse handle created while another handle is alive (smoke()'s order): its one-time
     clears must be done before its non-blocking streams start (a null-stream hipMemset still
