@@ -79,6 +79,7 @@ extern "C" {
 #define PTX_STAT_FINAL_FUSED 11 /* count only (no time): PT_4 passes of the reuse pipeline that
                                    walked their replays inside their one logic launch
                                    (wfinal_one), so none of their queries reached trace_queue */
+#define PTX_STAT_DENOISE 12  /* launches of the denoiser's kernels (ms with PTX_FLAG_TIME_LAUNCHES) */
 
 /* buffers for ptx_read_buffer / ptx_write_buffer / ptx_device_pointer */
 #define PTX_BUF_GBUFFER 0    /* band_h * W * 4 u32   */
@@ -91,6 +92,7 @@ extern "C" {
 #define PTX_BUF_RESERVOIR_HIST 4 /* band_h * W * 32 u32: spatial output = Final's input and the
                                     next frame's temporal history (reuse pipeline)           */
 #define PTX_BUF_DIRECT 5     /* band_h * W * 4 f32: direct light of the GI init pass (GI pipeline) */
+#define PTX_BUF_DENOISED 6   /* band_h * W * 4 f32: ptx_denoise's output (read-only; exists after the first call) */
 
 #define PTX_FLAG_COUNT_WORK 1u     /* count rays / AABB / triangle tests on device (slower)   */
 #define PTX_FLAG_SIMPLE_KERNELS 2u   /* A/B: one thread per pixel, no ray exchange            */
@@ -235,6 +237,26 @@ int ptx_present(ptx_handle *h, uint32_t canvas_w, uint32_t canvas_h, int bgra, u
  * the frame it was enqueued after. */
 int ptx_present_async(ptx_handle *h, uint32_t canvas_w, uint32_t canvas_h, int bgra);
 int ptx_present_poll(ptx_handle *h, uint8_t *out, size_t bytes);
+/* The edge-avoiding a-trous wavelet filter of the accumulated image (Denoiser): guided
+ * by the primary hit of the current frame context's G-buffer (same instance and sub-mesh, normal,
+ * plane distance), luminance variance estimated from the image itself, so it fades as the image
+ * converges.  Asynchronous: enqueued on the handle's stream behind the frame last rendered, exactly
+ * where ptx_present_async enqueues (a pipelined handle's next frame accumulates after it).  Reads
+ * the accumulation and the G-buffer; writes only its own buffers (allocated by the first call,
+ * counted in device_bytes): PTX_BUF_DENOISED holds rgb after the last iteration, alpha 1; a pixel
+ * without a primary hit keeps its colour.  The camera position is the one of the uniform set on
+ * the handle: call it before the next frame's ptx_set_frame.  Whole-image handles of the pipelines with a G-buffer
+ * after at least one frame; anything else, or a parameter out of range, is PTX_E_INVALID. */
+typedef struct ptx_denoise_params {
+    uint32_t iterations;      /* 1..6 (step 2^i in iteration i); 0 = default 5 */
+    float sigma_lum;          /* luminance edge stop, in standard deviations; 0 = default 4 */
+    float sigma_plane;        /* plane-distance edge stop, as a fraction of the distance to the camera; 0 = default 0.02 */
+    uint32_t reserved[5];
+} ptx_denoise_params;
+int ptx_denoise(ptx_handle *h, const ptx_denoise_params *p /* NULL = defaults */);
+/* What ptx_present and ptx_present_async read: PTX_BUF_ACCUM (the default) or PTX_BUF_DENOISED
+ * (fails before the first ptx_denoise). */
+int ptx_present_source(ptx_handle *h, int which);
 /* What this libptx.so is, as one JSON object in `out` (NUL-terminated, truncated to `bytes`):
  * {"abi": 5, "build": "product" | "ab" (every PTX_AB switch live: the measurement build) | "wgt"
  *  (per-wave timing), "arch": "gfx950", "ptx_ab": <PTX_AB as read>, "ptx_ab_ignored": [keys this

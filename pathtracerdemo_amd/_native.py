@@ -23,8 +23,10 @@ PTX_PASS_TEMPORAL, PTX_PASS_SPATIAL = 8, 9
 PTX_STAT_WAVE_TRACE, PTX_STAT_WAVE_LOGIC, PTX_STAT_FRAME = 5, 6, 7  # stats-only slots (include/ptx.h)
 PTX_STAT_PASS_GROUP = 10
 PTX_STAT_FINAL_FUSED = 11
+PTX_STAT_DENOISE = 12  # launches of the denoiser's kernels
 PTX_BUF_GBUFFER, PTX_BUF_RESERVOIR, PTX_BUF_ACCUM, PTX_BUF_COUNTERS, PTX_BUF_RESERVOIR_HIST = 0, 1, 2, 3, 4
 PTX_BUF_DIRECT = 5
+PTX_BUF_DENOISED = 6  # ptx_denoise's output (read-only)
 PTX_COUNTER_MOTION_CLIP = 6  # word of PTX_BUF_COUNTERS: pixels a band could not reproject (ptx.h)
 PTX_FLAG_COUNT_WORK = 1
 PTX_FLAG_SIMPLE_KERNELS = 2
@@ -44,7 +46,7 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_trace", "ptx_trace_device", "ptx_run_passes", "ptx_halo_rows", "ptx_halo_pack",
             "ptx_halo_unpack", "ptx_comm_unique_id", "ptx_comm_init", "ptx_comm_init_all", "ptx_render_bands",
             "ptx_row_census", "ptx_comm_info", "ptx_present", "ptx_present_async", "ptx_present_poll",
-            "ptx_build_info"]
+            "ptx_build_info", "ptx_denoise", "ptx_present_source"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -59,6 +61,11 @@ class PtxStats(ctypes.Structure):
                 ("kernel_launches", ctypes.c_uint64 * 16), ("triangles", ctypes.c_uint32),
                 ("bvh_nodes", ctypes.c_uint32), ("instances", ctypes.c_uint32), ("max_bvh_depth", ctypes.c_uint32),
                 ("device_bytes", ctypes.c_uint64)]
+
+
+class PtxDenoiseParams(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_uint32), ("sigma_lum", ctypes.c_float), ("sigma_plane", ctypes.c_float),
+                ("reserved", ctypes.c_uint32 * 5)]
 
 
 class PtxError(RuntimeError):
@@ -116,6 +123,8 @@ def load(path: str = LIB_PATH):
     lib.ptx_present_async.argtypes = [H, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
     lib.ptx_present_poll.argtypes = [H, P, ctypes.c_size_t]
     lib.ptx_build_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+    lib.ptx_denoise.argtypes = [H, ctypes.POINTER(PtxDenoiseParams)]
+    lib.ptx_present_source.argtypes = [H, ctypes.c_int]
     lib.ptx_run_passes.argtypes = [H, P, ctypes.c_int]
     lib.ptx_halo_rows.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
                                   ctypes.POINTER(ctypes.c_size_t)]

@@ -1427,8 +1427,14 @@ static bool buffer_view(ptx_handle *h, int which, DevBuf &v) {
     case PTX_BUF_ACCUM: v = h->d_accum; return true;
     case PTX_BUF_COUNTERS: v = h->d_counters; return true;
     case PTX_BUF_RESERVOIR_HIST: v.p = h->d_hist.p ? hist_band(h) : nullptr; v.bytes = px * 16u * h->res_u4; return v.p != nullptr;
+    case PTX_BUF_DENOISED: v = h->d_denoised; return v.p != nullptr;
     default: return false;
     }
+}
+
+// what ptx_present / ptx_present_async show (ptx_present_source)
+static const float4 *present_texture(const ptx_handle *h) {
+    return (const float4 *)(h->present_src == PTX_BUF_DENOISED ? h->d_denoised.p : h->d_accum.p);
 }
 
 }  // namespace ptx
@@ -1599,7 +1605,9 @@ int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]) {
 int ptx_run_pass(ptx_handle *h, int pass) {
     if (!h) return PTX_E_INVALID;
     HIP_CHECK(h, hipSetDevice(h->device));  // handles of one process may sit on several GPUs
-    return timed_launch(h, pass);
+    const int rc = timed_launch(h, pass);
+    if (rc == PTX_OK) h->rendered = true;
+    return rc;
 }
 
 int ptx_run_passes(ptx_handle *h, const int *passes, int n) {
@@ -1620,6 +1628,7 @@ int ptx_run_passes(ptx_handle *h, const int *passes, int n) {
     if (fl & (PTX_FLAG_SIMPLE_KERNELS | PTX_FLAG_COUNT_WORK)) {
         for (int i = 0; i < n; ++i)
             if (int rc = timed_launch(h, passes[i])) return rc;
+        h->rendered = true;
         return PTX_OK;
     }
     if (!h->scene_loaded || !h->frame_set) return fail(h, PTX_E_INVALID, "scene and frame must be set before rendering");
@@ -1635,6 +1644,7 @@ int ptx_run_passes(ptx_handle *h, const int *passes, int n) {
     if (gb && !tables_fit_lds(sc)) {  // the segment-mapped G-buffer needs LDS tables
         for (int i = 0; i < n; ++i)
             if (int rc = timed_launch(h, passes[i])) return rc;
+        h->rendered = true;
         return PTX_OK;
     }
     WaveBufs w{};
@@ -1652,6 +1662,7 @@ int ptx_run_passes(ptx_handle *h, const int *passes, int n) {
     t.pending = true;
     for (int i = 0; i < n; ++i)
         if (passes[i] == PTX_PASS_SPATIAL) mark_history(h);
+    h->rendered = true;
     return PTX_OK;
 }
 
@@ -1733,6 +1744,7 @@ int ptx_render(ptx_handle *h, float *rgba_out) {
         if (int rc = timed_launch(h, PTX_PASS_MCPT)) return rc;
     }
     h->frames++;
+    h->rendered = true;
     if (rgba_out)
         if (int rc = read_to_host(h, rgba_out, h->d_accum.p, h->d_accum.bytes)) return rc;
     return PTX_OK;
@@ -1768,7 +1780,8 @@ int ptx_get_stats(ptx_handle *h, ptx_stats *out) {
     out->device_bytes = h->d_scene.bytes + h->d_geometry.bytes + h->d_tris.bytes + h->d_nodes.bytes + h->d_subs.bytes +
                         h->d_insts.bytes + h->d_mats.bytes + h->d_tverts.bytes + c.gbuf.bytes + c.res.bytes + h->d_accum.bytes +
                         h->d_hist.bytes + h->d_jstate.bytes + h->d_jres.bytes + c.tjstate.bytes + c.tjres.bytes + c.nbr.bytes +
-                        c.surf.bytes + h->d_psurf.bytes + c.direct.bytes;
+                        c.surf.bytes + h->d_psurf.bytes + c.direct.bytes + h->d_dn_guide.bytes + h->d_dn_work.bytes +
+                        h->d_denoised.bytes;
     return PTX_OK;
 }
 
@@ -1840,6 +1853,7 @@ int ptx_read_buffer(ptx_handle *h, int which, void *host_dst, size_t bytes) {
 int ptx_write_buffer(ptx_handle *h, int which, const void *host_src, size_t bytes) {
     if (!h || !host_src) return PTX_E_INVALID;
     DevBuf b;
+    if (which == PTX_BUF_DENOISED) return fail(h, PTX_E_INVALID, "the denoised image is ptx_denoise's output: read-only");
     if (!buffer_view(h, which, b) || bytes > b.bytes)
         return fail(h, PTX_E_INVALID, "write of %zu bytes to buffer %d", bytes, which);
     HIP_CHECK(h, copy_sync(h, b.p, host_src, bytes, hipMemcpyHostToDevice));
@@ -1874,7 +1888,7 @@ int ptx_present(ptx_handle *h, uint32_t canvas_w, uint32_t canvas_h, int bgra, u
     HIP_CHECK(h, hipSetDevice(h->device));
     const size_t bytes = (size_t)canvas_w * canvas_h * 4u;
     if (int rc = alloc_buf(h, h->d_canvas, bytes)) return rc;
-    const hipError_t e = launch_present((const float4 *)h->d_accum.p, h->cfg.width, h->cfg.height, canvas_w, canvas_h,
+    const hipError_t e = launch_present(present_texture(h), h->cfg.width, h->cfg.height, canvas_w, canvas_h,
                                         bgra != 0, (uint32_t *)h->d_canvas.p, h->cur().stream);
     if (e != hipSuccess) return fail(h, PTX_E_HIP, "ptx_present: %s", hipGetErrorString(e));
     return read_to_host(h, out, h->d_canvas.p, bytes);
@@ -1901,7 +1915,7 @@ int ptx_present_async(ptx_handle *h, uint32_t canvas_w, uint32_t canvas_h, int b
     if (!h->ev_present) HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_present, hipEventDisableTiming));
     // on the current frame's stream, after it: a pipelined handle's next frame records ev_prev
     // on this stream before it enqueues anything, and its accumulation waits for ev_prev
-    const hipError_t e = launch_present((const float4 *)h->d_accum.p, h->cfg.width, h->cfg.height, canvas_w, canvas_h,
+    const hipError_t e = launch_present(present_texture(h), h->cfg.width, h->cfg.height, canvas_w, canvas_h,
                                         bgra != 0, (uint32_t *)h->d_canvas_async.p, h->cur().stream);
     if (e != hipSuccess) return fail(h, PTX_E_HIP, "ptx_present_async: %s", hipGetErrorString(e));
     HIP_CHECK(h, hipMemcpyAsync(h->present_host, h->d_canvas_async.p, bytes, hipMemcpyDeviceToHost, h->cur().stream));
@@ -1924,6 +1938,64 @@ int ptx_present_poll(ptx_handle *h, uint8_t *out, size_t bytes) {
     }
     std::memcpy(out, h->present_host, h->present_bytes);
     h->present_pending = false;
+    return PTX_OK;
+}
+
+int ptx_denoise(ptx_handle *h, const ptx_denoise_params *p) {
+    if (!h) return PTX_E_INVALID;
+    const uint32_t n = p && p->iterations ? p->iterations : 5u;
+    const float sigma_lum = p && p->sigma_lum != 0.0f ? p->sigma_lum : 4.0f;
+    const float sigma_plane = p && p->sigma_plane != 0.0f ? p->sigma_plane : 0.02f;
+    if (n > 6u) return fail(h, PTX_E_INVALID, "ptx_denoise: %u iterations (1..6)", n);
+    if (!(sigma_lum > 0.0f) || !(sigma_plane > 0.0f) || std::isinf(sigma_lum) || std::isinf(sigma_plane))
+        return fail(h, PTX_E_INVALID, "ptx_denoise: sigma_lum %g, sigma_plane %g (finite, > 0)", sigma_lum, sigma_plane);
+    if (h->cfg.row_begin != 0 || h->band_h != h->cfg.height)
+        return fail(h, PTX_E_INVALID, "ptx_denoise: a band handle (rows %u..%u): the filter reaches 62 rows and a band's "
+                                      "accumulation has no halo", h->cfg.row_begin, h->cfg.row_end);
+    if (h->cfg.pipeline == PTX_PIPELINE_MCPT) return fail(h, PTX_E_INVALID, "ptx_denoise: the TEST_MCPT pipeline has no G-buffer");
+    if (!h->rendered || !h->scene_loaded || !h->frame_set || !h->layout_valid)
+        return fail(h, PTX_E_INVALID, "ptx_denoise: nothing rendered");
+    HIP_CHECK(h, hipSetDevice(h->device));
+    const uint32_t W = h->cfg.width, H = h->cfg.height;
+    const size_t px = (size_t)W * H;
+    // (first use: nothing of the handle's runs on these buffers yet)
+    if (int rc = alloc_buf(h, h->d_dn_guide, px * 32u)) return rc;
+    if (int rc = alloc_buf(h, h->d_dn_work, px * 16u)) return rc;
+    if (int rc = alloc_buf(h, h->d_denoised, px * 16u)) return rc;
+    // on the current frame's stream, after it (ptx_present_async's place): a pipelined handle's next
+    // frame records ev_prev on this stream first, and its accumulation waits for ev_prev; this
+    // context's G-buffer is next written by this context's next frame, on this stream
+    const hipStream_t st = h->cur().stream;
+    const Scene sc = make_scene(h);
+    float4 *guide = (float4 *)h->d_dn_guide.p;
+    // the working image alternates between the two buffers; the last iteration writes the output
+    float4 *buf[2] = {(float4 *)h->d_dn_work.p, (float4 *)h->d_denoised.p};
+    uint32_t cur = n & 1u ? 0u : 1u;
+    auto timed = [&](auto &&launch) {
+        TimedLaunch *t = event_begin(h, PTX_STAT_DENOISE, st);
+        const hipError_t le = launch();
+        event_end(t, st);
+        if (!t && le == hipSuccess) h->launches[PTX_STAT_DENOISE] += 1;  // (untimed handles: the count alone)
+        return le;
+    };
+    hipError_t e = timed([&] { return launch_denoise_guide(sc, gbuf_band(h), guide, sigma_plane, st); });
+    if (e == hipSuccess)
+        e = timed([&] { return launch_denoise_variance(W, H, (const float4 *)h->d_accum.p, guide, buf[cur], st); });
+    for (uint32_t i = 0; e == hipSuccess && i < n; ++i, cur ^= 1u)
+        e = timed([&] {
+            return launch_denoise_atrous(W, H, 1u << i, buf[cur], guide, buf[cur ^ 1u], sigma_lum, i + 1u == n, st);
+        });
+    if (e != hipSuccess) return fail(h, PTX_E_HIP, "ptx_denoise: %s", hipGetErrorString(e));
+    return PTX_OK;
+}
+
+int ptx_present_source(ptx_handle *h, int which) {
+    if (!h) return PTX_E_INVALID;
+    if (which != PTX_BUF_ACCUM && which != PTX_BUF_DENOISED)
+        return fail(h, PTX_E_INVALID, "ptx_present_source: buffer %d (PTX_BUF_ACCUM or PTX_BUF_DENOISED)", which);
+    if (which == PTX_BUF_DENOISED && !h->d_denoised.p)
+        return fail(h, PTX_E_INVALID, "ptx_present_source: no denoised image yet (ptx_denoise first)");
+    h->present_src = which;
     return PTX_OK;
 }
 
@@ -1990,7 +2062,8 @@ int ptx_destroy(ptx_handle *h) {
     if (h->present_host) (void)hipHostFree(h->present_host);
     for (DevBuf *b : {&h->d_canvas, &h->d_canvas_async, &h->d_scene, &h->d_geometry, &h->d_tris, &h->d_nodes, &h->d_subs,
                       &h->d_insts, &h->d_mats, &h->d_tverts, &h->d_accum, &h->d_counters, &h->d_qrays, &h->d_qhits, &h->d_hist,
-                      &h->d_jstate, &h->d_jres, &h->d_psurf, &h->d_census, &h->d_wgt})
+                      &h->d_jstate, &h->d_jres, &h->d_psurf, &h->d_census, &h->d_wgt, &h->d_dn_guide, &h->d_dn_work,
+                      &h->d_denoised})
         free_buf(*b);
     for (auto &c : h->ctx) {
         for (DevBuf *b : {&c.gbuf, &c.res, &c.direct, &c.nbr, &c.tjstate, &c.tjres, &c.surf, &c.wstate, &c.wrays, &c.wres[0],

@@ -1,0 +1,255 @@
+// ptx_denoise.hip -- edge-avoiding a-trous wavelet filter of the accumulated image (ptx_denoise,
+// DESIGN.md §Denoiser): guided by the primary hit of the frame context's G-buffer, variance
+// estimated spatially from the image.  Three kernels, all one lane per pixel, no atomics:
+//   dn_guide     G-buffer texel -> 32-byte guide record {P.xyz, key | kDnMiss}{N.xyz, r}
+//   dn_variance  7x7 guide-weighted luminance moments -> working image {r, g, b, v}
+//   dn_atrous    one iteration at step 2^i on the working image (ping-pong); steps 1, 2, 4 stage
+//                the 16x16 tile and its apron in LDS, steps >= 8 gather their taps directly
+// Arithmetic is the definition's, operation by operation (tests/denoise_ref.py restates it in
+// numpy and the outputs are compared bit for bit): f32, no contraction, sums in tap order, a
+// skipped tap leaves every sum untouched.
+#include "ptx_wave_common.h"
+
+namespace ptx {
+
+constexpr uint32_t kDnMiss = 0xFFFFFFFFu;  // guide key word of a pixel without a primary hit (a key has bit 31 clear)
+constexpr int kDnTile = 16;                // a workgroup's pixels: 16 x 16, thread t -> (t & 15, t >> 4)
+static_assert(kDnTile * kDnTile == kBlock, "one lane per pixel of the tile");
+
+// ---------------------------------------------------------------- guide records
+__global__ __launch_bounds__(kBlock) void dn_guide(const Scene sc, const uint4 *__restrict__ gbuf,
+                                                   float4 *__restrict__ guide, float sigma_plane) {
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t x, y;
+    if (p >= padded_pixels(sc) || !tile_xy(sc, p, x, y)) return;
+    const size_t pix = (size_t)y * sc.width + x;
+    const uint4 g = gbuf[pix];
+    if (!(g.x & 0x80000000u)) {
+        guide[2u * pix] = make_float4(0.0f, 0.0f, 0.0f, asf(kDnMiss));
+        guide[2u * pix + 1u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const Surface X = get_surface(sc, gdecode(g));
+    const f3 cam = mk(asf(sc.U[U_CAMPOS]), asf(sc.U[U_CAMPOS + 1]), asf(sc.U[U_CAMPOS + 2]));
+    const float r = sigma_plane * length(X.pos - cam);
+    guide[2u * pix] = make_float4(X.pos.x, X.pos.y, X.pos.z, asf(g.x & 0x7fffffffu));
+    guide[2u * pix + 1u] = make_float4(X.nrm.x, X.nrm.y, X.nrm.z, r);
+}
+
+// ---------------------------------------------------------------- shared arithmetic
+// Guide weight of a tap with the centre's key (the caller skips every other tap).
+__device__ __forceinline__ float dn_gamma(f3 Pp, f3 Np, float rp, f3 Pq, f3 Nq) {
+    float wn = fmaxf(0.0f, dot(Np, Nq));
+#pragma unroll
+    for (int k = 0; k < 7; ++k) wn = wn * wn;
+    const float wd = fmaxf(0.0f, 1.0f - __builtin_fabsf(dot(Np, Pq - Pp)) / rp);
+    return wn * wd;
+}
+__device__ __forceinline__ f3 rgb(float4 c) { return mk(c.x, c.y, c.z); }
+
+// A tile's staging area: the 16x16 pixels and an apron of A pixels on every side.
+template <int A>
+struct DnTile {
+    static constexpr int N = kDnTile + 2 * A, E = N * N;
+    // entry of pixel (tx + dx, ty + dy) of the tile (|dx|, |dy| <= A)
+    static __device__ __forceinline__ int at(int tx, int ty, int dx, int dy) { return (ty + A + dy) * N + (tx + A + dx); }
+};
+// Fill the staging area from global memory; pixels outside the image become misses (never a tap).
+template <int A, bool WITH_CV, bool WITH_LUM>
+__device__ __forceinline__ void dn_stage(uint32_t W, uint32_t H, const float4 *__restrict__ guide,
+                                         const float4 *__restrict__ img, float4 *g0, float4 *g1, float4 *cv, float *lum) {
+    using T = DnTile<A>;
+    const int x0 = (int)blockIdx.x * kDnTile - A, y0 = (int)blockIdx.y * kDnTile - A;
+    for (int e = (int)threadIdx.x; e < T::E; e += kBlock) {
+        const int gx = x0 + e % T::N, gy = y0 + e / T::N;
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, asf(kDnMiss)), b = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = b;
+        if (gx >= 0 && gy >= 0 && gx < (int)W && gy < (int)H) {
+            const size_t q = (size_t)gy * W + (size_t)gx;
+            a = guide[2u * q];
+            b = guide[2u * q + 1u];
+            c = img[q];
+        }
+        g0[e] = a;
+        g1[e] = b;
+        if (WITH_CV) cv[e] = c;
+        if (WITH_LUM) lum[e] = luminance(rgb(c));
+    }
+    __syncthreads();
+}
+
+// ---------------------------------------------------------------- variance pass
+__global__ __launch_bounds__(kBlock) void dn_variance(uint32_t W, uint32_t H, const float4 *__restrict__ accum,
+                                                      const float4 *__restrict__ guide, float4 *__restrict__ out) {
+    using T = DnTile<3>;
+    __shared__ float4 g0[T::E], g1[T::E];
+    __shared__ float lum[T::E];
+    dn_stage<3, false, true>(W, H, guide, accum, g0, g1, nullptr, lum);
+    const int tx = (int)(threadIdx.x & 15u), ty = (int)(threadIdx.x >> 4);
+    const uint32_t x = blockIdx.x * kDnTile + (uint32_t)tx, y = blockIdx.y * kDnTile + (uint32_t)ty;
+    if (x >= W || y >= H) return;
+    const size_t pix = (size_t)y * W + x;
+    const float4 c = accum[pix];
+    const float4 a = g0[T::at(tx, ty, 0, 0)], b = g1[T::at(tx, ty, 0, 0)];
+    const uint32_t key = asu(a.w);
+    float v = 0.0f;
+    if (key != kDnMiss) {
+        const f3 Pp = rgb(a), Np = rgb(b);
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+        for (int dy = -3; dy <= 3; ++dy) {
+#pragma unroll
+            for (int dx = -3; dx <= 3; ++dx) {
+                const int e = T::at(tx, ty, dx, dy);
+                const float4 qa = g0[e];
+                if (asu(qa.w) != key) continue;
+                const float gm = dn_gamma(Pp, Np, b.w, rgb(qa), rgb(g1[e]));
+                const float lq = lum[e];
+                s0 += gm;
+                s1 += gm * lq;
+                s2 += gm * (lq * lq);
+            }
+        }
+        const float m = s1 / s0;
+        v = fmaxf(0.0f, s2 / s0 - m * m);
+    }
+    out[pix] = make_float4(c.x, c.y, c.z, v);
+}
+
+// ---------------------------------------------------------------- a-trous iteration
+struct DnSums { float sw; f3 sc; float sv; };
+__device__ __forceinline__ void dn_tap(DnSums &S, float h, f3 Pp, f3 Np, float rp, float lp, float dp, float4 qa,
+                                       float4 qb, float4 qc) {
+    const float gm = dn_gamma(Pp, Np, rp, rgb(qa), rgb(qb));
+    const float t = fmaxf(0.0f, 1.0f - (__builtin_fabsf(lp - luminance(rgb(qc))) / dp) / 4.0f);
+    const float wl = (t * t) * (t * t);
+    const float w = (h * gm) * wl;
+    S.sw += w;
+    S.sc = S.sc + rgb(qc) * w;
+    S.sv += (w * w) * qc.w;
+}
+__device__ __forceinline__ float dn_b(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1) ? 0.25f : 0.0625f; }
+__device__ __forceinline__ float dn_w3(int d) { return d == 0 ? 0.5f : 0.25f; }
+
+// Steps 1, 2, 4: the tile and its apron of 2 * STEP pixels in LDS (48 B per entry: 19 / 27 / 48 KiB).
+template <int STEP>
+__global__ __launch_bounds__(kBlock) void dn_atrous_tiled(uint32_t W, uint32_t H, const float4 *__restrict__ in,
+                                                          const float4 *__restrict__ guide, float4 *__restrict__ out,
+                                                          float sigma_lum, uint32_t last) {
+    using T = DnTile<2 * STEP>;
+    __shared__ float4 g0[T::E], g1[T::E], cv[T::E];
+    dn_stage<2 * STEP, true, false>(W, H, guide, in, g0, g1, cv, nullptr);
+    const int tx = (int)(threadIdx.x & 15u), ty = (int)(threadIdx.x >> 4);
+    const uint32_t x = blockIdx.x * kDnTile + (uint32_t)tx, y = blockIdx.y * kDnTile + (uint32_t)ty;
+    if (x >= W || y >= H) return;
+    const int ec = T::at(tx, ty, 0, 0);
+    const float4 a = g0[ec], b = g1[ec], c = cv[ec];
+    const uint32_t key = asu(a.w);
+    float4 o = make_float4(c.x, c.y, c.z, 0.0f);
+    if (key != kDnMiss) {
+        float vb = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int e = T::at(tx, ty, dx, dy);
+                if (asu(g0[e].w) == key) vb += (dn_w3(dy) * dn_w3(dx)) * cv[e].w;
+            }
+        const float dp = sigma_lum * __builtin_sqrtf(vb) + 1e-6f;
+        const float lp = luminance(rgb(c));
+        const f3 Pp = rgb(a), Np = rgb(b);
+        DnSums S{0.0f, mk(0.0f, 0.0f, 0.0f), 0.0f};
+        for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+            for (int dx = -2; dx <= 2; ++dx) {
+                const int e = T::at(tx, ty, STEP * dx, STEP * dy);
+                const float4 qa = g0[e];
+                if (asu(qa.w) != key) continue;
+                dn_tap(S, dn_b(dy) * dn_b(dx), Pp, Np, b.w, lp, dp, qa, g1[e], cv[e]);
+            }
+        }
+        const f3 cn = S.sc / S.sw;
+        o = make_float4(cn.x, cn.y, cn.z, S.sv / (S.sw * S.sw));
+    }
+    if (last) o.w = 1.0f;
+    out[(size_t)y * W + x] = o;
+}
+
+// Steps >= 8: a pixel's taps share no cache line with its neighbours' -- gathered directly, one
+// tap row's 15 loads issued together ahead of that row's weight chains.
+__global__ __launch_bounds__(kBlock) void dn_atrous_gather(uint32_t W, uint32_t H, int step, const float4 *__restrict__ in,
+                                                           const float4 *__restrict__ guide, float4 *__restrict__ out,
+                                                           float sigma_lum, uint32_t last) {
+    const int x = (int)(blockIdx.x * kDnTile + (threadIdx.x & 15u)), y = (int)(blockIdx.y * kDnTile + (threadIdx.x >> 4));
+    if (x >= (int)W || y >= (int)H) return;
+    const size_t pix = (size_t)y * W + (size_t)x;
+    const float4 a = guide[2u * pix], b = guide[2u * pix + 1u], c = in[pix];
+    const uint32_t key = asu(a.w);
+    float4 o = make_float4(c.x, c.y, c.z, 0.0f);
+    if (key != kDnMiss) {
+        float vb = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int qx = x + dx, qy = y + dy;
+                const bool inside = qx >= 0 && qy >= 0 && qx < (int)W && qy < (int)H;
+                const size_t q = inside ? (size_t)qy * W + (size_t)qx : pix;
+                const uint32_t kq = asu(guide[2u * q].w);
+                const float vq = in[q].w;
+                if (inside && kq == key) vb += (dn_w3(dy) * dn_w3(dx)) * vq;
+            }
+        const float dp = sigma_lum * __builtin_sqrtf(vb) + 1e-6f;
+        const float lp = luminance(rgb(c));
+        const f3 Pp = rgb(a), Np = rgb(b);
+        DnSums S{0.0f, mk(0.0f, 0.0f, 0.0f), 0.0f};
+        for (int dy = -2; dy <= 2; ++dy) {
+            const int qy = y + step * dy;
+            const bool row_in = qy >= 0 && qy < (int)H;
+            float4 qa[5], qb[5], qc[5];
+            bool ok[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const int qx = x + step * (k - 2);
+                ok[k] = row_in && qx >= 0 && qx < (int)W;
+                const size_t q = ok[k] ? (size_t)qy * W + (size_t)qx : pix;  // (an outside tap loads the centre, unused)
+                qa[k] = guide[2u * q];
+                qb[k] = guide[2u * q + 1u];
+                qc[k] = in[q];
+            }
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                if (!ok[k] || asu(qa[k].w) != key) continue;
+                dn_tap(S, dn_b(dy) * dn_b(k - 2), Pp, Np, b.w, lp, dp, qa[k], qb[k], qc[k]);
+            }
+        }
+        const f3 cn = S.sc / S.sw;
+        o = make_float4(cn.x, cn.y, cn.z, S.sv / (S.sw * S.sw));
+    }
+    if (last) o.w = 1.0f;
+    out[pix] = o;
+}
+
+// ---------------------------------------------------------------- launches
+static dim3 dn_grid(uint32_t W, uint32_t H) { return dim3((W + kDnTile - 1) / kDnTile, (H + kDnTile - 1) / kDnTile); }
+
+hipError_t launch_denoise_guide(const Scene &sc, const uint4 *gbuf, float4 *guide, float sigma_plane, hipStream_t s) {
+    const uint32_t tiles = ((sc.width + 7u) / 8u) * ((sc.row_end - sc.row_begin + 7u) / 8u);
+    hipLaunchKernelGGL(dn_guide, dim3((tiles * 64u + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, gbuf, guide, sigma_plane);
+    return hipGetLastError();
+}
+hipError_t launch_denoise_variance(uint32_t W, uint32_t H, const float4 *accum, const float4 *guide, float4 *out,
+                                   hipStream_t s) {
+    hipLaunchKernelGGL(dn_variance, dn_grid(W, H), dim3(kBlock), 0, s, W, H, accum, guide, out);
+    return hipGetLastError();
+}
+hipError_t launch_denoise_atrous(uint32_t W, uint32_t H, uint32_t step, const float4 *in, const float4 *guide, float4 *out,
+                                 float sigma_lum, bool last, hipStream_t s) {
+    const dim3 g = dn_grid(W, H), bl(kBlock);
+    const uint32_t l = last ? 1u : 0u;
+    if (step == 1u) hipLaunchKernelGGL(dn_atrous_tiled<1>, g, bl, 0, s, W, H, in, guide, out, sigma_lum, l);
+    else if (step == 2u) hipLaunchKernelGGL(dn_atrous_tiled<2>, g, bl, 0, s, W, H, in, guide, out, sigma_lum, l);
+    else if (step == 4u) hipLaunchKernelGGL(dn_atrous_tiled<4>, g, bl, 0, s, W, H, in, guide, out, sigma_lum, l);
+    else hipLaunchKernelGGL(dn_atrous_gather, g, bl, 0, s, W, H, (int)step, in, guide, out, sigma_lum, l);
+    return hipGetLastError();
+}
+
+}  // namespace ptx

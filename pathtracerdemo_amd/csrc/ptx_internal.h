@@ -161,6 +161,12 @@ struct ptx_handle {
     size_t present_host_bytes = 0, present_bytes = 0;
     hipEvent_t ev_present = nullptr;
     bool present_pending = false;
+    // ptx_denoise (allocated by its first call): guide records (32 B per pixel), the working image
+    // {r, g, b, v} and the output, which is the other half of the working image's ping-pong;
+    // what ptx_present* read (PTX_BUF_ACCUM or PTX_BUF_DENOISED); a frame or pass has run
+    DevBuf d_dn_guide, d_dn_work, d_denoised;
+    int present_src = PTX_BUF_ACCUM;
+    bool rendered = false;
     // stats
     TimedLaunch ring[kEventRing];
     int ring_pos = 0;

@@ -38,6 +38,15 @@ hipError_t launch_mcpt(const Scene &sc, float4 *accum, uint32_t stack_depth, hip
 hipError_t launch_present(const float4 *tex, uint32_t W, uint32_t H, uint32_t cw, uint32_t ch, bool bgra,
                           uint32_t *out, hipStream_t s);
 
+// the denoiser (ptx_denoise.hip; whole-image handles): guide records (2 float4 per pixel) from the
+// G-buffer, the variance pass accum -> {r, g, b, v}, one a-trous iteration at `step` (a power of
+// two; `last`: the output's alpha is 1)
+hipError_t launch_denoise_guide(const Scene &sc, const uint4 *gbuf, float4 *guide, float sigma_plane, hipStream_t s);
+hipError_t launch_denoise_variance(uint32_t W, uint32_t H, const float4 *accum, const float4 *guide, float4 *out,
+                                   hipStream_t s);
+hipError_t launch_denoise_atrous(uint32_t W, uint32_t H, uint32_t step, const float4 *in, const float4 *guide, float4 *out,
+                                 float sigma_lum, bool last, hipStream_t s);
+
 // closest-hit queries for a ray array (ptx_kernels.hip)
 hipError_t launch_trace_rays(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,
                              uint32_t stack_depth, hipStream_t s);

@@ -242,6 +242,22 @@ class Renderer:
         N.check(self._lib, self._h, rc, "ptx_present_poll")
         return out
 
+    def Denoise(self, iterations: int = 0, sigma_lum: float = 0.0, sigma_plane: float = 0.0) -> None:
+        """Enqueue the edge-avoiding a-trous filter of the accumulated image behind the frame last
+        rendered (ptx_denoise; 0 = the defaults: 5 iterations, sigma_lum 4, sigma_plane 0.02);
+        read_denoised() or Present with source "denoised" show the result."""
+        p = N.PtxDenoiseParams(iterations=int(iterations), sigma_lum=float(sigma_lum), sigma_plane=float(sigma_plane))
+        self._call("ptx_denoise", self._h, ctypes.byref(p))
+
+    def read_denoised(self) -> np.ndarray:
+        """The denoised image (band_h, W, 4) f32: rgb after the last iteration, alpha 1."""
+        return self._read(N.PTX_BUF_DENOISED, np.float32, 4)
+
+    def set_present_source(self, source: str) -> None:
+        """What Present / present_async show: "accum" (the default) or "denoised"."""
+        which = {"accum": N.PTX_BUF_ACCUM, "denoised": N.PTX_BUF_DENOISED}[source]
+        self._call("ptx_present_source", self._h, which)
+
     def trace(self, rays: np.ndarray, eps_mode: int = 1) -> np.ndarray:
         """Closest hits for an (n, 8) f32 ray array {o.xyz, d.xyz, -, -}; returns (n, 8) f32
         {t, flags|inst|mat bits, prim bits, bary.x, bary.y, pos.xyz} (include/ptx.h)."""

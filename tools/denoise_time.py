@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Time ptx_denoise (pathtracerdemo_amd/csrc/ptx_denoise.hip) on a rendered frame.
+
+    python tools/denoise_time.py                        # 1920x1080, C3, reuse pipeline, 5 iterations
+    rocprofv3 --kernel-trace -d OUT -o run --output-format csv -- python tools/denoise_time.py --no-events
+    python tools/denoise_time.py --trace OUT/.../run_kernel_trace.csv      # per kernel, from that trace
+
+The whole call is timed with device events around it on the handle's stream (a torch stream set
+with ptx_set_stream): the median of --calls calls after --warmup.  The same calls on a
+PTX_FLAG_TIME_LAUNCHES handle give the sum of the kernels' own times (stats slot
+PTX_STAT_DENOISE), for 1..6 iterations.  Per-kernel times come from a rocprofv3 kernel trace of
+this script, taken in a run of its own (--trace prints them with each kernel's compulsory bytes and
+its share of the streaming bound).  One JSON line either way.
+"""
+import argparse
+import csv
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_PEAK = 8.0e12  # B/s, the datasheet figure the bound is quoted against
+# compulsory bytes per pixel: what each kernel must read and write once
+BYTES = {"guide": 16 + 32, "variance": 48 + 16, "atrous": 48 + 16}
+
+
+def bound_ms(kind, px):
+    return BYTES[kind] * px / HBM_PEAK * 1e3
+
+
+def render(args, **kw):
+    from pathtracerdemo_amd.renderer import Renderer
+    from pathtracerdemo_amd.scene.world import compile_scene
+    r = Renderer(args.width, args.height, device=0, pipeline=args.pipeline, **kw)
+    r.Initialize(compile_scene(args.scene))
+    for _ in range(args.frames):
+        r.Update()
+        r.Render()
+    r.synchronize()
+    return r
+
+
+def measure(args):
+    px = args.width * args.height
+    out = {"what": "ptx_denoise", "width": args.width, "height": args.height, "scene": args.scene,
+           "pipeline": args.pipeline, "iterations": args.iterations, "calls": args.calls, "warmup": args.warmup,
+           "bound_ms_at_8TBs": round(bound_ms("guide", px) + bound_ms("variance", px) + args.iterations * bound_ms("atrous", px), 4)}
+    if not args.no_events:
+        import torch
+        r = render(args)
+        stream = torch.cuda.Stream()
+        r.set_stream(stream.cuda_stream)
+        ms = []
+        for i in range(args.warmup + args.calls):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            r.Denoise(iterations=args.iterations)
+            b.record(stream)
+            b.synchronize()
+            if i >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        r.set_stream(None)
+        r.close()
+        out["whole_call_ms"] = {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}
+        out["whole_call_fraction_of_bound"] = round(out["bound_ms_at_8TBs"] / statistics.median(ms), 3)
+    # the kernels' own times, summed per call (events around every launch), for 1..6 iterations
+    from pathtracerdemo_amd import _native as N
+    r = render(args, time_launches=True)
+    sums = {}
+    for n in ([args.iterations] if args.no_events else range(1, 7)):
+        per_call = []
+        for i in range(args.warmup + args.calls):
+            before = r.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE]
+            r.Denoise(iterations=n)
+            r.synchronize()
+            if i >= args.warmup:
+                per_call.append(r.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE] - before)
+        sums[n] = round(statistics.median(per_call), 4)
+    r.close()
+    out["kernel_sum_ms_by_iterations"] = sums
+    return out
+
+
+def from_trace(args):
+    """Median duration of each kernel of a call (guide, variance, iteration 0..n-1) over the traced
+    calls of the last handle (the TIME_LAUNCHES one), warm-up calls dropped."""
+    px = args.width * args.height
+    rows = [r for r in csv.DictReader(open(args.trace)) if "dn_" in r["Kernel_Name"]]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    per = 2 + args.iterations
+    calls, cur = [], []
+    for r in rows:  # a call starts at dn_guide
+        if "dn_guide" in r["Kernel_Name"] and cur:
+            calls.append(cur)
+            cur = []
+        cur.append(r)
+    calls.append(cur)
+    calls = [c for c in calls if len(c) == per][-args.calls:]
+    out = {"what": "ptx_denoise per kernel (rocprofv3 kernel trace)", "width": args.width, "height": args.height,
+           "iterations": args.iterations, "calls": len(calls), "kernels": []}
+    for k in range(per):
+        us = statistics.median((int(c[k]["End_Timestamp"]) - int(c[k]["Start_Timestamp"])) / 1e3 for c in calls)
+        kind = "guide" if k == 0 else "variance" if k == 1 else "atrous"
+        name = calls[0][k]["Kernel_Name"].split("(")[0].replace("void ", "")
+        out["kernels"].append({"kernel": name + ("" if k < 2 else f" step {1 << (k - 2)}"), "median_us": round(us, 2),
+                               "lds": int(calls[0][k]["LDS_Block_Size"]),
+                               "scratch": int(calls[0][k]["Scratch_Size"]),
+                               "bound_us_at_8TBs": round(bound_ms(kind, px) * 1e3, 2),
+                               "fraction_of_bound": round(bound_ms(kind, px) * 1e3 / us, 3)})
+    out["sum_us"] = round(sum(k["median_us"] for k in out["kernels"]), 2)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--scene", default="c3_interior_32")
+    ap.add_argument("--pipeline", default="reuse")
+    ap.add_argument("--frames", type=int, default=2, help="frames rendered before the timed calls")
+    ap.add_argument("--iterations", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--no-events", action="store_true", help="only the TIME_LAUNCHES handle (the run a profiler traces)")
+    ap.add_argument("--trace", help="a rocprofv3 run_kernel_trace.csv of this script: print per-kernel medians")
+    args = ap.parse_args()
+    print(json.dumps(from_trace(args) if args.trace else measure(args)))
+
+
+if __name__ == "__main__":
+    main()
