@@ -93,6 +93,12 @@ extern "C" {
                                     next frame's temporal history (reuse pipeline)           */
 #define PTX_BUF_DIRECT 5     /* band_h * W * 4 f32: direct light of the GI init pass (GI pipeline) */
 #define PTX_BUF_DENOISED 6   /* band_h * W * 4 f32: ptx_denoise's output (read-only; exists after the first call) */
+#define PTX_BUF_FRAME_COLOR 7 /* band_h * W * 4 f32 {r, g, b, 1}: the radiance of the frame last rendered alone, what
+                                 WriteColor mixed into the accumulation (PTX_FLAG_FRAME_COLOR handles; read-only;
+                                 unspecified at pixels without a primary hit, which get the environment colour) */
+#define PTX_BUF_DENOISE_HISTORY 8 /* band_h * W * 4 f32 {C.rgb, n}: the temporally integrated colour and the history
+                                     length (0..255; 0 = no primary hit) of the last temporal ptx_denoise
+                                     (read-only; exists after the first temporal call) */
 
 #define PTX_FLAG_COUNT_WORK 1u     /* count rays / AABB / triangle tests on device (slower)   */
 #define PTX_FLAG_SIMPLE_KERNELS 2u   /* A/B: one thread per pixel, no ray exchange            */
@@ -113,6 +119,11 @@ extern "C" {
                                         but skips the halo exchange -- the halo rows keep what
                                         they hold, so the edge rows are NOT the split frame's.
                                         Timing only (a band timed alone: bench.py calibration) */
+#define PTX_FLAG_FRAME_COLOR 512u  /* keep PTX_BUF_FRAME_COLOR: every WriteColor also stores the frame's own
+                                        radiance (one more band_h * W * 16 bytes, counted in device_bytes;
+                                        written by the kernels that write the accumulation, in its order).
+                                        Accumulation, reservoirs and G-buffer keep their bits.  Needed by
+                                        ptx_denoise's temporal mode; any pipeline (TEST_MCPT included)  */
 /* no variant flag: the wavefront pipeline (compacted ray queues, one trace round per
    path vertex) -- the default */
 
@@ -246,12 +257,34 @@ int ptx_present_poll(ptx_handle *h, uint8_t *out, size_t bytes);
  * counted in device_bytes): PTX_BUF_DENOISED holds rgb after the last iteration, alpha 1; a pixel
  * without a primary hit keeps its colour.  The camera position is the one of the uniform set on
  * the handle: call it before the next frame's ptx_set_frame.  Whole-image handles of the pipelines with a G-buffer
- * after at least one frame; anything else, or a parameter out of range, is PTX_E_INVALID. */
+ * after at least one frame; anything else, or a parameter out of range, is PTX_E_INVALID.
+ * Launches (PTX_STAT_DENOISE): 2 + iterations (guide records, variance, the iterations).
+ *
+ * Temporal mode (reserved[0] = 1; PTX_FLAG_FRAME_COLOR handles, PTX_E_INVALID otherwise, before the
+ * GPU is touched): the filter's input is not the accumulation but the frame colours integrated over
+ * the calls, carried across camera moves.  The handle keeps, from the previous temporal call, its
+ * guide records, its uniform words 4..22 with their VP (the inverse of words 4..19), and per pixel
+ * the integrated colour C, the luminance moments m1, m2 and the history length n (80 bytes per pixel
+ * beside the spatial filter's 64, allocated by the first temporal call, counted in device_bytes).
+ * A pixel with a primary hit looks its history up at itself when words 4..22 are that call's bit
+ * for bit, else at the four pixels around its hit point's projection through that VP (bilinear
+ * weights); a tap counts when it lies inside the image with the same instance and sub-mesh, n >= 1,
+ * normals within dot >= 0.9 and within the plane distance r.  With history n = min(n_h + 1, 255),
+ * alpha = max(1 / n, alpha_min) and C, m1, m2 move towards the frame's colour and luminance moments by
+ * alpha; without, they start from them with n = 1.  The variance is max(0, m2 - m1^2) where n >= 4,
+ * the spatial estimate on C elsewhere; the iterations then run unchanged on (C, variance) into
+ * PTX_BUF_DENOISED, and (C, m1, m2, n) -- not the filtered image -- is the next call's history
+ * (C and n: PTX_BUF_DENOISE_HISTORY).  A pixel without a primary hit keeps its accumulated colour,
+ * n = 0.  ptx_upload_scene and ptx_reset_accumulation drop the history; ptx_set_frame and the frame
+ * index never do (the engine's ResetFrameCount on a camera move keeps it); a call with reserved[0] = 0
+ * is the spatial filter exactly and neither reads nor writes the state.
+ * Launches: 3 + iterations (guide records, dn_temporal, variance, the iterations). */
 typedef struct ptx_denoise_params {
     uint32_t iterations;      /* 1..6 (step 2^i in iteration i); 0 = default 5 */
     float sigma_lum;          /* luminance edge stop, in standard deviations; 0 = default 4 */
     float sigma_plane;        /* plane-distance edge stop, as a fraction of the distance to the camera; 0 = default 0.02 */
-    uint32_t reserved[5];
+    uint32_t reserved[5];     /* [0] temporal: 0 = off, 1 = on; [1] alpha_min, the bit pattern of an f32: 0 = default
+                                 0.05, else finite and in (0, 1] (read in temporal mode only); [2..4] zero */
 } ptx_denoise_params;
 int ptx_denoise(ptx_handle *h, const ptx_denoise_params *p /* NULL = defaults */);
 /* What ptx_present and ptx_present_async read: PTX_BUF_ACCUM (the default) or PTX_BUF_DENOISED

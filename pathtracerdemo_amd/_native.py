@@ -27,7 +27,9 @@ PTX_STAT_DENOISE = 12  # launches of the denoiser's kernels
 PTX_BUF_GBUFFER, PTX_BUF_RESERVOIR, PTX_BUF_ACCUM, PTX_BUF_COUNTERS, PTX_BUF_RESERVOIR_HIST = 0, 1, 2, 3, 4
 PTX_BUF_DIRECT = 5
 PTX_BUF_DENOISED = 6  # ptx_denoise's output (read-only)
-PTX_COUNTER_MOTION_CLIP = 6  # word of PTX_BUF_COUNTERS: pixels a band could not reproject (ptx.h)
+PTX_BUF_FRAME_COLOR = 7  # the frame's own radiance (PTX_FLAG_FRAME_COLOR handles; read-only)
+PTX_BUF_DENOISE_HISTORY = 8  # {C.rgb, n} of the last temporal ptx_denoise (read-only)
+PTX_COUNTER_MOTION_CLIP = 6 # word of PTX_BUF_COUNTERS: pixels a band could not reproject (ptx.h)
 PTX_FLAG_COUNT_WORK = 1
 PTX_FLAG_SIMPLE_KERNELS = 2
 PTX_FLAGS_RETIRED = 12  # the removed persistent-lane / tiled A/B variants: ptx_create rejects them
@@ -36,6 +38,7 @@ PTX_FLAG_SINGLE_STREAM = 32
 PTX_FLAG_ROW_CENSUS = 64
 PTX_FLAG_HALO_OVERLAP = 128
 PTX_FLAG_HALO_SKIP = 256  # band frame without the exchange: timing only (edge rows are not the split frame's)
+PTX_FLAG_FRAME_COLOR = 512  # keep PTX_BUF_FRAME_COLOR (needed by ptx_denoise's temporal mode)
 PTX_COMM_ID_BYTES = 128
 VARIANT_FLAGS = {"wave": 0, "simple": PTX_FLAG_SIMPLE_KERNELS}
 

@@ -1,8 +1,12 @@
 // ptx_denoise.hip -- edge-avoiding a-trous wavelet filter of the accumulated image (ptx_denoise,
 // DESIGN.md §Denoiser): guided by the primary hit of the frame context's G-buffer, variance
-// estimated spatially from the image.  Three kernels, all one lane per pixel, no atomics:
+// estimated spatially from the image; in temporal mode the image is the frame colours integrated
+// over the calls, looked up through the previous call's camera (tests/denoise_temporal_ref.py).
+// All kernels one lane per pixel, no atomics:
 //   dn_guide     G-buffer texel -> 32-byte guide record {P.xyz, key | kDnMiss}{N.xyz, r}
-//   dn_variance  7x7 guide-weighted luminance moments -> working image {r, g, b, v}
+//   dn_temporal  (temporal mode) history lookup + integration -> history {C.rgb, n}, moments {m1, m2}
+//   dn_variance  7x7 guide-weighted luminance moments -> working image {r, g, b, v}; <true>: on the
+//                history, the integrated moments' variance where n >= 4
 //   dn_atrous    one iteration at step 2^i on the working image (ping-pong); steps 1, 2, 4 stage
 //                the 16x16 tile and its apron in LDS, steps >= 8 gather their taps directly
 // Arithmetic is the definition's, operation by operation (tests/denoise_ref.py restates it in
@@ -77,39 +81,153 @@ __device__ __forceinline__ void dn_stage(uint32_t W, uint32_t H, const float4 *_
     __syncthreads();
 }
 
+// ---------------------------------------------------------------- temporal integration
+// The previous temporal call as dn_temporal sees it.  mode: 0 no history (the first call, or after a
+// reset), 1 the camera words are that call's (the history of pixel p is at p), 2 reproject through vp.
+struct DnHistory {
+    float vp[16];  // that call's VP (mat4_inverse of its uniform words 4..19)
+    float alpha_min;
+    uint32_t mode;
+};
+constexpr float kDnNMax = 255.0f;    // the history length saturates here
+constexpr float kDnNMoments = 4.0f;  // from this length on the variance comes from the integrated moments
+
+// History lookup and integration of one pixel: reads this frame's guide record and colour and up to
+// four previous guide / history / moment records, writes the new history {C.rgb, n} and moments
+// {m1, m2}.  The four taps' records are gathered directly, all issued ahead of the tests: under
+// camera motion a tile's footprint in the previous frame is a shifted, nearly rigid tile, so
+// neighbouring lanes' taps share cache lines, but its extent is not bounded.
+__global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, const DnHistory Hs,
+                                                      const float4 *__restrict__ guide, const float4 *__restrict__ frame,
+                                                      const float4 *__restrict__ accum, const float4 *__restrict__ pguide,
+                                                      const float4 *__restrict__ phist, const float2 *__restrict__ pmom,
+                                                      float4 *__restrict__ hist, float2 *__restrict__ mom) {
+    const uint32_t x = blockIdx.x * kDnTile + (threadIdx.x & 15u), y = blockIdx.y * kDnTile + (threadIdx.x >> 4);
+    if (x >= W || y >= H) return;
+    const size_t pix = (size_t)y * W + x;
+    const float4 a = guide[2u * pix];
+    const uint32_t key = asu(a.w);
+    if (key == kDnMiss) {  // no primary hit: the accumulated colour, never a tap (n = 0)
+        const float4 c = accum[pix];
+        hist[pix] = make_float4(c.x, c.y, c.z, 0.0f);
+        mom[pix] = make_float2(0.0f, 0.0f);
+        return;
+    }
+    const float4 b = guide[2u * pix + 1u];
+    const f3 F = rgb(frame[pix]), Pp = rgb(a), Np = rgb(b);
+    const float l = luminance(F);
+    f3 C = F;
+    float m1 = l, m2 = l * l, n = 1.0f;
+    if (Hs.mode != 0u) {
+        // candidate taps k = 2 j + i (j outer): pixel, bilinear weight, inside the image
+        size_t q[4];
+        float w[4];
+        bool in[4];
+        if (Hs.mode == 1u) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { q[k] = pix; w[k] = 1.0f; in[k] = k == 0; }
+        } else {
+            const float *vp = Hs.vp;
+            const float cx = ((vp[0] * Pp.x + vp[4] * Pp.y) + vp[8] * Pp.z) + vp[12];
+            const float cy = ((vp[1] * Pp.x + vp[5] * Pp.y) + vp[9] * Pp.z) + vp[13];
+            const float cw = ((vp[3] * Pp.x + vp[7] * Pp.y) + vp[11] * Pp.z) + vp[15];
+            const float fx = ((cx / cw + 1.0f) * 0.5f) * (float)W - 0.5f, fy = ((cy / cw + 1.0f) * 0.5f) * (float)H - 0.5f;
+            const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
+            const float ax = fx - x0, ay = fy - y0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int i = k & 1, j = k >> 1;
+                const float qx = x0 + (float)i, qy = y0 + (float)j;
+                // (a NaN or infinite projection compares false: outside)
+                in[k] = cw > 0.0f && qx >= 0.0f && qx < (float)W && qy >= 0.0f && qy < (float)H;
+                q[k] = in[k] ? (size_t)(int)qy * W + (size_t)(int)qx : pix;  // (an outside tap loads the centre, unused)
+                w[k] = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+            }
+        }
+        float4 qa[4], qb[4], qh[4];
+        float2 qm[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            qa[k] = pguide[2u * q[k]];
+            qb[k] = pguide[2u * q[k] + 1u];
+            qh[k] = phist[q[k]];
+            qm[k] = pmom[q[k]];
+        }
+        float sw = 0.0f, s1 = 0.0f, s2 = 0.0f, nh = __builtin_inff();
+        f3 sC = mk(0.0f, 0.0f, 0.0f);
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!in[k] || asu(qa[k].w) != key || !(qh[k].w >= 1.0f)) continue;
+            if (!(dot(Np, rgb(qb[k])) >= 0.9f)) continue;
+            if (!(__builtin_fabsf(dot(Np, rgb(qa[k]) - Pp)) <= b.w)) continue;
+            sw += w[k];
+            sC = sC + rgb(qh[k]) * w[k];
+            s1 += w[k] * qm[k].x;
+            s2 += w[k] * qm[k].y;
+            nh = fminf(nh, qh[k].w);
+            any = true;
+        }
+        if (any && sw > 0.0f) {
+            n = fminf(nh + 1.0f, kDnNMax);
+            const float al = fmaxf(1.0f / n, Hs.alpha_min);
+            C = mix3(sC / sw, F, al);
+            m1 = mixf(s1 / sw, l, al);
+            m2 = mixf(s2 / sw, l * l, al);
+        }
+    }
+    hist[pix] = make_float4(C.x, C.y, C.z, n);
+    mom[pix] = make_float2(m1, m2);
+}
+
 // ---------------------------------------------------------------- variance pass
-__global__ __launch_bounds__(kBlock) void dn_variance(uint32_t W, uint32_t H, const float4 *__restrict__ accum,
-                                                      const float4 *__restrict__ guide, float4 *__restrict__ out) {
+// The 7x7 guide-weighted luminance moments of a hit pixel of the staged tile.
+__device__ __forceinline__ float dn_var7(const float4 *g0, const float4 *g1, const float *lum, int tx, int ty, float4 a,
+                                         float4 b) {
+    using T = DnTile<3>;
+    const uint32_t key = asu(a.w);
+    const f3 Pp = rgb(a), Np = rgb(b);
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    for (int dy = -3; dy <= 3; ++dy) {
+#pragma unroll
+        for (int dx = -3; dx <= 3; ++dx) {
+            const int e = T::at(tx, ty, dx, dy);
+            const float4 qa = g0[e];
+            if (asu(qa.w) != key) continue;
+            const float gm = dn_gamma(Pp, Np, b.w, rgb(qa), rgb(g1[e]));
+            const float lq = lum[e];
+            s0 += gm;
+            s1 += gm * lq;
+            s2 += gm * (lq * lq);
+        }
+    }
+    const float m = s1 / s0;
+    return fmaxf(0.0f, s2 / s0 - m * m);
+}
+// MOMENTS (temporal mode): `img` is the new history {C.rgb, n}; where n >= kDnNMoments the variance
+// is the integrated moments', and the 7x7 sums run only elsewhere.
+template <bool MOMENTS>
+__global__ __launch_bounds__(kBlock) void dn_variance(uint32_t W, uint32_t H, const float4 *__restrict__ img,
+                                                      const float2 *__restrict__ mom, const float4 *__restrict__ guide,
+                                                      float4 *__restrict__ out) {
     using T = DnTile<3>;
     __shared__ float4 g0[T::E], g1[T::E];
     __shared__ float lum[T::E];
-    dn_stage<3, false, true>(W, H, guide, accum, g0, g1, nullptr, lum);
+    dn_stage<3, false, true>(W, H, guide, img, g0, g1, nullptr, lum);
     const int tx = (int)(threadIdx.x & 15u), ty = (int)(threadIdx.x >> 4);
     const uint32_t x = blockIdx.x * kDnTile + (uint32_t)tx, y = blockIdx.y * kDnTile + (uint32_t)ty;
     if (x >= W || y >= H) return;
     const size_t pix = (size_t)y * W + x;
-    const float4 c = accum[pix];
+    const float4 c = img[pix];
     const float4 a = g0[T::at(tx, ty, 0, 0)], b = g1[T::at(tx, ty, 0, 0)];
-    const uint32_t key = asu(a.w);
     float v = 0.0f;
-    if (key != kDnMiss) {
-        const f3 Pp = rgb(a), Np = rgb(b);
-        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-        for (int dy = -3; dy <= 3; ++dy) {
-#pragma unroll
-            for (int dx = -3; dx <= 3; ++dx) {
-                const int e = T::at(tx, ty, dx, dy);
-                const float4 qa = g0[e];
-                if (asu(qa.w) != key) continue;
-                const float gm = dn_gamma(Pp, Np, b.w, rgb(qa), rgb(g1[e]));
-                const float lq = lum[e];
-                s0 += gm;
-                s1 += gm * lq;
-                s2 += gm * (lq * lq);
-            }
+    if (asu(a.w) != kDnMiss) {
+        if (MOMENTS && c.w >= kDnNMoments) {
+            const float2 m = mom[pix];
+            v = fmaxf(0.0f, m.y - m.x * m.x);
+        } else {
+            v = dn_var7(g0, g1, lum, tx, ty, a, b);
         }
-        const float m = s1 / s0;
-        v = fmaxf(0.0f, s2 / s0 - m * m);
     }
     out[pix] = make_float4(c.x, c.y, c.z, v);
 }
@@ -238,7 +356,23 @@ hipError_t launch_denoise_guide(const Scene &sc, const uint4 *gbuf, float4 *guid
 }
 hipError_t launch_denoise_variance(uint32_t W, uint32_t H, const float4 *accum, const float4 *guide, float4 *out,
                                    hipStream_t s) {
-    hipLaunchKernelGGL(dn_variance, dn_grid(W, H), dim3(kBlock), 0, s, W, H, accum, guide, out);
+    hipLaunchKernelGGL(dn_variance<false>, dn_grid(W, H), dim3(kBlock), 0, s, W, H, accum, (const float2 *)nullptr, guide, out);
+    return hipGetLastError();
+}
+hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const float *vp_prev, float alpha_min, uint32_t mode,
+                                   const float4 *guide, const float4 *frame, const float4 *accum, const float4 *pguide,
+                                   const float4 *phist, const float2 *pmom, float4 *hist, float2 *mom, hipStream_t s) {
+    DnHistory Hs{};
+    for (int i = 0; i < 16; ++i) Hs.vp[i] = vp_prev[i];
+    Hs.alpha_min = alpha_min;
+    Hs.mode = mode;
+    hipLaunchKernelGGL(dn_temporal, dn_grid(W, H), dim3(kBlock), 0, s, W, H, Hs, guide, frame, accum, pguide, phist, pmom,
+                       hist, mom);
+    return hipGetLastError();
+}
+hipError_t launch_denoise_variance_moments(uint32_t W, uint32_t H, const float4 *hist, const float2 *mom,
+                                           const float4 *guide, float4 *out, hipStream_t s) {
+    hipLaunchKernelGGL(dn_variance<true>, dn_grid(W, H), dim3(kBlock), 0, s, W, H, hist, mom, guide, out);
     return hipGetLastError();
 }
 hipError_t launch_denoise_atrous(uint32_t W, uint32_t H, uint32_t step, const float4 *in, const float4 *guide, float4 *out,

@@ -90,6 +90,9 @@ struct Scene {
     // (8 pixel rows); block census_tile_rows() + s: every query of trace-queue slot s
     // (segments of contiguous tiles in census mode, so the host maps them to tile rows)
     unsigned long long *census;
+    // PTX_FLAG_FRAME_COLOR: the frame's own radiance (PTX_BUF_FRAME_COLOR), stored beside every
+    // WriteColor at the accumulation's index; nullptr without the flag
+    float4 *frame_color;
 #ifdef PTX_WG_TIMES
     unsigned long long *wgt;  // diagnostic build only: per-wave {start, end, kernel | block, hw id} records
 #endif

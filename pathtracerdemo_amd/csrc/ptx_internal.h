@@ -165,6 +165,18 @@ struct ptx_handle {
     // {r, g, b, v} and the output, which is the other half of the working image's ping-pong;
     // what ptx_present* read (PTX_BUF_ACCUM or PTX_BUF_DENOISED); a frame or pass has run
     DevBuf d_dn_guide, d_dn_work, d_denoised;
+    // PTX_FLAG_FRAME_COLOR: the frame's own radiance (Scene::frame_color), shared by the frames in
+    // flight like the accumulation, whose kernels write it
+    DevBuf d_frame_color;
+    // ptx_denoise's temporal mode (allocated by its first temporal call), from the previous temporal
+    // call: its guide records (a call ends by swapping d_dn_guide with d_dn_guide_prev, no copy), two
+    // sets of history {C.rgb, n} and moments {m1, m2} (dn_set: the one that call wrote, the next
+    // call reads it and writes the other), its uniform words 4..22 and their VP
+    DevBuf d_dn_guide_prev, d_dn_hist[2], d_dn_mom[2];
+    int dn_set = 0;
+    bool dn_hist_valid = false;
+    uint32_t dn_camera[19] = {0};
+    float dn_vp[16] = {0};
     int present_src = PTX_BUF_ACCUM;
     bool rendered = false;
     // stats

@@ -67,6 +67,7 @@ __device__ __forceinline__ void write_color(const Scene &sc, float4 *accum, size
     float t = 1.0f / (float)(sc.U[U_FRAME] + 1u);
     float4 a = accum[i];
     accum[i] = make_float4(mixf(a.x, c.x, t), mixf(a.y, c.y, t), mixf(a.z, c.z, t), 1.0f);
+    if (sc.frame_color) sc.frame_color[i] = make_float4(c.x, c.y, c.z, 1.0f);
 }
 
 // =========================================================================== PT_01

@@ -46,6 +46,14 @@ hipError_t launch_denoise_variance(uint32_t W, uint32_t H, const float4 *accum, 
                                    hipStream_t s);
 hipError_t launch_denoise_atrous(uint32_t W, uint32_t H, uint32_t step, const float4 *in, const float4 *guide, float4 *out,
                                  float sigma_lum, bool last, hipStream_t s);
+// temporal mode: the history lookup and integration (mode 0 no history, 1 same pixel, 2 through
+// vp_prev; p*: the previous call's guide, history and moment records) -> history {C.rgb, n},
+// moments {m1, m2}; the variance pass on that history, the moments' variance where n >= 4
+hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const float *vp_prev, float alpha_min, uint32_t mode,
+                                   const float4 *guide, const float4 *frame, const float4 *accum, const float4 *pguide,
+                                   const float4 *phist, const float2 *pmom, float4 *hist, float2 *mom, hipStream_t s);
+hipError_t launch_denoise_variance_moments(uint32_t W, uint32_t H, const float4 *hist, const float2 *mom,
+                                           const float4 *guide, float4 *out, hipStream_t s);
 
 // closest-hit queries for a ray array (ptx_kernels.hip)
 hipError_t launch_trace_rays(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,

@@ -161,6 +161,7 @@ __device__ __forceinline__ void mix_color(const Scene &sc, float4 *accum, uint32
     float t = 1.0f / (float)(sc.U[U_FRAME] + 1u);  // WriteColor, PT_4:599-606
     float4 a = accum[i];
     accum[i] = make_float4(mixf(a.x, c.x, t), mixf(a.y, c.y, t), mixf(a.z, c.z, t), 1.0f);
+    if (sc.frame_color) sc.frame_color[i] = make_float4(c.x, c.y, c.z, 1.0f);  // (wave-uniform: a kernel argument)
 }
 // pixel -> (x, y) for the start kernels: 8x8 tiles so a wave's first rays are coherent
 __device__ __forceinline__ bool tile_xy(const Scene &sc, uint32_t p, uint32_t &x, uint32_t &y) {

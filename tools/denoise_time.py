@@ -4,6 +4,7 @@
     python tools/denoise_time.py                        # 1920x1080, C3, reuse pipeline, 5 iterations
     rocprofv3 --kernel-trace -d OUT -o run --output-format csv -- python tools/denoise_time.py --no-events
     python tools/denoise_time.py --trace OUT/.../run_kernel_trace.csv      # per kernel, from that trace
+    python tools/denoise_time.py --temporal [--yaw-step DEG]   # the temporal mode (both forms above take it too)
 
 The whole call is timed with device events around it on the handle's stream (a torch stream set
 with ptx_set_stream): the median of --calls calls after --warmup.  The same calls on a
@@ -11,6 +12,9 @@ PTX_FLAG_TIME_LAUNCHES handle give the sum of the kernels' own times (stats slot
 PTX_STAT_DENOISE), for 1..6 iterations.  Per-kernel times come from a rocprofv3 kernel trace of
 this script, taken in a run of its own (--trace prints them with each kernel's compulsory bytes and
 its share of the streaming bound).  One JSON line either way.
+--temporal times the temporal mode on a frame_color handle: before every call the camera yaws by
+--yaw-step degrees (0: a still camera, the same-pixel lookup) and a frame is rendered with the frame
+index restarted, as the engine does on a move; only the ptx_denoise call is inside the events.
 """
 import argparse
 import csv
@@ -24,7 +28,10 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK = 8.0e12  # B/s, the datasheet figure the bound is quoted against
 # compulsory bytes per pixel: what each kernel must read and write once
-BYTES = {"guide": 16 + 32, "variance": 48 + 16, "atrous": 48 + 16}
+# (temporal: this frame's guide record and colour, one previous guide / history / moments record,
+# the new history and moments; its variance pass reads the guide record, history and moments)
+BYTES = {"guide": 16 + 32, "variance": 48 + 16, "atrous": 48 + 16, "temporal": 32 + 16 + 32 + 16 + 8 + 16 + 8,
+         "variance_moments": 32 + 16 + 8 + 16}
 
 
 def bound_ms(kind, px):
@@ -34,7 +41,7 @@ def bound_ms(kind, px):
 def render(args, **kw):
     from pathtracerdemo_amd.renderer import Renderer
     from pathtracerdemo_amd.scene.world import compile_scene
-    r = Renderer(args.width, args.height, device=0, pipeline=args.pipeline, **kw)
+    r = Renderer(args.width, args.height, device=0, pipeline=args.pipeline, frame_color=args.temporal, **kw)
     r.Initialize(compile_scene(args.scene))
     for _ in range(args.frames):
         r.Update()
@@ -43,11 +50,28 @@ def render(args, **kw):
     return r
 
 
+def next_frame(args, r, i):
+    """Temporal mode: the frame the next call follows (outside the timed region)."""
+    if not args.temporal:
+        return
+    if args.yaw_step:
+        r.GetCamera().set_yaw(args.yaw_step * (i + 1))
+        r.ResetFrameCount()
+    r.Update()
+    r.Render()
+    r.synchronize()
+
+
+def call_bound_ms(args, px):
+    head = bound_ms("temporal", px) + bound_ms("variance_moments", px) if args.temporal else bound_ms("variance", px)
+    return bound_ms("guide", px) + head + args.iterations * bound_ms("atrous", px)
+
+
 def measure(args):
     px = args.width * args.height
-    out = {"what": "ptx_denoise", "width": args.width, "height": args.height, "scene": args.scene,
+    out = {"what": "ptx_denoise", "temporal": args.temporal, "yaw_step": args.yaw_step, "width": args.width, "height": args.height, "scene": args.scene,
            "pipeline": args.pipeline, "iterations": args.iterations, "calls": args.calls, "warmup": args.warmup,
-           "bound_ms_at_8TBs": round(bound_ms("guide", px) + bound_ms("variance", px) + args.iterations * bound_ms("atrous", px), 4)}
+           "bound_ms_at_8TBs": round(call_bound_ms(args, px), 4)}
     if not args.no_events:
         import torch
         r = render(args)
@@ -55,9 +79,10 @@ def measure(args):
         r.set_stream(stream.cuda_stream)
         ms = []
         for i in range(args.warmup + args.calls):
+            next_frame(args, r, i)
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record(stream)
-            r.Denoise(iterations=args.iterations)
+            r.Denoise(iterations=args.iterations, temporal=args.temporal)
             b.record(stream)
             b.synchronize()
             if i >= args.warmup:
@@ -73,8 +98,9 @@ def measure(args):
     for n in ([args.iterations] if args.no_events else range(1, 7)):
         per_call = []
         for i in range(args.warmup + args.calls):
+            next_frame(args, r, i)
             before = r.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE]
-            r.Denoise(iterations=n)
+            r.Denoise(iterations=n, temporal=args.temporal)
             r.synchronize()
             if i >= args.warmup:
                 per_call.append(r.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE] - before)
@@ -85,12 +111,13 @@ def measure(args):
 
 
 def from_trace(args):
-    """Median duration of each kernel of a call (guide, variance, iteration 0..n-1) over the traced
+    """Median duration of each kernel of a call (guide, [temporal,] variance, iteration 0..n-1) over the traced
     calls of the last handle (the TIME_LAUNCHES one), warm-up calls dropped."""
     px = args.width * args.height
     rows = [r for r in csv.DictReader(open(args.trace)) if "dn_" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    per = 2 + args.iterations
+    head = ["guide", "temporal", "variance_moments"] if args.temporal else ["guide", "variance"]
+    per = len(head) + args.iterations
     calls, cur = [], []
     for r in rows:  # a call starts at dn_guide
         if "dn_guide" in r["Kernel_Name"] and cur:
@@ -103,9 +130,9 @@ def from_trace(args):
            "iterations": args.iterations, "calls": len(calls), "kernels": []}
     for k in range(per):
         us = statistics.median((int(c[k]["End_Timestamp"]) - int(c[k]["Start_Timestamp"])) / 1e3 for c in calls)
-        kind = "guide" if k == 0 else "variance" if k == 1 else "atrous"
+        kind = head[k] if k < len(head) else "atrous"
         name = calls[0][k]["Kernel_Name"].split("(")[0].replace("void ", "")
-        out["kernels"].append({"kernel": name + ("" if k < 2 else f" step {1 << (k - 2)}"), "median_us": round(us, 2),
+        out["kernels"].append({"kernel": name + ("" if k < len(head) else f" step {1 << (k - len(head))}"), "median_us": round(us, 2),
                                "lds": int(calls[0][k]["LDS_Block_Size"]),
                                "scratch": int(calls[0][k]["Scratch_Size"]),
                                "bound_us_at_8TBs": round(bound_ms(kind, px) * 1e3, 2),
@@ -124,6 +151,8 @@ def main():
     ap.add_argument("--iterations", type=int, default=5)
     ap.add_argument("--calls", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--temporal", action="store_true", help="the temporal mode on a frame_color handle")
+    ap.add_argument("--yaw-step", type=float, default=0.5, help="--temporal: degrees the camera yaws before every call (0: still)")
     ap.add_argument("--no-events", action="store_true", help="only the TIME_LAUNCHES handle (the run a profiler traces)")
     ap.add_argument("--trace", help="a rocprofv3 run_kernel_trace.csv of this script: print per-kernel medians")
     args = ap.parse_args()
