@@ -89,6 +89,10 @@ extern "C" {
 /* PTX_BUF_COUNTERS word 6, every build: pixels whose history a band could not reproject (past its
  * motion halo of reuse_radius rows; such a pixel has no temporal history); zeroed by ptx_reset_stats */
 #define PTX_COUNTER_MOTION_CLIP 6
+/* PTX_BUF_COUNTERS word 7, every build: pixels of ptx_denoise_bands' temporal mode with a history
+ * candidate inside the image but outside the rows the band's state covers (not taken; see
+ * ptx_denoise_bands); zeroed by ptx_reset_stats */
+#define PTX_COUNTER_DENOISE_CLIP 7
 #define PTX_BUF_RESERVOIR_HIST 4 /* band_h * W * 32 u32: spatial output = Final's input and the
                                     next frame's temporal history (reuse pipeline)           */
 #define PTX_BUF_DIRECT 5     /* band_h * W * 4 f32: direct light of the GI init pass (GI pipeline) */
@@ -257,7 +261,7 @@ int ptx_present_poll(ptx_handle *h, uint8_t *out, size_t bytes);
  * counted in device_bytes): PTX_BUF_DENOISED holds rgb after the last iteration, alpha 1; a pixel
  * without a primary hit keeps its colour.  The camera position is the one of the uniform set on
  * the handle: call it before the next frame's ptx_set_frame.  Whole-image handles of the pipelines with a G-buffer
- * after at least one frame; anything else, or a parameter out of range, is PTX_E_INVALID.
+ * after at least one frame (a frame split into bands: ptx_denoise_bands); anything else, or a parameter out of range, is PTX_E_INVALID.
  * Launches (PTX_STAT_DENOISE): 2 + iterations (guide records, variance, the iterations).
  *
  * Temporal mode (reserved[0] = 1; PTX_FLAG_FRAME_COLOR handles, PTX_E_INVALID otherwise, before the
@@ -287,6 +291,42 @@ typedef struct ptx_denoise_params {
                                  0.05, else finite and in (0, 1] (read in temporal mode only); [2..4] zero */
 } ptx_denoise_params;
 int ptx_denoise(ptx_handle *h, const ptx_denoise_params *p /* NULL = defaults */);
+/* The same filter on a frame split into row bands.  handles: band handles in band order that cover
+ * the image's rows (ptx_render_bands' continuity rules), each after at least one frame; or one
+ * whole-image handle (n = 1: exactly ptx_denoise); or, n = 1 with a handle whose communicator has
+ * world > 1, this rank's band of a frame every rank makes the call for (the neighbours' rows as
+ * ptx_comm_init exchanged them).  Either every handle owns a communicator (the halo moves by one
+ * group of sends / receives over them, counted in halo_bytes_sent) or none (peer copies; several
+ * bands may share a GPU).  ptx_denoise itself keeps refusing band handles.
+ *   A band filters the WINDOW of its rows [b0, b1) and min(R, rows available) rows above and below,
+ * R = 2^(iterations + 1) (64 at the default 5, 128 at 6), as if the window were the whole image (rows
+ * of the window outside the image: taps skipped, as ever).  With R halo rows the band's rows of the
+ * result are the whole-image filter's bit for bit, with R - 1 they are not: the colour after k
+ * iterations reaches r_k rows, the variance s_k, r_0 = 0, s_0 = 3, r_(k+1) = max(r_k + 2^(k+1),
+ * s_k + 1), s_(k+1) = max(r_k, s_k) + 2^(k+1), so r_n = 2^(n+1).  One exchange per call brings, per
+ * halo pixel, the neighbour's G-buffer texel (16 B) and accumulated colour (16 B), straight from its
+ * buffers; with more than one band, a band of fewer than R rows is PTX_E_INVALID (the message names
+ * the band and the rows needed), as are bands that differ in size or pipeline, a gap, TEST_MCPT, a
+ * band that has not rendered, parameters out of ptx_denoise's ranges and temporal mode without
+ * PTX_FLAG_FRAME_COLOR on every band -- all before any GPU work.
+ *   Each band's PTX_BUF_DENOISED (temporal mode: and PTX_BUF_DENOISE_HISTORY) holds its own band_h
+ * rows; the buffers (with room for 128 halo rows on either side) are allocated by the first call and
+ * counted in device_bytes, launches count in PTX_STAT_DENOISE.  Asynchronous on each band's stream
+ * behind the frame last rendered; a band's next frame waits on the GPU until its neighbours have
+ * copied its rows.  Accumulation, reservoirs, history and G-buffer keep their bits.
+ *   Temporal mode: each band runs the guide kernel and the history integration on its own rows; the
+ * halo then carries the texel, {C, n} (16 B) and {m1, m2} (8 B); guides of the halo rows are
+ * recomputed from the texels, the variance pass and the iterations run on the window, and what was
+ * received becomes the state's halo rows: the band's state covers its window, for this call's filter
+ * and the next call's history lookups.  In that next call a candidate tap inside the image but
+ * outside the rows the state covers is not taken -- as if n' = 0 there -- and a pixel with at least
+ * one such candidate adds 1 to PTX_COUNTER_DENOISE_CLIP on its band (the same-pixel rule never
+ * clips).  So with the counter 0 on every band the split equals the whole-image handle bit for bit,
+ * and in general a band's new {C, m1, m2, n} on its own rows is the whole-image definition with the
+ * previous state's n' zeroed outside that band's window.  ptx_upload_scene and
+ * ptx_reset_accumulation drop a band's state as ever; it then starts without history, and its
+ * neighbours see n = 1 (n = 0 at misses) in the rows it sends. */
+int ptx_denoise_bands(ptx_handle *const *handles, int n, const ptx_denoise_params *p /* NULL = defaults */);
 /* What ptx_present and ptx_present_async read: PTX_BUF_ACCUM (the default) or PTX_BUF_DENOISED
  * (fails before the first ptx_denoise). */
 int ptx_present_source(ptx_handle *h, int which);

@@ -30,6 +30,7 @@ PTX_BUF_DENOISED = 6  # ptx_denoise's output (read-only)
 PTX_BUF_FRAME_COLOR = 7  # the frame's own radiance (PTX_FLAG_FRAME_COLOR handles; read-only)
 PTX_BUF_DENOISE_HISTORY = 8  # {C.rgb, n} of the last temporal ptx_denoise (read-only)
 PTX_COUNTER_MOTION_CLIP = 6 # word of PTX_BUF_COUNTERS: pixels a band could not reproject (ptx.h)
+PTX_COUNTER_DENOISE_CLIP = 7  # word of PTX_BUF_COUNTERS: pixels with a history candidate past a band's denoiser state
 PTX_FLAG_COUNT_WORK = 1
 PTX_FLAG_SIMPLE_KERNELS = 2
 PTX_FLAGS_RETIRED = 12  # the removed persistent-lane / tiled A/B variants: ptx_create rejects them
@@ -49,7 +50,7 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_trace", "ptx_trace_device", "ptx_run_passes", "ptx_halo_rows", "ptx_halo_pack",
             "ptx_halo_unpack", "ptx_comm_unique_id", "ptx_comm_init", "ptx_comm_init_all", "ptx_render_bands",
             "ptx_row_census", "ptx_comm_info", "ptx_present", "ptx_present_async", "ptx_present_poll",
-            "ptx_build_info", "ptx_denoise", "ptx_present_source"]
+            "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -127,6 +128,7 @@ def load(path: str = LIB_PATH):
     lib.ptx_present_poll.argtypes = [H, P, ctypes.c_size_t]
     lib.ptx_build_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
     lib.ptx_denoise.argtypes = [H, ctypes.POINTER(PtxDenoiseParams)]
+    lib.ptx_denoise_bands.argtypes = [ctypes.POINTER(H), ctypes.c_int, ctypes.POINTER(PtxDenoiseParams)]
     lib.ptx_present_source.argtypes = [H, ctypes.c_int]
     lib.ptx_run_passes.argtypes = [H, P, ctypes.c_int]
     lib.ptx_halo_rows.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),

@@ -1428,9 +1428,16 @@ static bool buffer_view(ptx_handle *h, int which, DevBuf &v) {
     case PTX_BUF_ACCUM: v = h->d_accum; return true;
     case PTX_BUF_COUNTERS: v = h->d_counters; return true;
     case PTX_BUF_RESERVOIR_HIST: v.p = h->d_hist.p ? hist_band(h) : nullptr; v.bytes = px * 16u * h->res_u4; return v.p != nullptr;
-    case PTX_BUF_DENOISED: v = h->d_denoised; return v.p != nullptr;
+    // (the denoiser's buffers of a band carry dn_cap_top halo rows above the band's)
+    case PTX_BUF_DENOISED:
+        v.p = h->d_denoised.p ? (char *)h->d_denoised.p + (size_t)h->dn_cap_top * h->cfg.width * 16u : nullptr;
+        v.bytes = px * 16u;
+        return v.p != nullptr;
     case PTX_BUF_FRAME_COLOR: v = h->d_frame_color; return v.p != nullptr;
-    case PTX_BUF_DENOISE_HISTORY: v = h->d_dn_hist[h->dn_set]; return v.p != nullptr;
+    case PTX_BUF_DENOISE_HISTORY:
+        v.p = h->d_dn_hist[h->dn_set].p ? (char *)h->d_dn_hist[h->dn_set].p + (size_t)h->dn_cap_top * h->cfg.width * 16u : nullptr;
+        v.bytes = px * 16u;
+        return v.p != nullptr;
     default: return false;
     }
 }
@@ -1438,6 +1445,183 @@ static bool buffer_view(ptx_handle *h, int which, DevBuf &v) {
 // what ptx_present / ptx_present_async show (ptx_present_source)
 static const float4 *present_texture(const ptx_handle *h) {
     return (const float4 *)(h->present_src == PTX_BUF_DENOISED ? h->d_denoised.p : h->d_accum.p);
+}
+
+
+// ---------------------------------------------------------------- denoiser (ptx_denoise, ptx_denoise_bands)
+int denoise_params(ptx_handle *h, const ptx_denoise_params *p, DnCall &c, const char *what) {
+    c.n = p && p->iterations ? p->iterations : 5u;
+    c.sigma_lum = p && p->sigma_lum != 0.0f ? p->sigma_lum : 4.0f;
+    c.sigma_plane = p && p->sigma_plane != 0.0f ? p->sigma_plane : 0.02f;
+    if (c.n > 6u) return fail(h, PTX_E_INVALID, "%s: %u iterations (1..6)", what, c.n);
+    if (!(c.sigma_lum > 0.0f) || !(c.sigma_plane > 0.0f) || std::isinf(c.sigma_lum) || std::isinf(c.sigma_plane))
+        return fail(h, PTX_E_INVALID, "%s: sigma_lum %g, sigma_plane %g (finite, > 0)", what, c.sigma_lum, c.sigma_plane);
+    // temporal mode: reserved[0]; its alpha_min is reserved[1]'s bits as an f32 (0 = 0.05)
+    c.temporal = p ? p->reserved[0] : 0u;
+    c.alpha_min = 0.05f;
+    if (c.temporal > 1u) return fail(h, PTX_E_INVALID, "%s: temporal %u (0 or 1)", what, c.temporal);
+    if (c.temporal) {
+        if (p->reserved[1]) std::memcpy(&c.alpha_min, &p->reserved[1], sizeof c.alpha_min);
+        if (!(c.alpha_min > 0.0f && c.alpha_min <= 1.0f))
+            return fail(h, PTX_E_INVALID, "%s: alpha_min %g (finite, in (0, 1])", what, c.alpha_min);
+        if (!(h->cfg.flags & PTX_FLAG_FRAME_COLOR))
+            return fail(h, PTX_E_INVALID, "%s: the temporal mode integrates PTX_BUF_FRAME_COLOR: create the "
+                                          "handle with PTX_FLAG_FRAME_COLOR", what);
+    }
+    return PTX_OK;
+}
+
+int denoise_check(ptx_handle *h, const DnCall &c, const char *what) {
+    if (c.temporal && !(h->cfg.flags & PTX_FLAG_FRAME_COLOR))
+        return fail(h, PTX_E_INVALID, "%s: the temporal mode integrates PTX_BUF_FRAME_COLOR: create the "
+                                      "handle with PTX_FLAG_FRAME_COLOR", what);
+    if (h->cfg.pipeline == PTX_PIPELINE_MCPT) return fail(h, PTX_E_INVALID, "%s: the TEST_MCPT pipeline has no G-buffer", what);
+    if (!h->rendered || !h->scene_loaded || !h->frame_set || !h->layout_valid)
+        return fail(h, PTX_E_INVALID, "%s: nothing rendered", what);
+    return PTX_OK;
+}
+
+int denoise_alloc(ptx_handle *h, const DnCall &c) {
+    const uint32_t W = h->cfg.width;
+    if (!h->d_dn_guide.p) {  // (first use: nothing of the handle's runs on these buffers yet)
+        h->dn_cap_top = std::min(dn_reach(6u), h->cfg.row_begin);
+        h->dn_cap_bot = std::min(dn_reach(6u), h->cfg.height - h->cfg.row_end);
+    }
+    const size_t px = (size_t)(h->dn_cap_top + h->band_h + h->dn_cap_bot) * W;
+    const size_t hpx = (size_t)(h->dn_cap_top + h->dn_cap_bot) * W;
+    if (int rc = alloc_buf(h, h->d_dn_guide, px * 32u)) return rc;
+    if (int rc = alloc_buf(h, h->d_dn_work, px * 16u)) return rc;
+    if (int rc = alloc_buf(h, h->d_denoised, px * 16u)) return rc;
+    if (hpx) {
+        if (int rc = alloc_buf(h, h->d_dn_halo_g, hpx * 16u)) return rc;
+        if (!c.temporal)
+            if (int rc = alloc_buf(h, h->d_dn_halo_c, hpx * 16u)) return rc;
+    }
+    if (c.temporal) {  // the state: 32 + 2 * (16 + 8) bytes per pixel
+        if (int rc = alloc_buf(h, h->d_dn_guide_prev, px * 32u)) return rc;
+        for (int k = 0; k < 2; ++k) {
+            if (int rc = alloc_buf(h, h->d_dn_hist[k], px * 16u)) return rc;
+            if (int rc = alloc_buf(h, h->d_dn_mom[k], px * 8u)) return rc;
+        }
+    }
+    return PTX_OK;
+}
+
+// The rows [c0, c1) of the window a stage computes, for a band whose own rows are [top, top + band_h)
+// of a window of `rows` rows.  stage -1 is the variance pass, stage k >= 0 iteration k of n (step 2^k).
+// The band needs the last iteration's colours on its own rows only.  Iteration k reads its input's
+// colours 2 * 2^k rows away and its variances one row further than its own (the 3x3 prefilter), so
+// colours exact on band rows +- E_k come from an input exact on band rows +- (E_k + 2^(k+1)):
+//   E_(n-1) = 0,  E_(k-1) = E_k + 2^(k+1)   =>   E_k = 2^(n+1) - 2^(k+2),
+// and the variance pass feeds iteration 0: E_0 + 2 = 2^(n+1) - 2 rows.  Rows past the window's ends
+// do not exist; on a whole image (top = 0, rows = band_h) every stage computes every row.  (The
+// variances of the outermost rows a stage writes are not the whole image's -- the variance pass would
+// need three rows more -- but no colour of a band row depends on them: DESIGN.md §4.5, the reach.)
+static DnWin denoise_stage_rows(uint32_t y0, uint32_t rows, uint32_t top, uint32_t band_h, uint32_t n, int stage) {
+    const uint32_t R = dn_reach(n), E = stage < 0 ? R - 2u : R - (4u << stage);
+    DnWin w;
+    w.y0 = y0;
+    w.rows = rows;
+    w.c0 = top - std::min(top, E);
+    w.c1 = std::min(rows, top + band_h + E);
+    return w;
+}
+
+// One launch with its event pair, unless an earlier one of the call failed.
+template <class F>
+static hipError_t denoise_timed(ptx_handle *h, hipStream_t st, hipError_t le_in, F &&launch) {
+    if (le_in != hipSuccess) return le_in;
+    TimedLaunch *t = event_begin(h, PTX_STAT_DENOISE, st);
+    const hipError_t le = launch();
+    event_end(t, st);
+    if (!t && le == hipSuccess) h->launches[PTX_STAT_DENOISE] += 1;  // (untimed handles: the count alone)
+    return le;
+}
+
+// The window's row 0 in the denoiser's buffers (they start dn_cap_top rows above the band).
+static size_t dn_win_px(const ptx_handle *h, const DnBand &b) { return (size_t)(h->dn_cap_top - b.top) * h->cfg.width; }
+
+int denoise_front(ptx_handle *h, const DnCall &c, DnBand &b) {
+    // on the current frame's stream, after it (ptx_present_async's place): a pipelined handle's next
+    // frame records ev_prev on this stream first, and its accumulation waits for ev_prev; this
+    // context's G-buffer is next written by this context's next frame, on this stream.  The frame
+    // colour is written by the kernels that write the accumulation, so the same holds for it; and
+    // the temporal state a call on another context's stream left is read after that frame's
+    // accumulation on this stream, which waited for ev_prev, recorded behind that call.
+    const hipStream_t st = h->cur().stream;
+    const Scene sc = make_scene(h);
+    const uint32_t W = h->cfg.width;
+    const size_t wpx = dn_win_px(h, b), own = wpx + (size_t)b.top * W;
+    float4 *guide = (float4 *)h->d_dn_guide.p;
+    hipError_t e = denoise_timed(h, st, hipSuccess, [&] {
+        return launch_denoise_guide(sc, gbuf_band(h), guide + 2u * own, c.sigma_plane, st);
+    });
+    if (c.temporal) {
+        const int rd = h->dn_set;
+        b.wr = h->dn_set ^ 1;
+        const uint32_t mode = !h->dn_hist_valid ? 0u : std::memcmp(h->dn_camera, h->uniform + 4, sizeof h->dn_camera) == 0 ? 1u : 2u;
+        h->dn_hist_valid = false;  // (until every launch of this call is enqueued)
+        // dn_temporal runs on the band's own rows; the previous state covers [dn_cov_lo, dn_cov_hi)
+        DnWin win{h->cfg.row_begin - b.top, b.top + h->band_h + b.bot, b.top, b.top + h->band_h};
+        const uint32_t buf0 = h->cfg.row_begin - h->dn_cap_top;  // the frame's row of the buffers' row 0
+        const uint32_t plo = mode ? h->dn_cov_lo : h->cfg.row_begin, phi = mode ? h->dn_cov_hi : h->cfg.row_end;
+        const size_t ppx = (size_t)(plo - buf0) * W;
+        e = denoise_timed(h, st, e, [&] {
+            return launch_denoise_temporal(W, h->cfg.height, win, h->dn_vp, c.alpha_min, mode, plo, phi - plo, guide + 2u * wpx,
+                                           (const float4 *)h->d_frame_color.p, (const float4 *)h->d_accum.p,
+                                           (const float4 *)h->d_dn_guide_prev.p + 2u * ppx,
+                                           (const float4 *)h->d_dn_hist[rd].p + ppx, (const float2 *)h->d_dn_mom[rd].p + ppx,
+                                           (float4 *)h->d_dn_hist[b.wr].p + wpx, (float2 *)h->d_dn_mom[b.wr].p + wpx,
+                                           (unsigned long long *)h->d_counters.p + CNT_DENOISE_CLIP, st);
+        });
+    }
+    if (e != hipSuccess) return fail(h, PTX_E_HIP, "denoiser launch: %s", hipGetErrorString(e));
+    return PTX_OK;
+}
+
+int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b) {
+    const hipStream_t st = h->cur().stream;
+    const Scene sc = make_scene(h);
+    const uint32_t W = h->cfg.width, n = c.n, y0 = h->cfg.row_begin - b.top, rows = b.top + h->band_h + b.bot;
+    const size_t wpx = dn_win_px(h, b);
+    float4 *guide = (float4 *)h->d_dn_guide.p + 2u * wpx;
+    // the working image alternates between the two buffers; the last iteration writes the output
+    float4 *buf[2] = {(float4 *)h->d_dn_work.p + wpx, (float4 *)h->d_denoised.p + wpx};
+    uint32_t cur = n & 1u ? 0u : 1u;
+    hipError_t e = hipSuccess;
+    if (b.top + b.bot)
+        e = denoise_timed(h, st, e, [&] {
+            return launch_denoise_guide_halo(sc, (const uint4 *)h->d_dn_halo_g.p, b.top, b.bot, guide, c.sigma_plane, st);
+        });
+    const DnWin vw = denoise_stage_rows(y0, rows, b.top, h->band_h, n, -1);
+    if (!c.temporal) {
+        const DnImage img{(const float4 *)h->d_accum.p, (const float4 *)h->d_dn_halo_c.p, b.top, b.top + h->band_h};
+        e = denoise_timed(h, st, e, [&] { return launch_denoise_variance(W, vw, img, guide, buf[cur], st); });
+    } else {
+        e = denoise_timed(h, st, e, [&] {
+            return launch_denoise_variance_moments(W, vw, (const float4 *)h->d_dn_hist[b.wr].p + wpx,
+                                                   (const float2 *)h->d_dn_mom[b.wr].p + wpx, guide, buf[cur], st);
+        });
+    }
+    for (uint32_t i = 0; i < n; ++i, cur ^= 1u) {
+        const DnWin iw = denoise_stage_rows(y0, rows, b.top, h->band_h, n, (int)i);
+        e = denoise_timed(h, st, e, [&] {
+            return launch_denoise_atrous(W, iw, 1u << i, buf[cur], guide, buf[cur ^ 1u], c.sigma_lum, i + 1u == n, st);
+        });
+    }
+    if (e != hipSuccess) return fail(h, PTX_E_HIP, "denoiser launch: %s", hipGetErrorString(e));
+    if (c.temporal) {  // this call is the next one's previous call: its guides (no copy), history set and camera
+        std::swap(h->d_dn_guide, h->d_dn_guide_prev);
+        h->dn_set = b.wr;
+        h->dn_cov_lo = y0;
+        h->dn_cov_hi = y0 + rows;
+        std::memcpy(h->dn_camera, h->uniform + 4, sizeof h->dn_camera);
+        float vpinv[16];
+        std::memcpy(vpinv, h->dn_camera, sizeof vpinv);
+        mat4_inverse(vpinv, h->dn_vp);
+        h->dn_hist_valid = true;
+    }
+    return PTX_OK;
 }
 
 }  // namespace ptx
@@ -1791,7 +1975,8 @@ int ptx_get_stats(ptx_handle *h, ptx_stats *out) {
                         h->d_hist.bytes + h->d_jstate.bytes + h->d_jres.bytes + c.tjstate.bytes + c.tjres.bytes + c.nbr.bytes +
                         c.surf.bytes + h->d_psurf.bytes + c.direct.bytes + h->d_dn_guide.bytes + h->d_dn_work.bytes +
                         h->d_denoised.bytes + h->d_frame_color.bytes + h->d_dn_guide_prev.bytes + h->d_dn_hist[0].bytes +
-                        h->d_dn_hist[1].bytes + h->d_dn_mom[0].bytes + h->d_dn_mom[1].bytes;
+                        h->d_dn_hist[1].bytes + h->d_dn_mom[0].bytes + h->d_dn_mom[1].bytes + h->d_dn_halo_g.bytes +
+                        h->d_dn_halo_c.bytes;
     return PTX_OK;
 }
 
@@ -1955,95 +2140,17 @@ int ptx_present_poll(ptx_handle *h, uint8_t *out, size_t bytes) {
 
 int ptx_denoise(ptx_handle *h, const ptx_denoise_params *p) {
     if (!h) return PTX_E_INVALID;
-    const uint32_t n = p && p->iterations ? p->iterations : 5u;
-    const float sigma_lum = p && p->sigma_lum != 0.0f ? p->sigma_lum : 4.0f;
-    const float sigma_plane = p && p->sigma_plane != 0.0f ? p->sigma_plane : 0.02f;
-    if (n > 6u) return fail(h, PTX_E_INVALID, "ptx_denoise: %u iterations (1..6)", n);
-    if (!(sigma_lum > 0.0f) || !(sigma_plane > 0.0f) || std::isinf(sigma_lum) || std::isinf(sigma_plane))
-        return fail(h, PTX_E_INVALID, "ptx_denoise: sigma_lum %g, sigma_plane %g (finite, > 0)", sigma_lum, sigma_plane);
-    // temporal mode: reserved[0]; its alpha_min is reserved[1]'s bits as an f32 (0 = 0.05)
-    const uint32_t temporal = p ? p->reserved[0] : 0u;
-    float alpha_min = 0.05f;
-    if (temporal > 1u) return fail(h, PTX_E_INVALID, "ptx_denoise: temporal %u (0 or 1)", temporal);
-    if (temporal) {
-        if (p->reserved[1]) std::memcpy(&alpha_min, &p->reserved[1], sizeof alpha_min);
-        if (!(alpha_min > 0.0f && alpha_min <= 1.0f))
-            return fail(h, PTX_E_INVALID, "ptx_denoise: alpha_min %g (finite, in (0, 1])", alpha_min);
-        if (!(h->cfg.flags & PTX_FLAG_FRAME_COLOR))
-            return fail(h, PTX_E_INVALID, "ptx_denoise: the temporal mode integrates PTX_BUF_FRAME_COLOR: create the "
-                                          "handle with PTX_FLAG_FRAME_COLOR");
-    }
+    DnCall c;
+    if (int rc = denoise_params(h, p, c, "ptx_denoise")) return rc;
     if (h->cfg.row_begin != 0 || h->band_h != h->cfg.height)
         return fail(h, PTX_E_INVALID, "ptx_denoise: a band handle (rows %u..%u): the filter reaches 62 rows and a band's "
                                       "accumulation has no halo", h->cfg.row_begin, h->cfg.row_end);
-    if (h->cfg.pipeline == PTX_PIPELINE_MCPT) return fail(h, PTX_E_INVALID, "ptx_denoise: the TEST_MCPT pipeline has no G-buffer");
-    if (!h->rendered || !h->scene_loaded || !h->frame_set || !h->layout_valid)
-        return fail(h, PTX_E_INVALID, "ptx_denoise: nothing rendered");
+    if (int rc = denoise_check(h, c, "ptx_denoise")) return rc;
     HIP_CHECK(h, hipSetDevice(h->device));
-    const uint32_t W = h->cfg.width, H = h->cfg.height;
-    const size_t px = (size_t)W * H;
-    // (first use: nothing of the handle's runs on these buffers yet)
-    if (int rc = alloc_buf(h, h->d_dn_guide, px * 32u)) return rc;
-    if (int rc = alloc_buf(h, h->d_dn_work, px * 16u)) return rc;
-    if (int rc = alloc_buf(h, h->d_denoised, px * 16u)) return rc;
-    if (temporal) {  // the state: 32 + 2 * (16 + 8) bytes per pixel
-        if (int rc = alloc_buf(h, h->d_dn_guide_prev, px * 32u)) return rc;
-        for (int k = 0; k < 2; ++k) {
-            if (int rc = alloc_buf(h, h->d_dn_hist[k], px * 16u)) return rc;
-            if (int rc = alloc_buf(h, h->d_dn_mom[k], px * 8u)) return rc;
-        }
-    }
-    // on the current frame's stream, after it (ptx_present_async's place): a pipelined handle's next
-    // frame records ev_prev on this stream first, and its accumulation waits for ev_prev; this
-    // context's G-buffer is next written by this context's next frame, on this stream.  The frame
-    // colour is written by the kernels that write the accumulation, so the same holds for it; and
-    // the temporal state a call on another context's stream left is read after that frame's
-    // accumulation on this stream, which waited for ev_prev, recorded behind that call.
-    const hipStream_t st = h->cur().stream;
-    const Scene sc = make_scene(h);
-    float4 *guide = (float4 *)h->d_dn_guide.p;
-    // the working image alternates between the two buffers; the last iteration writes the output
-    float4 *buf[2] = {(float4 *)h->d_dn_work.p, (float4 *)h->d_denoised.p};
-    uint32_t cur = n & 1u ? 0u : 1u;
-    auto timed = [&](auto &&launch) {
-        TimedLaunch *t = event_begin(h, PTX_STAT_DENOISE, st);
-        const hipError_t le = launch();
-        event_end(t, st);
-        if (!t && le == hipSuccess) h->launches[PTX_STAT_DENOISE] += 1;  // (untimed handles: the count alone)
-        return le;
-    };
-    hipError_t e = timed([&] { return launch_denoise_guide(sc, gbuf_band(h), guide, sigma_plane, st); });
-    if (e == hipSuccess && !temporal)
-        e = timed([&] { return launch_denoise_variance(W, H, (const float4 *)h->d_accum.p, guide, buf[cur], st); });
-    if (temporal) {
-        const int rd = h->dn_set, wr = h->dn_set ^ 1;
-        const uint32_t mode = !h->dn_hist_valid ? 0u : std::memcmp(h->dn_camera, h->uniform + 4, sizeof h->dn_camera) == 0 ? 1u : 2u;
-        float4 *hist = (float4 *)h->d_dn_hist[wr].p;
-        float2 *mom = (float2 *)h->d_dn_mom[wr].p;
-        h->dn_hist_valid = false;  // (until every launch of this call is enqueued)
-        if (e == hipSuccess)
-            e = timed([&] {
-                return launch_denoise_temporal(W, H, h->dn_vp, alpha_min, mode, guide, (const float4 *)h->d_frame_color.p,
-                                               (const float4 *)h->d_accum.p, (const float4 *)h->d_dn_guide_prev.p,
-                                               (const float4 *)h->d_dn_hist[rd].p, (const float2 *)h->d_dn_mom[rd].p, hist, mom, st);
-            });
-        if (e == hipSuccess) e = timed([&] { return launch_denoise_variance_moments(W, H, hist, mom, guide, buf[cur], st); });
-    }
-    for (uint32_t i = 0; e == hipSuccess && i < n; ++i, cur ^= 1u)
-        e = timed([&] {
-            return launch_denoise_atrous(W, H, 1u << i, buf[cur], guide, buf[cur ^ 1u], sigma_lum, i + 1u == n, st);
-        });
-    if (e != hipSuccess) return fail(h, PTX_E_HIP, "ptx_denoise: %s", hipGetErrorString(e));
-    if (temporal) {  // this call is the next one's previous call: its guides (no copy), history set and camera
-        std::swap(h->d_dn_guide, h->d_dn_guide_prev);
-        h->dn_set ^= 1;
-        std::memcpy(h->dn_camera, h->uniform + 4, sizeof h->dn_camera);
-        float vpinv[16];
-        std::memcpy(vpinv, h->dn_camera, sizeof vpinv);
-        mat4_inverse(vpinv, h->dn_vp);
-        h->dn_hist_valid = true;
-    }
-    return PTX_OK;
+    if (int rc = denoise_alloc(h, c)) return rc;
+    DnBand b;  // (the window is the image)
+    if (int rc = denoise_front(h, c, b)) return rc;
+    return denoise_back(h, c, b);
 }
 
 int ptx_present_source(ptx_handle *h, int which) {
@@ -2121,7 +2228,7 @@ int ptx_destroy(ptx_handle *h) {
                       &h->d_insts, &h->d_mats, &h->d_tverts, &h->d_accum, &h->d_counters, &h->d_qrays, &h->d_qhits, &h->d_hist,
                       &h->d_jstate, &h->d_jres, &h->d_psurf, &h->d_census, &h->d_wgt, &h->d_dn_guide, &h->d_dn_work,
                       &h->d_denoised, &h->d_frame_color, &h->d_dn_guide_prev, &h->d_dn_hist[0], &h->d_dn_hist[1], &h->d_dn_mom[0],
-                      &h->d_dn_mom[1]})
+                      &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c})
         free_buf(*b);
     for (auto &c : h->ctx) {
         for (DevBuf *b : {&c.gbuf, &c.res, &c.direct, &c.nbr, &c.tjstate, &c.tjres, &c.surf, &c.wstate, &c.wrays, &c.wres[0],
@@ -2135,6 +2242,8 @@ int ptx_destroy(ptx_handle *h) {
         if (c.own) (void)hipStreamDestroy(c.own);
     }
     if (h->ev_prev) (void)hipEventDestroy(h->ev_prev);
+    if (h->ev_dn_ready) (void)hipEventDestroy(h->ev_dn_ready);
+    if (h->ev_dn_copied) (void)hipEventDestroy(h->ev_dn_copied);
     delete h;
     return PTX_OK;
 }

@@ -13,6 +13,8 @@
 //   * inside one process (ptx_render_bands, e.g. one Node host driving every GPU, or several
 //     bands on one GPU): the same through the handles' communicators, or hipMemcpyPeerAsync
 //     when the handles have none.
+// The denoiser of a split frame (ptx_denoise_bands) exchanges a second halo the
+// same two ways: the rows of the neighbours' G-buffer and colours (or temporal state) its filter reaches.
 // PTX_FLAG_HALO_OVERLAP splits the spatial pass into the rows whose neighbourhood lies inside
 // the band (run while the halo is in flight) and the edge rows (run when it has landed).
 //
@@ -386,6 +388,7 @@ int band_back(ptx_handle *h, const Scene &sc, const WaveBufs &w, TimedLaunch *fr
     frame_t->pass = PTX_STAT_FRAME;
     frame_t->pending = true;
     h->frames++;
+    h->rendered = true;  // (ptx_denoise_bands asks)
     return PTX_OK;
 }
 
@@ -440,6 +443,10 @@ int check_neighbours(ptx_handle *h) {
         return done(fail(h, PTX_E_HIP, "neighbour check: %s", hipGetErrorString(e)));
     }
     const uint32_t *up = got[0], *dn = got[1];
+    for (int k = 0; k < 2; ++k) {  // (kept for ptx_denoise_bands' rank form: a neighbour's rows)
+        h->nb_rows[k][0] = got[k][2];
+        h->nb_rows[k][1] = got[k][3];
+    }
     if (h->rank > 0 && (up[0] != mine[0] || up[1] != mine[1] || up[3] != mine[2] || up[5] != mine[4]))
         return done(fail(h, PTX_E_INVALID,
                          "ptx_comm_init: rank %d has rows [%u,%u) with a %u-row halo below in a %ux%u frame; this band "
@@ -451,6 +458,66 @@ int check_neighbours(ptx_handle *h) {
                          "(rank %d) ends at row %u with a %u-row halo below in a %ux%u frame",
                          h->rank + 1, dn[2], dn[3], dn[4], dn[0], dn[1], h->rank, mine[3], mine[5], mine[0], mine[1]));
     return done(PTX_OK);
+}
+
+// ---- ptx_denoise_bands: the denoiser's halo.  Band h filters the window of its rows and b.top /
+// b.bot rows of its neighbours; per halo pixel it needs the neighbour's G-buffer texel and, in
+// spatial mode, its accumulated colour, in temporal mode the {C, n} and {m1, m2} its dn_temporal
+// just wrote.  All are contiguous rows of buffers the neighbour holds: its last `rows` own rows
+// (for the band below it) or its first (for the band above).
+struct DnRows {
+    char *g, *c, *m;   // texels, colour or history, moments (temporal mode)
+    size_t gb, cb, mb;
+};
+// the own rows [r0, r0 + rows) of band h that a neighbour reads
+DnRows dn_send_rows(ptx_handle *h, const DnCall &c, const DnBand &b, uint32_t r0, uint32_t rows) {
+    const size_t W = h->cfg.width, n = (size_t)rows * W, own = ((size_t)h->dn_cap_top + r0) * W;
+    DnRows r{(char *)gbuf_band(h) + (size_t)r0 * W * 16u, nullptr, nullptr, n * 16u, n * 16u, 0};
+    if (c.temporal) {
+        r.c = (char *)h->d_dn_hist[b.wr].p + own * 16u;
+        r.m = (char *)h->d_dn_mom[b.wr].p + own * 8u;
+        r.mb = n * 8u;
+    } else {
+        r.c = (char *)h->d_accum.p + (size_t)r0 * W * 16u;
+    }
+    return r;
+}
+// where band h receives its top (above = true) or bottom halo rows
+DnRows dn_recv_rows(ptx_handle *h, const DnCall &c, const DnBand &b, bool above) {
+    const size_t W = h->cfg.width, rows = above ? b.top : b.bot, n = rows * W;
+    const size_t hrow = above ? 0u : b.top;  // (the received texels and colours: top rows, then bottom rows)
+    const size_t srow = above ? h->dn_cap_top - b.top : h->dn_cap_top + h->band_h;  // (the state's halo rows)
+    DnRows r{(char *)h->d_dn_halo_g.p + hrow * W * 16u, nullptr, nullptr, n * 16u, n * 16u, 0};
+    if (c.temporal) {
+        r.c = (char *)h->d_dn_hist[b.wr].p + srow * W * 16u;
+        r.m = (char *)h->d_dn_mom[b.wr].p + srow * W * 8u;
+        r.mb = n * 8u;
+    } else {
+        r.c = (char *)h->d_dn_halo_c.p + hrow * W * 16u;
+    }
+    return r;
+}
+// Enqueue band h's sends / receives on its communicator (inside a group), on its stream: behind its
+// frame and its dn_temporal, ahead of the rest of its call.  Per neighbour the messages go in one
+// order on both sides (texels, colour or history, moments).
+int nccl_dn_halo(ptx_handle *h, const DnCall &c, const DnBand &b) {
+    const Rccl &R = rccl();
+    ncclComm_t cm = (ncclComm_t)h->comm;
+    const hipStream_t st = h->cur().stream;
+    for (int side = 0; side < 2; ++side) {
+        const uint32_t rows = side == 0 ? b.top : b.bot;  // (every band's halo is the call's reach: what it receives it sends)
+        if (!rows) continue;
+        const int peer = side == 0 ? h->rank - 1 : h->rank + 1;
+        const DnRows s = dn_send_rows(h, c, b, side == 0 ? 0u : h->band_h - rows, rows), r = dn_recv_rows(h, c, b, side == 0);
+        NCCL_CHECK(h, R.send(s.g, s.gb, ncclUint8, peer, cm, st));
+        NCCL_CHECK(h, R.send(s.c, s.cb, ncclUint8, peer, cm, st));
+        if (s.mb) NCCL_CHECK(h, R.send(s.m, s.mb, ncclUint8, peer, cm, st));
+        NCCL_CHECK(h, R.recv(r.g, r.gb, ncclUint8, peer, cm, st));
+        NCCL_CHECK(h, R.recv(r.c, r.cb, ncclUint8, peer, cm, st));
+        if (r.mb) NCCL_CHECK(h, R.recv(r.m, r.mb, ncclUint8, peer, cm, st));
+        h->halo_bytes_sent += s.gb + s.cb + s.mb;
+    }
+    return PTX_OK;
 }
 
 }  // namespace
@@ -781,6 +848,128 @@ int ptx_render_bands(ptx_handle *const *hs, int n, float *rgba_out) {
             HIP_CHECK(hs[i], hipSetDevice(h->device));
             if (int rc = read_to_host(h, (char *)rgba_out + off, h->d_accum.p, h->d_accum.bytes)) return rc;
             off += h->d_accum.bytes;
+        }
+    }
+    return PTX_OK;
+}
+
+int ptx_denoise_bands(ptx_handle *const *hs, int n, const ptx_denoise_params *p) {
+    if (!hs || n < 1 || n > 64) return PTX_E_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (!hs[i]) return PTX_E_INVALID;
+    ptx_handle *h0 = hs[0];
+    const char *what = "ptx_denoise_bands";
+    // ---- refusals, all before any GPU work
+    DnCall c;
+    if (int rc = denoise_params(h0, p, c, what)) return rc;
+    const bool nccl = h0->comm != nullptr;
+    // the rank form: one band of a frame whose other bands are other ranks' (every rank makes the call)
+    const bool rank_form = n == 1 && nccl && h0->world > 1;
+    const uint32_t R = dn_reach(c.n), H = h0->cfg.height;
+    for (int i = 0; i < n; ++i) {
+        ptx_handle *h = hs[i];
+        if (h->cfg.width != h0->cfg.width || h->cfg.height != H || h->cfg.pipeline != h0->cfg.pipeline)
+            return fail(h, PTX_E_INVALID, "%s: band %d differs in size or pipeline", what, i);
+        if ((h->comm != nullptr) != nccl) return fail(h, PTX_E_INVALID, "%s: either every band owns a communicator or none", what);
+        if (nccl && !rank_form && n > 1 && (h->rank != i || h->world != n))
+            return fail(h, PTX_E_INVALID, "%s: band %d is rank %d of %d", what, i, h->rank, h->world);
+        if (i && hs[i - 1]->cfg.row_end != h->cfg.row_begin)
+            return fail(h, PTX_E_INVALID, "%s: band %d does not start where band %d ends", what, i, i - 1);
+        if (int rc = denoise_check(h, c, what)) return rc;
+    }
+    if (!rank_form && (h0->cfg.row_begin != 0 || hs[n - 1]->cfg.row_end != H))
+        return fail(h0, PTX_E_INVALID, "%s: the bands cover rows %u..%u of %u: a window needs the rows above and below it",
+                    what, h0->cfg.row_begin, hs[n - 1]->cfg.row_end, H);
+    if (n > 1 || rank_form) {  // a band's halo comes from the bands next to it alone
+        for (int i = 0; i < n; ++i)
+            if (hs[i]->band_h < R)
+                return fail(hs[i], PTX_E_INVALID, "%s: band %d has %u rows; %u iterations need %u rows of every band",
+                            what, rank_form ? h0->rank : i, hs[i]->band_h, c.n, R);
+    }
+    if (rank_form) {
+        ptx_handle *h = h0;
+        if ((h->cfg.row_begin != 0) != (h->rank > 0) || (h->cfg.row_end != H) != (h->rank + 1 < h->world))
+            return fail(h, PTX_E_INVALID, "%s: rank %d of %d holds rows %u..%u of %u", what, h->rank, h->world,
+                        h->cfg.row_begin, h->cfg.row_end, H);
+        for (int k = 0; k < 2; ++k) {
+            if (k == 0 ? h->rank == 0 : h->rank + 1 == h->world) continue;
+            const uint32_t rows = h->nb_rows[k][1] - h->nb_rows[k][0];
+            if (rows < R)
+                return fail(h, PTX_E_INVALID, "%s: band %d has %u rows; %u iterations need %u rows of every band", what,
+                            k == 0 ? h->rank - 1 : h->rank + 1, rows, c.n, R);
+        }
+    }
+    if (nccl)
+        for (int i = 0; i < n; ++i)
+            if (int rc = comm_health(hs[i])) return rc;
+    // ---- every band: its buffers, its window, and what comes before the exchange
+    std::vector<DnBand> b(n);
+    for (int i = 0; i < n; ++i) {
+        ptx_handle *h = hs[i];
+        HIP_CHECK(h, hipSetDevice(h->device));
+        if (int rc = denoise_alloc(h, c)) return rc;
+        b[i].top = std::min(R, h->cfg.row_begin);
+        b[i].bot = std::min(R, H - h->cfg.row_end);
+        if (int rc = denoise_front(h, c, b[i])) return rc;
+    }
+    // ---- the exchange
+    if (nccl && (n > 1 || rank_form)) {  // one group per call
+        NCCL_CHECK(h0, rccl().group_start());
+        int rc = PTX_OK;
+        for (int i = 0; i < n && !rc; ++i) {
+            HIP_CHECK(hs[i], hipSetDevice(hs[i]->device));
+            rc = nccl_dn_halo(hs[i], c, b[i]);
+        }
+        if (rc) {
+            (void)rccl().group_end();
+            return rc;
+        }
+        if (rank_form) {
+            if (int r2 = group_end_wait(h0)) return r2;
+        } else {
+            NCCL_CHECK(h0, rccl().group_end());
+        }
+    } else if (n > 1) {
+        // peer copies, ordered as ptx_render_bands orders its halo: a band's rows are ready behind its
+        // frame (temporal mode: behind its dn_temporal); a band copies once its neighbours' are ready ...
+        for (int i = 0; i < n; ++i) {
+            ptx_handle *h = hs[i];
+            HIP_CHECK(h, hipSetDevice(h->device));
+            if (!h->ev_dn_ready) HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_dn_ready, hipEventDisableTiming));
+            if (!h->ev_dn_copied) HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_dn_copied, hipEventDisableTiming));
+            HIP_CHECK(h, hipEventRecord(h->ev_dn_ready, h->cur().stream));
+        }
+        for (int i = 0; i < n; ++i) {
+            ptx_handle *h = hs[i];
+            HIP_CHECK(h, hipSetDevice(h->device));
+            const hipStream_t st = h->cur().stream;
+            for (int side = 0; side < 2; ++side) {
+                const uint32_t rows = side == 0 ? b[i].top : b[i].bot;
+                if (!rows) continue;
+                ptx_handle *a = hs[side == 0 ? i - 1 : i + 1];
+                const DnBand &ab = b[side == 0 ? i - 1 : i + 1];
+                const DnRows s = dn_send_rows(a, c, ab, side == 0 ? a->band_h - rows : 0u, rows),
+                             r = dn_recv_rows(h, c, b[i], side == 0);
+                HIP_CHECK(h, hipStreamWaitEvent(st, a->ev_dn_ready, 0));
+                HIP_CHECK(h, hipMemcpyPeerAsync(r.g, h->device, s.g, a->device, r.gb, st));
+                HIP_CHECK(h, hipMemcpyPeerAsync(r.c, h->device, s.c, a->device, r.cb, st));
+                if (r.mb) HIP_CHECK(h, hipMemcpyPeerAsync(r.m, h->device, s.m, a->device, r.mb, st));
+            }
+            HIP_CHECK(h, hipEventRecord(h->ev_dn_copied, st));
+        }
+    }
+    // ---- every band: the rest of its call on its window
+    for (int i = 0; i < n; ++i) {
+        HIP_CHECK(hs[i], hipSetDevice(hs[i]->device));
+        if (int rc = denoise_back(hs[i], c, b[i])) return rc;
+    }
+    if (!nccl && n > 1) {
+        // ... and a band's next frame (it records ev_prev on this stream first) starts once its
+        // neighbours have copied its rows: a frame enqueued right after the call overwrites them
+        for (int i = 0; i < n; ++i) {
+            HIP_CHECK(hs[i], hipSetDevice(hs[i]->device));
+            if (i > 0) HIP_CHECK(hs[i], hipStreamWaitEvent(hs[i]->cur().stream, hs[i - 1]->ev_dn_copied, 0));
+            if (i + 1 < n) HIP_CHECK(hs[i], hipStreamWaitEvent(hs[i]->cur().stream, hs[i + 1]->ev_dn_copied, 0));
         }
     }
     return PTX_OK;

@@ -2,13 +2,17 @@
 // DESIGN.md §Denoiser): guided by the primary hit of the frame context's G-buffer, variance
 // estimated spatially from the image; in temporal mode the image is the frame colours integrated
 // over the calls, looked up through the previous call's camera (tests/denoise_temporal_ref.py).
-// All kernels one lane per pixel, no atomics:
+// All kernels one lane per pixel; the one atomic is dn_temporal's count of clipped pixels, one add
+// per wave that has any:
 //   dn_guide     G-buffer texel -> 32-byte guide record {P.xyz, key | kDnMiss}{N.xyz, r}
 //   dn_temporal  (temporal mode) history lookup + integration -> history {C.rgb, n}, moments {m1, m2}
 //   dn_variance  7x7 guide-weighted luminance moments -> working image {r, g, b, v}; <true>: on the
 //                history, the integrated moments' variance where n >= 4
 //   dn_atrous    one iteration at step 2^i on the working image (ping-pong); steps 1, 2, 4 stage
 //                the 16x16 tile and its apron in LDS, steps >= 8 gather their taps directly
+// Every kernel but dn_guide addresses a row window (DnWin): a W x rows image that is the whole
+// frame, or a band with the halo rows ptx_denoise_bands brought from its neighbours, filtered as if
+// it were the whole image; a launch computes rows [c0, c1) of it.
 // Arithmetic is the definition's, operation by operation (tests/denoise_ref.py restates it in
 // numpy and the outputs are compared bit for bit): f32, no contraction, sums in tap order, a
 // skipped tap leaves every sum untouched.
@@ -21,13 +25,8 @@ constexpr int kDnTile = 16;                // a workgroup's pixels: 16 x 16, thr
 static_assert(kDnTile * kDnTile == kBlock, "one lane per pixel of the tile");
 
 // ---------------------------------------------------------------- guide records
-__global__ __launch_bounds__(kBlock) void dn_guide(const Scene sc, const uint4 *__restrict__ gbuf,
-                                                   float4 *__restrict__ guide, float sigma_plane) {
-    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
-    uint32_t x, y;
-    if (p >= padded_pixels(sc) || !tile_xy(sc, p, x, y)) return;
-    const size_t pix = (size_t)y * sc.width + x;
-    const uint4 g = gbuf[pix];
+__device__ __forceinline__ void dn_guide_px(const Scene &sc, uint4 g, float4 *__restrict__ guide, size_t pix,
+                                            float sigma_plane) {
     if (!(g.x & 0x80000000u)) {
         guide[2u * pix] = make_float4(0.0f, 0.0f, 0.0f, asf(kDnMiss));
         guide[2u * pix + 1u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -38,6 +37,34 @@ __global__ __launch_bounds__(kBlock) void dn_guide(const Scene sc, const uint4 *
     const float r = sigma_plane * length(X.pos - cam);
     guide[2u * pix] = make_float4(X.pos.x, X.pos.y, X.pos.z, asf(g.x & 0x7fffffffu));
     guide[2u * pix + 1u] = make_float4(X.nrm.x, X.nrm.y, X.nrm.z, r);
+}
+// The band's own rows, read through the Scene's tiling: `gbuf` and `guide` start at the band's first row.
+__global__ __launch_bounds__(kBlock) void dn_guide(const Scene sc, const uint4 *__restrict__ gbuf,
+                                                   float4 *__restrict__ guide, float sigma_plane) {
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t x, y;
+    if (p >= padded_pixels(sc) || !tile_xy(sc, p, x, y)) return;
+    const size_t pix = (size_t)(y - sc.row_begin) * sc.width + x;
+    dn_guide_px(sc, gbuf[pix], guide, pix, sigma_plane);
+}
+// A window's halo rows, from the neighbours' texels: `texels` holds the `top` rows above the band,
+// then the rows below it; texel row r is window row r (r < top) or r + skip (skip = the band's rows).
+__global__ __launch_bounds__(kBlock) void dn_guide_halo(const Scene sc, const uint4 *__restrict__ texels, uint32_t rows,
+                                                        uint32_t top, uint32_t skip, float4 *__restrict__ guide,
+                                                        float sigma_plane) {
+    const uint32_t x = blockIdx.x * kDnTile + (threadIdx.x & 15u), r = blockIdx.y * kDnTile + (threadIdx.x >> 4);
+    if (x >= sc.width || r >= rows) return;
+    const uint32_t y = r < top ? r : r + skip;
+    dn_guide_px(sc, texels[(size_t)r * sc.width + x], guide, (size_t)y * sc.width + x, sigma_plane);
+}
+
+// ---------------------------------------------------------------- row window
+// (DnWin and DnImage: ptx_launch.h)  A window's pixel (x, y) is element y * W + x of every buffer a
+// kernel is given; rows outside [0, rows) are outside the image: never a tap.
+// The pixel of a filter input whose own rows and halo rows lie in two buffers.
+__device__ __forceinline__ float4 dn_load(const DnImage &I, uint32_t W, uint32_t x, uint32_t y) {
+    if (y >= I.o0 && y < I.o1) return I.own[(size_t)(y - I.o0) * W + x];
+    return I.halo[(size_t)(y < I.o0 ? y : y - (I.o1 - I.o0)) * W + x];
 }
 
 // ---------------------------------------------------------------- shared arithmetic
@@ -58,20 +85,21 @@ struct DnTile {
     // entry of pixel (tx + dx, ty + dy) of the tile (|dx|, |dy| <= A)
     static __device__ __forceinline__ int at(int tx, int ty, int dx, int dy) { return (ty + A + dy) * N + (tx + A + dx); }
 };
-// Fill the staging area from global memory; pixels outside the image become misses (never a tap).
-template <int A, bool WITH_CV, bool WITH_LUM>
-__device__ __forceinline__ void dn_stage(uint32_t W, uint32_t H, const float4 *__restrict__ guide,
-                                         const float4 *__restrict__ img, float4 *g0, float4 *g1, float4 *cv, float *lum) {
+// Fill the staging area from global memory; pixels outside the window become misses (never a tap).
+// img(x, y): the input's pixel.
+template <int A, bool WITH_CV, bool WITH_LUM, class Img>
+__device__ __forceinline__ void dn_stage(uint32_t W, const DnWin &win, const float4 *__restrict__ guide, Img img,
+                                         float4 *g0, float4 *g1, float4 *cv, float *lum) {
     using T = DnTile<A>;
-    const int x0 = (int)blockIdx.x * kDnTile - A, y0 = (int)blockIdx.y * kDnTile - A;
+    const int x0 = (int)blockIdx.x * kDnTile - A, y0 = (int)(win.c0 + blockIdx.y * kDnTile) - A;
     for (int e = (int)threadIdx.x; e < T::E; e += kBlock) {
         const int gx = x0 + e % T::N, gy = y0 + e / T::N;
         float4 a = make_float4(0.0f, 0.0f, 0.0f, asf(kDnMiss)), b = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = b;
-        if (gx >= 0 && gy >= 0 && gx < (int)W && gy < (int)H) {
+        if (gx >= 0 && gy >= 0 && gx < (int)W && gy < (int)win.rows) {
             const size_t q = (size_t)gy * W + (size_t)gx;
             a = guide[2u * q];
             b = guide[2u * q + 1u];
-            c = img[q];
+            c = img((uint32_t)gx, (uint32_t)gy);
         }
         g0[e] = a;
         g1[e] = b;
@@ -88,33 +116,41 @@ struct DnHistory {
     float vp[16];  // that call's VP (mat4_inverse of its uniform words 4..19)
     float alpha_min;
     uint32_t mode;
+    // the rows of the frame that call's state covers (a band: its window then), [y0, y0 + rows):
+    // pguide, phist and pmom start at row y0
+    uint32_t y0, rows;
 };
 constexpr float kDnNMax = 255.0f;    // the history length saturates here
 constexpr float kDnNMoments = 4.0f;  // from this length on the variance comes from the integrated moments
 
 // History lookup and integration of one pixel: reads this frame's guide record and colour and up to
 // four previous guide / history / moment records, writes the new history {C.rgb, n} and moments
-// {m1, m2}.  The four taps' records are gathered directly, all issued ahead of the tests: under
+// {m1, m2}.  Pixels are projected in the W x H frame's coordinates (the window's row 0 is its row
+// win.y0); `frame` and `accum` start at row c0 of the window (the band's own rows: what a launch
+// computes).  A candidate inside the frame but outside the rows the previous state covers is not
+// taken (as if n' = 0 there), and a pixel with such a candidate counts in *clip.
+// The four taps' records are gathered directly, all issued ahead of the tests: under
 // camera motion a tile's footprint in the previous frame is a shifted, nearly rigid tile, so
 // neighbouring lanes' taps share cache lines, but its extent is not bounded.
-__global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, const DnHistory Hs,
+__global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, const DnWin win, const DnHistory Hs,
                                                       const float4 *__restrict__ guide, const float4 *__restrict__ frame,
                                                       const float4 *__restrict__ accum, const float4 *__restrict__ pguide,
                                                       const float4 *__restrict__ phist, const float2 *__restrict__ pmom,
-                                                      float4 *__restrict__ hist, float2 *__restrict__ mom) {
-    const uint32_t x = blockIdx.x * kDnTile + (threadIdx.x & 15u), y = blockIdx.y * kDnTile + (threadIdx.x >> 4);
-    if (x >= W || y >= H) return;
-    const size_t pix = (size_t)y * W + x;
+                                                      float4 *__restrict__ hist, float2 *__restrict__ mom,
+                                                      unsigned long long *__restrict__ clip) {
+    const uint32_t x = blockIdx.x * kDnTile + (threadIdx.x & 15u), y = win.c0 + blockIdx.y * kDnTile + (threadIdx.x >> 4);
+    if (x >= W || y >= win.c1) return;
+    const size_t pix = (size_t)y * W + x, own = (size_t)(y - win.c0) * W + x;
     const float4 a = guide[2u * pix];
     const uint32_t key = asu(a.w);
     if (key == kDnMiss) {  // no primary hit: the accumulated colour, never a tap (n = 0)
-        const float4 c = accum[pix];
+        const float4 c = accum[own];
         hist[pix] = make_float4(c.x, c.y, c.z, 0.0f);
         mom[pix] = make_float2(0.0f, 0.0f);
         return;
     }
     const float4 b = guide[2u * pix + 1u];
-    const f3 F = rgb(frame[pix]), Pp = rgb(a), Np = rgb(b);
+    const f3 F = rgb(frame[own]), Pp = rgb(a), Np = rgb(b);
     const float l = luminance(F);
     f3 C = F;
     float m1 = l, m2 = l * l, n = 1.0f;
@@ -122,10 +158,12 @@ __global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, co
         // candidate taps k = 2 j + i (j outer): pixel, bilinear weight, inside the image
         size_t q[4];
         float w[4];
-        bool in[4];
+        bool in[4], clipped = false;
+        // this pixel in the previous state (a band's own rows are always covered)
+        const size_t pc = (size_t)(win.y0 + y - Hs.y0) * W + x;
         if (Hs.mode == 1u) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { q[k] = pix; w[k] = 1.0f; in[k] = k == 0; }
+            for (int k = 0; k < 4; ++k) { q[k] = pc; w[k] = 1.0f; in[k] = k == 0; }
         } else {
             const float *vp = Hs.vp;
             const float cx = ((vp[0] * Pp.x + vp[4] * Pp.y) + vp[8] * Pp.z) + vp[12];
@@ -140,9 +178,16 @@ __global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, co
                 const float qx = x0 + (float)i, qy = y0 + (float)j;
                 // (a NaN or infinite projection compares false: outside)
                 in[k] = cw > 0.0f && qx >= 0.0f && qx < (float)W && qy >= 0.0f && qy < (float)H;
-                q[k] = in[k] ? (size_t)(int)qy * W + (size_t)(int)qx : pix;  // (an outside tap loads the centre, unused)
+                const uint32_t ry = (uint32_t)(in[k] ? (int)qy : (int)Hs.y0) - Hs.y0;  // (below y0: wraps past rows)
+                if (in[k] && ry >= Hs.rows) {
+                    clipped = true;
+                    in[k] = false;
+                }
+                q[k] = in[k] ? (size_t)ry * W + (size_t)(int)qx : pc;  // (an outside tap loads the centre, unused)
                 w[k] = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
             }
+            const unsigned long long cm = __ballot(clipped);  // (over the wave's lanes that look a history up)
+            if (clipped && __lane_id() == (uint32_t)__ffsll((long long)cm) - 1u) atomicAdd(clip, (unsigned long long)__popcll(cm));
         }
         float4 qa[4], qb[4], qh[4];
         float2 qm[4];
@@ -206,19 +251,22 @@ __device__ __forceinline__ float dn_var7(const float4 *g0, const float4 *g1, con
 }
 // MOMENTS (temporal mode): `img` is the new history {C.rgb, n}; where n >= kDnNMoments the variance
 // is the integrated moments', and the 7x7 sums run only elsewhere.
+// The input is a DnImage: the accumulation's halo rows lie in a buffer of their own (the history is
+// one buffer: o0 = 0, o1 = rows).
 template <bool MOMENTS>
-__global__ __launch_bounds__(kBlock) void dn_variance(uint32_t W, uint32_t H, const float4 *__restrict__ img,
+__global__ __launch_bounds__(kBlock) void dn_variance(uint32_t W, const DnWin win, const DnImage img,
                                                       const float2 *__restrict__ mom, const float4 *__restrict__ guide,
                                                       float4 *__restrict__ out) {
     using T = DnTile<3>;
     __shared__ float4 g0[T::E], g1[T::E];
     __shared__ float lum[T::E];
-    dn_stage<3, false, true>(W, H, guide, img, g0, g1, nullptr, lum);
+    dn_stage<3, false, true>(W, win, guide, [&](uint32_t qx, uint32_t qy) { return dn_load(img, W, qx, qy); }, g0, g1,
+                             nullptr, lum);
     const int tx = (int)(threadIdx.x & 15u), ty = (int)(threadIdx.x >> 4);
-    const uint32_t x = blockIdx.x * kDnTile + (uint32_t)tx, y = blockIdx.y * kDnTile + (uint32_t)ty;
-    if (x >= W || y >= H) return;
+    const uint32_t x = blockIdx.x * kDnTile + (uint32_t)tx, y = win.c0 + blockIdx.y * kDnTile + (uint32_t)ty;
+    if (x >= W || y >= win.c1) return;
     const size_t pix = (size_t)y * W + x;
-    const float4 c = img[pix];
+    const float4 c = dn_load(img, W, x, y);
     const float4 a = g0[T::at(tx, ty, 0, 0)], b = g1[T::at(tx, ty, 0, 0)];
     float v = 0.0f;
     if (asu(a.w) != kDnMiss) {
@@ -249,15 +297,16 @@ __device__ __forceinline__ float dn_w3(int d) { return d == 0 ? 0.5f : 0.25f; }
 
 // Steps 1, 2, 4: the tile and its apron of 2 * STEP pixels in LDS (48 B per entry: 19 / 27 / 48 KiB).
 template <int STEP>
-__global__ __launch_bounds__(kBlock) void dn_atrous_tiled(uint32_t W, uint32_t H, const float4 *__restrict__ in,
+__global__ __launch_bounds__(kBlock) void dn_atrous_tiled(uint32_t W, const DnWin win, const float4 *__restrict__ in,
                                                           const float4 *__restrict__ guide, float4 *__restrict__ out,
                                                           float sigma_lum, uint32_t last) {
     using T = DnTile<2 * STEP>;
     __shared__ float4 g0[T::E], g1[T::E], cv[T::E];
-    dn_stage<2 * STEP, true, false>(W, H, guide, in, g0, g1, cv, nullptr);
+    dn_stage<2 * STEP, true, false>(W, win, guide, [&](uint32_t qx, uint32_t qy) { return in[(size_t)qy * W + qx]; }, g0,
+                                    g1, cv, nullptr);
     const int tx = (int)(threadIdx.x & 15u), ty = (int)(threadIdx.x >> 4);
-    const uint32_t x = blockIdx.x * kDnTile + (uint32_t)tx, y = blockIdx.y * kDnTile + (uint32_t)ty;
-    if (x >= W || y >= H) return;
+    const uint32_t x = blockIdx.x * kDnTile + (uint32_t)tx, y = win.c0 + blockIdx.y * kDnTile + (uint32_t)ty;
+    if (x >= W || y >= win.c1) return;
     const int ec = T::at(tx, ty, 0, 0);
     const float4 a = g0[ec], b = g1[ec], c = cv[ec];
     const uint32_t key = asu(a.w);
@@ -293,11 +342,12 @@ __global__ __launch_bounds__(kBlock) void dn_atrous_tiled(uint32_t W, uint32_t H
 
 // Steps >= 8: a pixel's taps share no cache line with its neighbours' -- gathered directly, one
 // tap row's 15 loads issued together ahead of that row's weight chains.
-__global__ __launch_bounds__(kBlock) void dn_atrous_gather(uint32_t W, uint32_t H, int step, const float4 *__restrict__ in,
-                                                           const float4 *__restrict__ guide, float4 *__restrict__ out,
-                                                           float sigma_lum, uint32_t last) {
-    const int x = (int)(blockIdx.x * kDnTile + (threadIdx.x & 15u)), y = (int)(blockIdx.y * kDnTile + (threadIdx.x >> 4));
-    if (x >= (int)W || y >= (int)H) return;
+__global__ __launch_bounds__(kBlock) void dn_atrous_gather(uint32_t W, const DnWin win, int step,
+                                                           const float4 *__restrict__ in, const float4 *__restrict__ guide,
+                                                           float4 *__restrict__ out, float sigma_lum, uint32_t last) {
+    const int x = (int)(blockIdx.x * kDnTile + (threadIdx.x & 15u)), y = (int)(win.c0 + blockIdx.y * kDnTile + (threadIdx.x >> 4));
+    const int H = (int)win.rows;
+    if (x >= (int)W || y >= (int)win.c1) return;
     const size_t pix = (size_t)y * W + (size_t)x;
     const float4 a = guide[2u * pix], b = guide[2u * pix + 1u], c = in[pix];
     const uint32_t key = asu(a.w);
@@ -309,7 +359,7 @@ __global__ __launch_bounds__(kBlock) void dn_atrous_gather(uint32_t W, uint32_t 
 #pragma unroll
             for (int dx = -1; dx <= 1; ++dx) {
                 const int qx = x + dx, qy = y + dy;
-                const bool inside = qx >= 0 && qy >= 0 && qx < (int)W && qy < (int)H;
+                const bool inside = qx >= 0 && qy >= 0 && qx < (int)W && qy < H;
                 const size_t q = inside ? (size_t)qy * W + (size_t)qx : pix;
                 const uint32_t kq = asu(guide[2u * q].w);
                 const float vq = in[q].w;
@@ -321,7 +371,7 @@ __global__ __launch_bounds__(kBlock) void dn_atrous_gather(uint32_t W, uint32_t 
         DnSums S{0.0f, mk(0.0f, 0.0f, 0.0f), 0.0f};
         for (int dy = -2; dy <= 2; ++dy) {
             const int qy = y + step * dy;
-            const bool row_in = qy >= 0 && qy < (int)H;
+            const bool row_in = qy >= 0 && qy < H;
             float4 qa[5], qb[5], qc[5];
             bool ok[5];
 #pragma unroll
@@ -347,42 +397,55 @@ __global__ __launch_bounds__(kBlock) void dn_atrous_gather(uint32_t W, uint32_t 
 }
 
 // ---------------------------------------------------------------- launches
-static dim3 dn_grid(uint32_t W, uint32_t H) { return dim3((W + kDnTile - 1) / kDnTile, (H + kDnTile - 1) / kDnTile); }
+static dim3 dn_grid(uint32_t W, const DnWin &win) {
+    return dim3((W + kDnTile - 1) / kDnTile, (win.c1 - win.c0 + kDnTile - 1) / kDnTile);
+}
 
 hipError_t launch_denoise_guide(const Scene &sc, const uint4 *gbuf, float4 *guide, float sigma_plane, hipStream_t s) {
     const uint32_t tiles = ((sc.width + 7u) / 8u) * ((sc.row_end - sc.row_begin + 7u) / 8u);
     hipLaunchKernelGGL(dn_guide, dim3((tiles * 64u + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, gbuf, guide, sigma_plane);
     return hipGetLastError();
 }
-hipError_t launch_denoise_variance(uint32_t W, uint32_t H, const float4 *accum, const float4 *guide, float4 *out,
-                                   hipStream_t s) {
-    hipLaunchKernelGGL(dn_variance<false>, dn_grid(W, H), dim3(kBlock), 0, s, W, H, accum, (const float2 *)nullptr, guide, out);
+hipError_t launch_denoise_guide_halo(const Scene &sc, const uint4 *texels, uint32_t top, uint32_t bottom, float4 *guide,
+                                     float sigma_plane, hipStream_t s) {
+    const uint32_t rows = top + bottom;
+    hipLaunchKernelGGL(dn_guide_halo, dim3((sc.width + kDnTile - 1) / kDnTile, (rows + kDnTile - 1) / kDnTile), dim3(kBlock), 0,
+                       s, sc, texels, rows, top, sc.row_end - sc.row_begin, guide, sigma_plane);
     return hipGetLastError();
 }
-hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const float *vp_prev, float alpha_min, uint32_t mode,
-                                   const float4 *guide, const float4 *frame, const float4 *accum, const float4 *pguide,
-                                   const float4 *phist, const float2 *pmom, float4 *hist, float2 *mom, hipStream_t s) {
+hipError_t launch_denoise_variance(uint32_t W, const DnWin &win, const DnImage &img, const float4 *guide, float4 *out,
+                                   hipStream_t s) {
+    hipLaunchKernelGGL(dn_variance<false>, dn_grid(W, win), dim3(kBlock), 0, s, W, win, img, (const float2 *)nullptr, guide, out);
+    return hipGetLastError();
+}
+hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const DnWin &win, const float *vp_prev, float alpha_min,
+                                   uint32_t mode, uint32_t prev_y0, uint32_t prev_rows, const float4 *guide,
+                                   const float4 *frame, const float4 *accum, const float4 *pguide, const float4 *phist,
+                                   const float2 *pmom, float4 *hist, float2 *mom, unsigned long long *clip, hipStream_t s) {
     DnHistory Hs{};
     for (int i = 0; i < 16; ++i) Hs.vp[i] = vp_prev[i];
     Hs.alpha_min = alpha_min;
     Hs.mode = mode;
-    hipLaunchKernelGGL(dn_temporal, dn_grid(W, H), dim3(kBlock), 0, s, W, H, Hs, guide, frame, accum, pguide, phist, pmom,
-                       hist, mom);
+    Hs.y0 = prev_y0;
+    Hs.rows = prev_rows;
+    hipLaunchKernelGGL(dn_temporal, dn_grid(W, win), dim3(kBlock), 0, s, W, H, win, Hs, guide, frame, accum, pguide, phist,
+                       pmom, hist, mom, clip);
     return hipGetLastError();
 }
-hipError_t launch_denoise_variance_moments(uint32_t W, uint32_t H, const float4 *hist, const float2 *mom,
+hipError_t launch_denoise_variance_moments(uint32_t W, const DnWin &win, const float4 *hist, const float2 *mom,
                                            const float4 *guide, float4 *out, hipStream_t s) {
-    hipLaunchKernelGGL(dn_variance<true>, dn_grid(W, H), dim3(kBlock), 0, s, W, H, hist, mom, guide, out);
+    const DnImage img{hist, nullptr, 0u, win.rows};
+    hipLaunchKernelGGL(dn_variance<true>, dn_grid(W, win), dim3(kBlock), 0, s, W, win, img, mom, guide, out);
     return hipGetLastError();
 }
-hipError_t launch_denoise_atrous(uint32_t W, uint32_t H, uint32_t step, const float4 *in, const float4 *guide, float4 *out,
-                                 float sigma_lum, bool last, hipStream_t s) {
-    const dim3 g = dn_grid(W, H), bl(kBlock);
+hipError_t launch_denoise_atrous(uint32_t W, const DnWin &win, uint32_t step, const float4 *in, const float4 *guide,
+                                 float4 *out, float sigma_lum, bool last, hipStream_t s) {
+    const dim3 g = dn_grid(W, win), bl(kBlock);
     const uint32_t l = last ? 1u : 0u;
-    if (step == 1u) hipLaunchKernelGGL(dn_atrous_tiled<1>, g, bl, 0, s, W, H, in, guide, out, sigma_lum, l);
-    else if (step == 2u) hipLaunchKernelGGL(dn_atrous_tiled<2>, g, bl, 0, s, W, H, in, guide, out, sigma_lum, l);
-    else if (step == 4u) hipLaunchKernelGGL(dn_atrous_tiled<4>, g, bl, 0, s, W, H, in, guide, out, sigma_lum, l);
-    else hipLaunchKernelGGL(dn_atrous_gather, g, bl, 0, s, W, H, (int)step, in, guide, out, sigma_lum, l);
+    if (step == 1u) hipLaunchKernelGGL(dn_atrous_tiled<1>, g, bl, 0, s, W, win, in, guide, out, sigma_lum, l);
+    else if (step == 2u) hipLaunchKernelGGL(dn_atrous_tiled<2>, g, bl, 0, s, W, win, in, guide, out, sigma_lum, l);
+    else if (step == 4u) hipLaunchKernelGGL(dn_atrous_tiled<4>, g, bl, 0, s, W, win, in, guide, out, sigma_lum, l);
+    else hipLaunchKernelGGL(dn_atrous_gather, g, bl, 0, s, W, win, (int)step, in, guide, out, sigma_lum, l);
     return hipGetLastError();
 }
 

@@ -412,6 +412,7 @@ constexpr int CNT_CULL_MISS = 5;
 // the previous frame the band holds (its motion halo; ReuseArgs::prev_row_lo / hi) -- such a
 // pixel gets no history, where the whole image would have had it (0 keeps bands bit-identical)
 constexpr int CNT_MOTION_CLIP = 6;
+constexpr int CNT_DENOISE_CLIP = 7;  // PTX_COUNTER_DENOISE_CLIP: dn_temporal's clipped pixels (ptx_denoise_bands)
 __device__ __forceinline__ bool inst_may_hit(const Inst &I, f3 o, f3 winv, float omax, float vy) {
     if (!(I.wpad >= 0.0f)) return true;
     const float p = I.wpad + I.wscale * omax;

@@ -177,6 +177,21 @@ struct ptx_handle {
     bool dn_hist_valid = false;
     uint32_t dn_camera[19] = {0};
     float dn_vp[16] = {0};
+    // ptx_denoise_bands: a band filters the window of its rows and up to 2^(n+1) halo rows on either
+    // side, so the denoiser's buffers of a band handle hold dn_cap_top + band_h + dn_cap_bot rows (the
+    // 128 rows of 6 iterations, or what the frame has: row 0 of a buffer is row
+    // row_begin - dn_cap_top of the frame, whatever a call's iteration count).  Received per call:
+    // the neighbours' G-buffer texels and, in spatial mode, their accumulated colours (top rows, then
+    // bottom rows); the temporal state's halo rows arrive in d_dn_hist / d_dn_mom themselves.
+    uint32_t dn_cap_top = 0, dn_cap_bot = 0;
+    DevBuf d_dn_halo_g, d_dn_halo_c;
+    // the rows of the frame the temporal state covers (the window of the call that wrote it)
+    uint32_t dn_cov_lo = 0, dn_cov_hi = 0;
+    // peer-copy exchange: this band's rows are ready to be copied (the frame; in temporal mode its
+    // dn_temporal) / this band has copied its neighbours' rows
+    hipEvent_t ev_dn_ready = nullptr, ev_dn_copied = nullptr;
+    // the rows [begin, end) of the ranks above and below, as ptx_comm_init's neighbour check received them
+    uint32_t nb_rows[2][2] = {{0, 0}, {0, 0}};
     int present_src = PTX_BUF_ACCUM;
     bool rendered = false;
     // stats
@@ -238,6 +253,27 @@ int ensure_contexts(ptx_handle *h);
 void next_frame_ctx(ptx_handle *h);
 // back to the first frame context (quiesce first) before the handle's stream or mode changes
 int first_frame_ctx(ptx_handle *h);
+// The denoiser's host side (ptx_api.cpp), shared by ptx_denoise and ptx_denoise_bands (ptx_comm.cpp).
+// One call's parameters, and per band its window: `top` / `bot` halo rows this call uses.
+struct DnCall {
+    uint32_t n = 5, temporal = 0;
+    float sigma_lum = 4.0f, sigma_plane = 0.02f, alpha_min = 0.05f;
+};
+struct DnBand {
+    uint32_t top = 0, bot = 0;
+    int wr = 0;  // temporal mode: the state set this call writes
+};
+inline uint32_t dn_reach(uint32_t n) { return 2u << n; }  // halo rows of n iterations: 2^(n+1)
+// parameters in range (what: the entry point's name, for messages); this handle can denoise
+// (pipeline, flag, a frame rendered) -- both before any GPU work
+int denoise_params(ptx_handle *h, const ptx_denoise_params *p, DnCall &c, const char *what);
+int denoise_check(ptx_handle *h, const DnCall &c, const char *what);
+int denoise_alloc(ptx_handle *h, const DnCall &c);
+// before the exchange: guide records of the own rows and, in temporal mode, dn_temporal on them;
+// after it: guide records of the halo rows, the variance pass and the iterations, each over the rows
+// a later stage still reads, and the step to the next call's state
+int denoise_front(ptx_handle *h, const DnCall &c, DnBand &b);
+int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b);
 // ptx_comm.cpp: a frame of a band handle that owns a communicator; a band frame without the
 // exchange (PTX_FLAG_HALO_SKIP, timing only); the communicator's teardown
 int render_band_nccl(ptx_handle *h);

@@ -38,21 +38,41 @@ hipError_t launch_mcpt(const Scene &sc, float4 *accum, uint32_t stack_depth, hip
 hipError_t launch_present(const float4 *tex, uint32_t W, uint32_t H, uint32_t cw, uint32_t ch, bool bgra,
                           uint32_t *out, hipStream_t s);
 
-// the denoiser (ptx_denoise.hip; whole-image handles): guide records (2 float4 per pixel) from the
-// G-buffer, the variance pass accum -> {r, g, b, v}, one a-trous iteration at `step` (a power of
-// two; `last`: the output's alpha is 1)
+// the denoiser (ptx_denoise.hip).  Its kernels address a row window: a W x rows image -- the whole
+// frame, or a band with the halo rows its neighbours sent (ptx_denoise_bands) -- filtered as if it
+// were the whole image; every buffer a launch is given starts at the window's row 0.
+struct DnWin {
+    uint32_t y0;      // the row of the frame that is row 0 of the window (of the buffers)
+    uint32_t rows;    // the rows the window (the buffers) holds: a tap outside [0, rows) is outside the image
+    uint32_t c0, c1;  // the rows this launch computes, [c0, c1)
+};
+// A filter input whose rows lie in two buffers: window rows [o0, o1) in `own` (its row 0 = window
+// row o0: a band's accumulation), the rows above and then the rows below them in `halo`.
+struct DnImage {
+    const float4 *own, *halo;
+    uint32_t o0, o1;
+};
+// guide records (2 float4 per pixel) of the band's own rows from its G-buffer (gbuf and guide start
+// at the band's first row), and of a window's halo rows from received texels (`top` rows above the
+// band, then `bottom` below; guide starts at the window's row 0); the variance pass
+// image -> {r, g, b, v}; one a-trous iteration at `step` (a power of two; `last`: the output's alpha is 1)
 hipError_t launch_denoise_guide(const Scene &sc, const uint4 *gbuf, float4 *guide, float sigma_plane, hipStream_t s);
-hipError_t launch_denoise_variance(uint32_t W, uint32_t H, const float4 *accum, const float4 *guide, float4 *out,
+hipError_t launch_denoise_guide_halo(const Scene &sc, const uint4 *texels, uint32_t top, uint32_t bottom, float4 *guide,
+                                     float sigma_plane, hipStream_t s);
+hipError_t launch_denoise_variance(uint32_t W, const DnWin &win, const DnImage &img, const float4 *guide, float4 *out,
                                    hipStream_t s);
-hipError_t launch_denoise_atrous(uint32_t W, uint32_t H, uint32_t step, const float4 *in, const float4 *guide, float4 *out,
-                                 float sigma_lum, bool last, hipStream_t s);
-// temporal mode: the history lookup and integration (mode 0 no history, 1 same pixel, 2 through
-// vp_prev; p*: the previous call's guide, history and moment records) -> history {C.rgb, n},
+hipError_t launch_denoise_atrous(uint32_t W, const DnWin &win, uint32_t step, const float4 *in, const float4 *guide,
+                                 float4 *out, float sigma_lum, bool last, hipStream_t s);
+// temporal mode: the history lookup and integration over rows [c0, c1) of the window, the band's own
+// rows, where frame and accum start (mode 0 no history, 1 same pixel, 2 through vp_prev; p*: the
+// previous call's guide, history and moment records, which start at row prev_y0 of the W x H frame
+// and hold prev_rows rows; *clip counts the pixels with a candidate past them) -> history {C.rgb, n},
 // moments {m1, m2}; the variance pass on that history, the moments' variance where n >= 4
-hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const float *vp_prev, float alpha_min, uint32_t mode,
-                                   const float4 *guide, const float4 *frame, const float4 *accum, const float4 *pguide,
-                                   const float4 *phist, const float2 *pmom, float4 *hist, float2 *mom, hipStream_t s);
-hipError_t launch_denoise_variance_moments(uint32_t W, uint32_t H, const float4 *hist, const float2 *mom,
+hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const DnWin &win, const float *vp_prev, float alpha_min,
+                                   uint32_t mode, uint32_t prev_y0, uint32_t prev_rows, const float4 *guide,
+                                   const float4 *frame, const float4 *accum, const float4 *pguide, const float4 *phist,
+                                   const float2 *pmom, float4 *hist, float2 *mom, unsigned long long *clip, hipStream_t s);
+hipError_t launch_denoise_variance_moments(uint32_t W, const DnWin &win, const float4 *hist, const float2 *mom,
                                            const float4 *guide, float4 *out, hipStream_t s);
 
 // closest-hit queries for a ray array (ptx_kernels.hip)

@@ -256,6 +256,41 @@ class Renderer:
         p.reserved[1] = int(np.float32(alpha_min).view(np.uint32))
         self._call("ptx_denoise", self._h, ctypes.byref(p))
 
+    @staticmethod
+    def denoise_bands(renderers, out: np.ndarray | None = None, iterations: int = 0, sigma_lum: float = 0.0,
+                      sigma_plane: float = 0.0, temporal: bool | int = False, alpha_min: float = 0.0) -> None:
+        """Denoise over the band renderers of this process (ptx_denoise_bands): every band filters its
+        rows and 2^(iterations + 1) halo rows brought from its neighbours on the device (their
+        communicators, or peer copies), which gives the whole image's result on its rows.  Parameters as
+        Denoise; `out` (rows of all bands, W, 4) f32 optional: the bands' denoised rows in order
+        (blocking).  read_denoised / read_denoise_history / denoise_clips work per band."""
+        lib = N.load()
+        arr = (ctypes.c_void_p * len(renderers))(*[r._h.value for r in renderers])
+        p = N.PtxDenoiseParams(iterations=int(iterations), sigma_lum=float(sigma_lum), sigma_plane=float(sigma_plane))
+        p.reserved[0] = int(temporal)
+        p.reserved[1] = int(np.float32(alpha_min).view(np.uint32))
+        if out is not None:
+            rows = sum(r.band_rows for r in renderers)
+            assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == rows * renderers[0].width * 4
+        rc = lib.ptx_denoise_bands(arr, len(renderers), ctypes.byref(p))
+        if rc != N.PTX_OK:
+            msgs = [lib.ptx_last_error(r._h) for r in renderers]
+            raise N.PtxError(f"ptx_denoise_bands failed ({rc}): "
+                             + "; ".join(m.decode(errors="replace") for m in msgs if m))
+        if out is not None:
+            flat, row = out.reshape(rows, renderers[0].width, 4), 0
+            for r in renderers:
+                flat[row:row + r.band_rows] = r.read_denoised()
+                row += r.band_rows
+
+    def denoise_clips(self) -> int:
+        """Pixels of this band's temporal denoise_bands calls (since the last reset_stats) with a history
+        candidate inside the image but outside the rows the band's state covered: not taken.  0 on every
+        band: the split is the whole image's bit for bit (PTX_COUNTER_DENOISE_CLIP)."""
+        c = np.zeros(8, dtype=np.uint64)
+        self._call("ptx_read_buffer", self._h, N.PTX_BUF_COUNTERS, c.ctypes.data, c.nbytes)
+        return int(c[N.PTX_COUNTER_DENOISE_CLIP])
+
     def read_frame_color(self) -> np.ndarray:
         """The radiance of the frame last rendered alone (band_h, W, 4) f32 {r, g, b, 1}
         (frame_color=True; unspecified at pixels without a primary hit)."""

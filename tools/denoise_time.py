@@ -5,6 +5,7 @@
     rocprofv3 --kernel-trace -d OUT -o run --output-format csv -- python tools/denoise_time.py --no-events
     python tools/denoise_time.py --trace OUT/.../run_kernel_trace.csv      # per kernel, from that trace
     python tools/denoise_time.py --temporal [--yaw-step DEG]   # the temporal mode (both forms above take it too)
+    python tools/denoise_time.py --bands 8 --width 3840 --height 2160 [--temporal]   # the frame split into row bands
 
 The whole call is timed with device events around it on the handle's stream (a torch stream set
 with ptx_set_stream): the median of --calls calls after --warmup.  The same calls on a
@@ -15,6 +16,13 @@ its share of the streaming bound).  One JSON line either way.
 --temporal times the temporal mode on a frame_color handle: before every call the camera yaws by
 --yaw-step degrees (0: a still camera, the same-pixel lookup) and a frame is rendered with the frame
 index restarted, as the engine does on a move; only the ptx_denoise call is inside the events.
+--bands N times ptx_denoise_bands on the frame as N equal row bands on this GPU (peer copies,
+PTX_FLAG_TIME_LAUNCHES handles): the sum of the bands' kernel times per call against the whole-image
+call's on the same build, with the rows each stage computes and the bytes a band receives.  For the
+kernel times every band runs on ONE stream: on their own streams the bands' kernels share the GPU, and
+an event pair then spans its neighbours' kernels too (that sum is reported as well, labelled).  The
+time from the call to its completion on the bands' own streams, against the whole-image call's, is
+taken with the host clock.
 """
 import argparse
 import csv
@@ -110,6 +118,108 @@ def measure(args):
     return out
 
 
+def stage_rows(rows, top, band_h, n):
+    """Rows per launch of a band with `top` halo rows above and rows - top - band_h below: guide,
+    variance, iteration 0..n-1 (ptx_api.cpp denoise_stage_rows)."""
+    R = 2 << n
+
+    def span(e):
+        return min(rows, top + band_h + e) - (top - min(top, e))
+
+    return [rows, span(R - 2)] + [span(R - (4 << k)) for k in range(n)]
+
+
+def measure_bands(args):
+    from pathtracerdemo_amd import _native as N
+    from pathtracerdemo_amd.renderer import Renderer
+    from pathtracerdemo_amd.scene.world import compile_scene
+    W, H, n = args.width, args.height, args.iterations
+    cs = compile_scene(args.scene)
+    cuts = [H * i // args.bands for i in range(args.bands + 1)]
+
+    def make(a=0, b=0):
+        r = Renderer(W, H, device=0, pipeline=args.pipeline, row_begin=a, row_end=b, frame_color=args.temporal,
+                     time_launches=True)
+        r.Initialize(cs)
+        return r
+
+    one, bands = make(), [make(a, b) for a, b in zip(cuts, cuts[1:])]
+
+    def frame(i=None):
+        for r in [one] + bands:
+            if i is not None and args.yaw_step:
+                r.GetCamera().set_yaw(args.yaw_step * (i + 1))
+                r.ResetFrameCount()
+            r.Update()
+        one.Render()
+        Renderer.render_bands(bands)
+        for r in [one] + bands:
+            r.synchronize()
+
+    def spent(rs):
+        return sum(r.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE] for r in rs)
+
+    import time
+
+    import torch
+
+    def timed_calls(first):
+        whole, split, wall_whole, wall_split = [], [], [], []
+        for i in range(first, first + args.warmup + args.calls):
+            if args.temporal:
+                frame(i)
+            w0, s0 = spent([one]), spent(bands)
+            t0 = time.perf_counter()
+            one.Denoise(iterations=n, temporal=args.temporal)
+            one.synchronize()
+            t1 = time.perf_counter()
+            Renderer.denoise_bands(bands, iterations=n, temporal=args.temporal)
+            for b in bands:
+                b.synchronize()
+            t2 = time.perf_counter()
+            if i >= first + args.warmup:
+                whole.append(spent([one]) - w0)
+                split.append(spent(bands) - s0)
+                wall_whole.append((t1 - t0) * 1e3)
+                wall_split.append((t2 - t1) * 1e3)
+        return whole, split, wall_whole, wall_split
+
+    def mmm(v):
+        return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+
+    for _ in range(args.frames):
+        frame()
+    # the bands' own streams: what a host sees, and event pairs that span concurrent kernels
+    _, overlapped, wall_whole, wall_split = timed_calls(0)
+    # one stream for every band: each launch's events time that kernel alone
+    shared = torch.cuda.Stream()
+    for b in bands:
+        b.set_stream(shared.cuda_stream)
+    whole, split, _, _ = timed_calls(args.warmup + args.calls)
+    same = all((b.read_denoised().view("uint32") == one.read_denoised()[a:z].view("uint32")).all()
+               for b, a, z in zip(bands, cuts, cuts[1:]))
+    R = 2 << n
+    per_px = 16 + 16 + (8 if args.temporal else 0)
+    halo = [(min(R, a), min(R, H - z)) for a, z in zip(cuts, cuts[1:])]
+    rows = [stage_rows(t + (z - a) + b, t, z - a, n) for (t, b), a, z in zip(halo, cuts, cuts[1:])]
+    out = {"what": "ptx_denoise_bands", "temporal": args.temporal, "yaw_step": args.yaw_step, "width": W, "height": H,
+           "scene": args.scene, "pipeline": args.pipeline, "iterations": n, "bands": args.bands, "calls": args.calls,
+           "warmup": args.warmup, "equals_whole_image": bool(same),
+           "whole_image_kernel_ms": mmm(whole), "bands_kernel_ms_sum": mmm(split),
+           "ratio": round(statistics.median(split) / statistics.median(whole), 3),
+           "bands_kernel_ms_sum_on_own_streams_overlapped": mmm(overlapped),
+           "host_ms_call_to_completion": {"whole_image": mmm(wall_whole), "bands_own_streams": mmm(wall_split)},
+           "rows_per_stage": rows,
+           "rows_ratio_expected": round(sum(sum(r) for r in rows) / ((2 + n) * H), 3),
+           "halo_bytes_received_per_band": [[t * W * per_px, b * W * per_px] for t, b in halo],
+           "denoise_clips": [b.denoise_clips() for b in bands]}
+    for b in bands:
+        b.set_stream(None)
+    for r in [one] + bands:
+        r.close()
+    return out
+
+
 def from_trace(args):
     """Median duration of each kernel of a call (guide, [temporal,] variance, iteration 0..n-1) over the traced
     calls of the last handle (the TIME_LAUNCHES one), warm-up calls dropped."""
@@ -153,10 +263,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--temporal", action="store_true", help="the temporal mode on a frame_color handle")
     ap.add_argument("--yaw-step", type=float, default=0.5, help="--temporal: degrees the camera yaws before every call (0: still)")
+    ap.add_argument("--bands", type=int, default=0, help="time ptx_denoise_bands on the frame as this many equal row bands")
     ap.add_argument("--no-events", action="store_true", help="only the TIME_LAUNCHES handle (the run a profiler traces)")
     ap.add_argument("--trace", help="a rocprofv3 run_kernel_trace.csv of this script: print per-kernel medians")
     args = ap.parse_args()
-    print(json.dumps(from_trace(args) if args.trace else measure(args)))
+    print(json.dumps(from_trace(args) if args.trace else measure_bands(args) if args.bands else measure(args)))
 
 
 if __name__ == "__main__":
