@@ -327,8 +327,41 @@ int ptx_denoise(ptx_handle *h, const ptx_denoise_params *p /* NULL = defaults */
  * ptx_reset_accumulation drop a band's state as ever; it then starts without history, and its
  * neighbours see n = 1 (n = 0 at misses) in the rows it sends. */
 int ptx_denoise_bands(ptx_handle *const *handles, int n, const ptx_denoise_params *p /* NULL = defaults */);
+/* Guided upsampling (Upsampling): the denoised image of `lo`, a whole-image handle of
+ * w x h after at least one ptx_denoise (spatial or temporal), written at the size W x H = s*w x s*h
+ * (one integer s in 2, 3, 4) of the whole-image handle `hi` into hi's PTX_BUF_DENOISED, alpha 1,
+ * steered by hi's primary hits.  Primary rays are unjittered pixel centres, so lo's pixel (i, j)
+ * looks through hi's image at (s*i + (s-1)/2, s*j + (s-1)/2).  The call traces nothing: it turns the
+ * G-buffer of hi's current frame context, as it stands (a host-written one is honoured), into guide
+ * records with sigma_plane and reads lo's output and the guide records of lo's last ptx_denoise.
+ * hi pixel (x, y) sits at fx = (x + 0.5) / s - 0.5, x0 = floor(fx), ax = fx - x0 (y likewise) of lo:
+ *   stage 1  the pixels (x0 + i, y0 + j), i, j in 0, 1 (j outer), inside lo's image with hi's key
+ *            (instance and sub-mesh, or both without a primary hit), weighted by the bilinear weight
+ *            times the denoiser's guide weight (1 at a pixel without a hit): sum(wt * c) / sum(wt)
+ *            when sum(wt) > 0;
+ *   stage 2  else the plain average of the pixels (x0 - 1 + i, y0 - 1 + j), i, j in 0..3, inside the
+ *            image with that key, when there is one;
+ *   stage 3  else lo's pixel (x / s, y / s).
+ * Both handles: same device, pipelines with a G-buffer, uniform words 4..22 equal bit for bit, and
+ * equal triangles, bvh_nodes and instances (ptx_stats) -- the cheap guard for "the same scene", the
+ * rest of which is the caller's contract; hi has a scene and at least one G-buffer pass or frame
+ * since its upload.  Anything else (a null handle, hi == lo, a band handle, TEST_MCPT, no denoised
+ * image on lo, sizes that are no such multiple, a sigma_plane that is negative or not finite, a
+ * non-zero reserved word) is PTX_E_INVALID with the reason in hi's ptx_last_error, before any GPU work.
+ *   Asynchronous on hi's stream: it first waits for the tail of the stream lo's last denoise ran on,
+ * and lo's next GPU work (a frame, denoise, reset, upload or destroy, on whichever of lo's streams
+ * it runs) waits on the GPU until hi's kernels have read lo's buffers.  lo's accumulation, G-buffer, reservoirs, denoiser state and output
+ * and hi's G-buffer keep their bits.  hi's buffers (32 B guide record + 16 B output per pixel) are
+ * allocated by the first call and counted in device_bytes; PTX_BUF_DENOISED and
+ * ptx_present_source(hi, PTX_BUF_DENOISED) then work on hi as after a first ptx_denoise.
+ * Launches (hi's PTX_STAT_DENOISE): 2 (guide records, dn_upsample). */
+typedef struct ptx_upsample_params {
+    float sigma_plane;     /* plane-distance edge stop of the full-size guides; 0 = default 0.02 */
+    uint32_t reserved[7];  /* zero */
+} ptx_upsample_params;     /* 32 bytes */
+int ptx_upsample(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_params *p /* NULL = defaults */);
 /* What ptx_present and ptx_present_async read: PTX_BUF_ACCUM (the default) or PTX_BUF_DENOISED
- * (fails before the first ptx_denoise). */
+ * (fails before the first ptx_denoise or ptx_upsample). */
 int ptx_present_source(ptx_handle *h, int which);
 /* What this libptx.so is, as one JSON object in `out` (NUL-terminated, truncated to `bytes`):
  * {"abi": 5, "build": "product" | "ab" (every PTX_AB switch live: the measurement build) | "wgt"

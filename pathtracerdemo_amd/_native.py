@@ -50,7 +50,8 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_trace", "ptx_trace_device", "ptx_run_passes", "ptx_halo_rows", "ptx_halo_pack",
             "ptx_halo_unpack", "ptx_comm_unique_id", "ptx_comm_init", "ptx_comm_init_all", "ptx_render_bands",
             "ptx_row_census", "ptx_comm_info", "ptx_present", "ptx_present_async", "ptx_present_poll",
-            "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands"]
+            "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands",
+            "ptx_upsample"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -70,6 +71,10 @@ class PtxStats(ctypes.Structure):
 class PtxDenoiseParams(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_uint32), ("sigma_lum", ctypes.c_float), ("sigma_plane", ctypes.c_float),
                 ("reserved", ctypes.c_uint32 * 5)]
+
+
+class PtxUpsampleParams(ctypes.Structure):
+    _fields_ = [("sigma_plane", ctypes.c_float), ("reserved", ctypes.c_uint32 * 7)]
 
 
 class PtxError(RuntimeError):
@@ -129,6 +134,7 @@ def load(path: str = LIB_PATH):
     lib.ptx_build_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
     lib.ptx_denoise.argtypes = [H, ctypes.POINTER(PtxDenoiseParams)]
     lib.ptx_denoise_bands.argtypes = [ctypes.POINTER(H), ctypes.c_int, ctypes.POINTER(PtxDenoiseParams)]
+    lib.ptx_upsample.argtypes = [H, H, ctypes.POINTER(PtxUpsampleParams)]
     lib.ptx_present_source.argtypes = [H, ctypes.c_int]
     lib.ptx_run_passes.argtypes = [H, P, ctypes.c_int]
     lib.ptx_halo_rows.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),

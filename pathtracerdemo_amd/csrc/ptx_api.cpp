@@ -1610,6 +1610,8 @@ int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b) {
         });
     }
     if (e != hipSuccess) return fail(h, PTX_E_HIP, "denoiser launch: %s", hipGetErrorString(e));
+    h->dn_guide_swapped = c.temporal != 0u;  // (ptx_upsample reads this call's guide records)
+    h->dn_stream = st;
     if (c.temporal) {  // this call is the next one's previous call: its guides (no copy), history set and camera
         std::swap(h->d_dn_guide, h->d_dn_guide_prev);
         h->dn_set = b.wr;
@@ -1759,6 +1761,7 @@ int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const
     if (int rc = upload(h, h->d_geometry, geometry, n_geometry * 4u)) return rc;
     h->layout_valid = false;
     h->scene_loaded = true;
+    h->drawn = false;
     h->hist_valid = false;
     h->dn_hist_valid = false;  // (the denoiser's history shows the old scene)
     h->cur().init_state_valid = false;
@@ -1798,7 +1801,10 @@ int ptx_run_pass(ptx_handle *h, int pass) {
     if (!h) return PTX_E_INVALID;
     HIP_CHECK(h, hipSetDevice(h->device));  // handles of one process may sit on several GPUs
     const int rc = timed_launch(h, pass);
-    if (rc == PTX_OK) h->rendered = true;
+    if (rc == PTX_OK) {
+        h->rendered = true;
+        if (pass == PTX_PASS_GBUFFER) h->drawn = true;  // (ptx_upsample asks: a G-buffer of this scene)
+    }
     return rc;
 }
 
@@ -1816,11 +1822,17 @@ int ptx_run_passes(ptx_handle *h, const int *passes, int n) {
         if (p == PTX_PASS_MCPT && h->cfg.pipeline == PTX_PIPELINE_RESTIR_GI)
             return fail(h, PTX_E_INVALID, "the GI pipeline has no MCPT pass");
     }
+    bool gb = false, reuse = false;
+    for (int i = 0; i < n; ++i) {
+        gb |= passes[i] == PTX_PASS_GBUFFER;
+        reuse |= passes[i] == PTX_PASS_TEMPORAL || passes[i] == PTX_PASS_SPATIAL;
+    }
     const uint32_t fl = h->cfg.flags;
     if (fl & (PTX_FLAG_SIMPLE_KERNELS | PTX_FLAG_COUNT_WORK)) {
         for (int i = 0; i < n; ++i)
             if (int rc = timed_launch(h, passes[i])) return rc;
         h->rendered = true;
+        h->drawn |= gb;
         return PTX_OK;
     }
     if (!h->scene_loaded || !h->frame_set) return fail(h, PTX_E_INVALID, "scene and frame must be set before rendering");
@@ -1828,15 +1840,11 @@ int ptx_run_passes(ptx_handle *h, const int *passes, int n) {
         if (int rc = build_layout(h)) return rc;
     }
     Scene sc = make_scene(h);
-    bool gb = false, reuse = false;
-    for (int i = 0; i < n; ++i) {
-        gb |= passes[i] == PTX_PASS_GBUFFER;
-        reuse |= passes[i] == PTX_PASS_TEMPORAL || passes[i] == PTX_PASS_SPATIAL;
-    }
     if (gb && !tables_fit_lds(sc)) {  // the segment-mapped G-buffer needs LDS tables
         for (int i = 0; i < n; ++i)
             if (int rc = timed_launch(h, passes[i])) return rc;
         h->rendered = true;
+        h->drawn |= gb;
         return PTX_OK;
     }
     WaveBufs w{};
@@ -1855,6 +1863,7 @@ int ptx_run_passes(ptx_handle *h, const int *passes, int n) {
     for (int i = 0; i < n; ++i)
         if (passes[i] == PTX_PASS_SPATIAL) mark_history(h);
     h->rendered = true;
+    h->drawn |= gb;
     return PTX_OK;
 }
 
@@ -1936,7 +1945,7 @@ int ptx_render(ptx_handle *h, float *rgba_out) {
         if (int rc = timed_launch(h, PTX_PASS_MCPT)) return rc;
     }
     h->frames++;
-    h->rendered = true;
+    h->rendered = h->drawn = true;
     if (rgba_out)
         if (int rc = read_to_host(h, rgba_out, h->d_accum.p, h->d_accum.bytes)) return rc;
     return PTX_OK;
@@ -2153,6 +2162,70 @@ int ptx_denoise(ptx_handle *h, const ptx_denoise_params *p) {
     return denoise_back(h, c, b);
 }
 
+int ptx_upsample(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_params *p) {
+    if (!hi || !lo) return PTX_E_INVALID;
+    const char *what = "ptx_upsample";
+    // ---- refusals, all before any GPU work
+    if (hi == lo) return fail(hi, PTX_E_INVALID, "%s: one handle on both sides", what);
+    float sigma_plane = 0.02f;
+    if (p) {
+        for (uint32_t r : p->reserved)
+            if (r) return fail(hi, PTX_E_INVALID, "%s: a reserved word is not zero", what);
+        if (!std::isfinite(p->sigma_plane) || p->sigma_plane < 0.0f)
+            return fail(hi, PTX_E_INVALID, "%s: sigma_plane %g (finite, >= 0)", what, p->sigma_plane);
+        if (p->sigma_plane != 0.0f) sigma_plane = p->sigma_plane;
+    }
+    for (ptx_handle *h : {hi, lo}) {
+        const char *side = h == hi ? "full-size" : "small";
+        if (h->cfg.row_begin != 0 || h->band_h != h->cfg.height)
+            return fail(hi, PTX_E_INVALID, "%s: the %s handle is a band (rows %u..%u)", what, side, h->cfg.row_begin, h->cfg.row_end);
+        if (h->cfg.pipeline == PTX_PIPELINE_MCPT)
+            return fail(hi, PTX_E_INVALID, "%s: the %s handle runs the TEST_MCPT pipeline, which has no G-buffer", what, side);
+    }
+    if (hi->device != lo->device) return fail(hi, PTX_E_INVALID, "%s: the handles are on devices %d and %d", what, hi->device, lo->device);
+    const float4 *lguide = (const float4 *)(lo->dn_guide_swapped ? lo->d_dn_guide_prev.p : lo->d_dn_guide.p);
+    if (!lo->d_denoised.p || !lguide) return fail(hi, PTX_E_INVALID, "%s: the small handle has no denoised image (ptx_denoise first)", what);
+    if (!hi->scene_loaded || !hi->frame_set || !hi->layout_valid || !hi->drawn)
+        return fail(hi, PTX_E_INVALID, "%s: the full-size handle has no G-buffer of its scene yet (a G-buffer pass or a frame first)", what);
+    const uint32_t W = hi->cfg.width, H = hi->cfg.height, w = lo->cfg.width, hh = lo->cfg.height, s = W / w;
+    if (s < 2u || s > 4u || W != s * w || H != s * hh)
+        return fail(hi, PTX_E_INVALID, "%s: %ux%u is not 2, 3 or 4 times %ux%u", what, W, H, w, hh);
+    if (std::memcmp(hi->uniform + 4, lo->uniform + 4, 19 * sizeof(uint32_t)) != 0)
+        return fail(hi, PTX_E_INVALID, "%s: the handles' cameras differ (uniform words 4..22)", what);
+    if (hi->n_tris != lo->n_tris || hi->n_nodes != lo->n_nodes || hi->n_inst != lo->n_inst)
+        return fail(hi, PTX_E_INVALID, "%s: the handles' scenes differ (%u / %u triangles, %u / %u BVH nodes, %u / %u instances)", what,
+                    hi->n_tris, lo->n_tris, hi->n_nodes, lo->n_nodes, hi->n_inst, lo->n_inst);
+    // ---- buffers (first call), then: behind the small handle's denoise, the two launches, and the
+    // small handle's streams behind them
+    HIP_CHECK(hi, hipSetDevice(hi->device));
+    const size_t px = (size_t)W * H;
+    if (int rc = alloc_buf(hi, hi->d_dn_guide, px * 32u)) return rc;
+    if (int rc = alloc_buf(hi, hi->d_denoised, px * 16u)) return rc;
+    for (hipEvent_t *ev : {&lo->ev_up_src, &hi->ev_up_done})
+        if (!*ev) HIP_CHECK(hi, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    const hipStream_t st = hi->cur().stream;
+    HIP_CHECK(hi, hipEventRecord(lo->ev_up_src, lo->dn_stream));
+    HIP_CHECK(hi, hipStreamWaitEvent(st, lo->ev_up_src, 0));
+    const Scene sc = make_scene(hi);
+    float4 *guide = (float4 *)hi->d_dn_guide.p;
+    hipError_t e = denoise_timed(hi, st, hipSuccess, [&] { return launch_denoise_guide(sc, gbuf_band(hi), guide, sigma_plane, st); });
+    e = denoise_timed(hi, st, e, [&] {
+        return launch_denoise_upsample(s, W, H, guide, lguide, (const float4 *)lo->d_denoised.p, (float4 *)hi->d_denoised.p, st);
+    });
+    // (recorded whatever was launched: the small handle never waits on a stale event)
+    HIP_CHECK(hi, hipEventRecord(hi->ev_up_done, st));
+    // lo's next work runs on its current context's stream (a denoise, reset or upload) or on the next
+    // context's (a frame), and frames enqueued since the denoise have moved cur() off dn_stream: every
+    // stream lo's contexts run on waits
+    HIP_CHECK(hi, hipStreamWaitEvent(lo->dn_stream, hi->ev_up_done, 0));
+    for (auto &c : lo->ctx)
+        if (c.stream && c.stream != lo->dn_stream) HIP_CHECK(hi, hipStreamWaitEvent(c.stream, hi->ev_up_done, 0));
+    if (e != hipSuccess) return fail(hi, PTX_E_HIP, "%s launch: %s", what, hipGetErrorString(e));
+    hi->dn_guide_swapped = false;  // (this handle's output and the guide records it was written under)
+    hi->dn_stream = st;
+    return PTX_OK;
+}
+
 int ptx_present_source(ptx_handle *h, int which) {
     if (!h) return PTX_E_INVALID;
     if (which != PTX_BUF_ACCUM && which != PTX_BUF_DENOISED)
@@ -2200,7 +2273,12 @@ int ptx_trace(ptx_handle *h, const float *rays, float *hits, size_t n, int eps_m
 int ptx_set_stream(ptx_handle *h, void *hip_stream) {
     if (!h) return PTX_E_INVALID;
     if (int rc = first_frame_ctx(h)) return rc;
+    // a handle ptx_upsample has read: the waits for those reads sit on the streams it ran on so far,
+    // and its last denoise on dn_stream -- all of it finishes before work moves to another stream
+    if (h->ev_up_src || h->d_denoised.p)
+        if (int rc = quiesce(h)) return rc;
     h->ctx[0].stream = hip_stream ? (hipStream_t)hip_stream : h->ctx[0].own;
+    h->dn_stream = h->ctx[0].stream;
     gbuf_key_drop_all(h);  // (the orders of two streams are not related)
     return PTX_OK;
 }
@@ -2244,6 +2322,8 @@ int ptx_destroy(ptx_handle *h) {
     if (h->ev_prev) (void)hipEventDestroy(h->ev_prev);
     if (h->ev_dn_ready) (void)hipEventDestroy(h->ev_dn_ready);
     if (h->ev_dn_copied) (void)hipEventDestroy(h->ev_dn_copied);
+    if (h->ev_up_src) (void)hipEventDestroy(h->ev_up_src);
+    if (h->ev_up_done) (void)hipEventDestroy(h->ev_up_done);
     delete h;
     return PTX_OK;
 }

@@ -388,7 +388,7 @@ int band_back(ptx_handle *h, const Scene &sc, const WaveBufs &w, TimedLaunch *fr
     frame_t->pass = PTX_STAT_FRAME;
     frame_t->pending = true;
     h->frames++;
-    h->rendered = true;  // (ptx_denoise_bands asks)
+    h->rendered = h->drawn = true;  // (ptx_denoise_bands asks)
     return PTX_OK;
 }
 

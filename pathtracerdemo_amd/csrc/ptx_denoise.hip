@@ -10,6 +10,8 @@
 //                history, the integrated moments' variance where n >= 4
 //   dn_atrous    one iteration at step 2^i on the working image (ping-pong); steps 1, 2, 4 stage
 //                the 16x16 tile and its apron in LDS, steps >= 8 gather their taps directly
+//   dn_upsample  (ptx_upsample) a denoised image of 1/S the size, written at full size under the
+//                full-size guide records; the tile's footprint in the small image staged in LDS
 // Every kernel but dn_guide addresses a row window (DnWin): a W x rows image that is the whole
 // frame, or a band with the halo rows ptx_denoise_bands brought from its neighbours, filtered as if
 // it were the whole image; a launch computes rows [c0, c1) of it.
@@ -396,6 +398,87 @@ __global__ __launch_bounds__(kBlock) void dn_atrous_gather(uint32_t W, const DnW
     out[pix] = o;
 }
 
+// ---------------------------------------------------------------- guided upsampling (ptx_upsample)
+// A w x h image `lc` with the guide records `lg` of its denoise, written at S times the size under
+// the full-size guide records `hg` (Upsampling; tests/upsample_ref.py).  Pixel
+// (x, y) sits at f = (x + 0.5) / S - 0.5 of the small image, x0 = floor(f): stage 1 weighs the four
+// pixels (x0 + i, y0 + j) with the pixel's key bilinearly and by dn_gamma, stage 2 (no weight
+// there) averages the 16 of (x0 - 1 .. x0 + 2)^2 with its key, stage 3 (none either) takes pixel
+// (x / S, y / S).  A tile's x0 spans at most 16 / S + 1 columns, so every candidate of its pixels
+// lies in the kUpN x kUpN window staged from (x0 - 1, y0 - 1) of the tile's first pixel.
+constexpr int kUpN = 12;
+constexpr uint32_t kUpOutside = 0xFFFFFFFEu;  // staged key of an entry outside the image: no pixel's key (bit 31), not a miss
+template <int S>
+__global__ __launch_bounds__(kBlock) void dn_upsample(uint32_t W, uint32_t H, uint32_t w, uint32_t h,
+                                                      const float4 *__restrict__ hg, const float4 *__restrict__ lg,
+                                                      const float4 *__restrict__ lc, float4 *__restrict__ out) {
+    static_assert(S >= 2 && S <= 4 && (kDnTile + S - 2) / S + 4 <= kUpN, "the window holds a tile's candidates");
+    __shared__ float4 g0[kUpN * kUpN], g1[kUpN * kUpN], cv[kUpN * kUpN];
+    const int tx = (int)(threadIdx.x & 15u), ty = (int)(threadIdx.x >> 4);
+    const uint32_t bx = blockIdx.x * kDnTile, by = blockIdx.y * kDnTile;
+    const int ox = (int)__builtin_floorf(((float)bx + 0.5f) / (float)S - 0.5f) - 1;
+    const int oy = (int)__builtin_floorf(((float)by + 0.5f) / (float)S - 0.5f) - 1;
+    if (threadIdx.x < (uint32_t)(kUpN * kUpN)) {
+        const int e = (int)threadIdx.x, gx = ox + e % kUpN, gy = oy + e / kUpN;
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, asf(kUpOutside)), b = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = b;
+        if (gx >= 0 && gy >= 0 && gx < (int)w && gy < (int)h) {
+            const size_t q = (size_t)gy * w + (size_t)gx;
+            a = lg[2u * q];
+            b = lg[2u * q + 1u];
+            c = lc[q];
+        }
+        g0[e] = a;
+        g1[e] = b;
+        cv[e] = c;
+    }
+    __syncthreads();
+    const uint32_t x = bx + (uint32_t)tx, y = by + (uint32_t)ty;
+    if (x >= W || y >= H) return;
+    const size_t pix = (size_t)y * W + x;
+    const float4 a = hg[2u * pix], b = hg[2u * pix + 1u];
+    const uint32_t key = asu(a.w);
+    const f3 Pp = rgb(a), Np = rgb(b);
+    const float fx = ((float)x + 0.5f) / (float)S - 0.5f, fy = ((float)y + 0.5f) / (float)S - 0.5f;
+    const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
+    const float ax = fx - x0, ay = fy - y0;
+    // (x0, y0) in the window: 1 .. kUpN - 3 by the bound above (clamped: no LDS index depends on it holding)
+    const int lx = min(max((int)x0 - ox, 1), kUpN - 3), ly = min(max((int)y0 - oy, 1), kUpN - 3);
+    f3 o;
+    float sw = 0.0f;
+    f3 sc = mk(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e = (ly + j) * kUpN + (lx + i);
+            const float4 qa = g0[e];
+            if (asu(qa.w) != key) continue;
+            const float bw = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+            const float gm = key == kDnMiss ? 1.0f : dn_gamma(Pp, Np, b.w, rgb(qa), rgb(g1[e]));
+            const float wt = bw * gm;
+            sw += wt;
+            sc = sc + rgb(cv[e]) * wt;
+        }
+    if (sw > 0.0f) {
+        o = sc / sw;
+    } else {
+        uint32_t n = 0u;
+        sc = mk(0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int j = -1; j < 3; ++j)
+#pragma unroll
+            for (int i = -1; i < 3; ++i) {
+                const int e = (ly + j) * kUpN + (lx + i);
+                if (asu(g0[e].w) != key) continue;
+                n += 1u;
+                sc = sc + rgb(cv[e]);
+            }
+        if (n > 0u) o = sc / (float)n;
+        else o = rgb(cv[min(max((int)(y / (uint32_t)S) - oy, 0), kUpN - 1) * kUpN + min(max((int)(x / (uint32_t)S) - ox, 0), kUpN - 1)]);
+    }
+    out[pix] = make_float4(o.x, o.y, o.z, 1.0f);
+}
+
 // ---------------------------------------------------------------- launches
 static dim3 dn_grid(uint32_t W, const DnWin &win) {
     return dim3((W + kDnTile - 1) / kDnTile, (win.c1 - win.c0 + kDnTile - 1) / kDnTile);
@@ -446,6 +529,17 @@ hipError_t launch_denoise_atrous(uint32_t W, const DnWin &win, uint32_t step, co
     else if (step == 2u) hipLaunchKernelGGL(dn_atrous_tiled<2>, g, bl, 0, s, W, win, in, guide, out, sigma_lum, l);
     else if (step == 4u) hipLaunchKernelGGL(dn_atrous_tiled<4>, g, bl, 0, s, W, win, in, guide, out, sigma_lum, l);
     else hipLaunchKernelGGL(dn_atrous_gather, g, bl, 0, s, W, win, (int)step, in, guide, out, sigma_lum, l);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_upsample(uint32_t s, uint32_t W, uint32_t H, const float4 *guide_hi, const float4 *guide_lo,
+                                   const float4 *color_lo, float4 *out, hipStream_t st) {
+    const dim3 g((W + kDnTile - 1) / kDnTile, (H + kDnTile - 1) / kDnTile), bl(kBlock);
+    const uint32_t w = W / s, h = H / s;
+    if (s == 2u) hipLaunchKernelGGL(dn_upsample<2>, g, bl, 0, st, W, H, w, h, guide_hi, guide_lo, color_lo, out);
+    else if (s == 3u) hipLaunchKernelGGL(dn_upsample<3>, g, bl, 0, st, W, H, w, h, guide_hi, guide_lo, color_lo, out);
+    else if (s == 4u) hipLaunchKernelGGL(dn_upsample<4>, g, bl, 0, st, W, H, w, h, guide_hi, guide_lo, color_lo, out);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

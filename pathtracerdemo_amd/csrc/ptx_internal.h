@@ -190,6 +190,14 @@ struct ptx_handle {
     // peer-copy exchange: this band's rows are ready to be copied (the frame; in temporal mode its
     // dn_temporal) / this band has copied its neighbours' rows
     hipEvent_t ev_dn_ready = nullptr, ev_dn_copied = nullptr;
+    // ptx_upsample reads what the last ptx_denoise (or ptx_upsample) of the small handle left: its
+    // output and its guide records, which a temporal call has swapped into d_dn_guide_prev
+    // (dn_guide_swapped), behind everything on the stream that call ran on (dn_stream: ev_up_src is
+    // recorded at its tail); ev_up_done follows the full-size handle's kernels, and the small handle's
+    // stream waits for it.  drawn: a frame or pass has run since the scene was uploaded
+    bool dn_guide_swapped = false, drawn = false;
+    hipStream_t dn_stream = nullptr;
+    hipEvent_t ev_up_src = nullptr, ev_up_done = nullptr;
     // the rows [begin, end) of the ranks above and below, as ptx_comm_init's neighbour check received them
     uint32_t nb_rows[2][2] = {{0, 0}, {0, 0}};
     int present_src = PTX_BUF_ACCUM;

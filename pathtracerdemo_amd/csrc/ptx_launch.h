@@ -74,6 +74,10 @@ hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const DnWin &win, con
                                    const float2 *pmom, float4 *hist, float2 *mom, unsigned long long *clip, hipStream_t s);
 hipError_t launch_denoise_variance_moments(uint32_t W, const DnWin &win, const float4 *hist, const float2 *mom,
                                            const float4 *guide, float4 *out, hipStream_t s);
+// ptx_upsample: the (W / s) x (H / s) image `color_lo` with its guide records, written at W x H under
+// `guide_hi` (s: 2, 3 or 4)
+hipError_t launch_denoise_upsample(uint32_t s, uint32_t W, uint32_t H, const float4 *guide_hi, const float4 *guide_lo,
+                                   const float4 *color_lo, float4 *out, hipStream_t st);
 
 // closest-hit queries for a ray array (ptx_kernels.hip)
 hipError_t launch_trace_rays(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,

@@ -215,6 +215,22 @@ class NativeRenderer {
    */
   Denoise(opts) {
     addon.denoise(this.Handle, opts || {});
+    this.paintDenoised();
+  }
+
+  /**
+   * ptx_upsample (include/ptx.h): the denoised image of `lo` -- a NativeRenderer of 1/2, 1/3 or 1/4
+   * this one's size with the same scene and camera, after its Denoise() -- written at this
+   * renderer's size under this renderer's G-buffer as it stands (a RunPass of the G-buffer pass or
+   * a frame first); {sigmaPlane} optional.  With the source 'denoised' the canvas is painted from
+   * the result, as after Denoise().
+   */
+  Upsample(lo, opts) {
+    addon.upsample(this.Handle, lo.Handle, opts || {});
+    this.paintDenoised();
+  }
+
+  paintDenoised() {
     if (this.PresentSource !== 'denoised') return;
     if (!this.DenoisedSourceSet) {
       addon.presentSource(this.Handle, BUF.DENOISED);

@@ -765,6 +765,34 @@ static napi_value js_denoise(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* upsample(hiHandle, loHandle, {sigmaPlane}): ptx_upsample -- loHandle's denoised image written at
+ * hiHandle's size under hiHandle's G-buffer (include/ptx.h; sigmaPlane optional, 0 = the default) */
+static napi_value js_upsample(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    Handle *L = argc >= 2 ? get_handle(env, argv[1]) : NULL;
+    if (!L) return NULL;
+    ptx_upsample_params p;
+    memset(&p, 0, sizeof p);
+    napi_valuetype t = napi_undefined;
+    if (argc >= 3) napi_typeof(env, argv[2], &t);
+    if (t == napi_object) {
+        if (get_f32_prop(env, argv[2], "sigmaPlane", &p.sigma_plane)) {
+            napi_throw_type_error(env, NULL, "upsample(hiHandle, loHandle, {sigmaPlane})");
+            return NULL;
+        }
+    } else if (t != napi_undefined && t != napi_null) {
+        napi_throw_type_error(env, NULL, "upsample(hiHandle, loHandle, options): options must be an object");
+        return NULL;
+    }
+    int rc = ptx_upsample(H->h, L->h, &p);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_upsample");
+    return NULL;
+}
+
 /* presentSource(handle, which): what present / presentAsync show, PTX_BUF_ACCUM (2) or PTX_BUF_DENOISED (6) */
 static napi_value js_present_source(napi_env env, napi_callback_info info) {
     size_t argc = 2;
@@ -817,11 +845,12 @@ static napi_value init(napi_env env, napi_value exports) {
             napi_set_named_property(env, exports, fns[i].name, f) != napi_ok)
             return NULL;
     }
-    /* The denoiser's two calls are defined non-enumerable: Object.keys(addon) is the list of the
+    /* The denoiser's calls are defined non-enumerable: Object.keys(addon) is the list of the
      * ABI-5 exports that tests/test_node_host.py pins, and these came after it. */
     const napi_property_descriptor later[] = {
         {"denoise", NULL, js_denoise, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"presentSource", NULL, js_present_source, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"upsample", NULL, js_upsample, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
     };
     if (napi_define_properties(env, exports, sizeof later / sizeof later[0], later) != napi_ok) return NULL;
     return exports;

@@ -256,6 +256,14 @@ class Renderer:
         p.reserved[1] = int(np.float32(alpha_min).view(np.uint32))
         self._call("ptx_denoise", self._h, ctypes.byref(p))
 
+    def Upsample(self, lo: "Renderer", sigma_plane: float = 0.0) -> None:
+        """Write the denoised image of `lo` -- a renderer of 1/2, 1/3 or 1/4 this one's size with the same
+        scene and camera, after its Denoise() -- at this renderer's size, steered by this renderer's
+        G-buffer as it stands (ptx_upsample; run_pass(PTX_PASS_GBUFFER) or a frame first; sigma_plane
+        0 = 0.02).  read_denoised() or Present with source "denoised" show the result."""
+        p = N.PtxUpsampleParams(sigma_plane=float(sigma_plane))
+        self._call("ptx_upsample", self._h, lo._h, ctypes.byref(p))
+
     @staticmethod
     def denoise_bands(renderers, out: np.ndarray | None = None, iterations: int = 0, sigma_lum: float = 0.0,
                       sigma_plane: float = 0.0, temporal: bool | int = False, alpha_min: float = 0.0) -> None:

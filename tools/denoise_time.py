@@ -6,6 +6,8 @@
     python tools/denoise_time.py --trace OUT/.../run_kernel_trace.csv      # per kernel, from that trace
     python tools/denoise_time.py --temporal [--yaw-step DEG]   # the temporal mode (both forms above take it too)
     python tools/denoise_time.py --bands 8 --width 3840 --height 2160 [--temporal]   # the frame split into row bands
+    python tools/denoise_time.py --upsample 2           # ptx_upsample, 960x540 -> 1920x1080 (--no-events / --trace take it too)
+    python tools/denoise_time.py --displayed-frame [--upsample 2]   # ms per displayed frame under a yawing camera
 
 The whole call is timed with device events around it on the handle's stream (a torch stream set
 with ptx_set_stream): the median of --calls calls after --warmup.  The same calls on a
@@ -23,6 +25,14 @@ kernel times every band runs on ONE stream: on their own streams the bands' kern
 an event pair then spans its neighbours' kernels too (that sum is reported as well, labelled).  The
 time from the call to its completion on the bands' own streams, against the whole-image call's, is
 taken with the host clock.
+--upsample S times ptx_upsample the same way (events around the call on the full-size handle's stream):
+a handle of 1/S the size renders --frames frames and denoises once, the full-size handle runs one
+G-buffer pass; --width / --height are the full size.
+--displayed-frame times what a host does per displayed frame while the camera moves (it yaws by
+--yaw-step and the frame index restarts before every frame), with the host clock from the first call
+to the completion of the last: a full-size frame + ptx_denoise, or with --upsample S a frame +
+ptx_denoise at 1/S the size, then the G-buffer pass + ptx_upsample at full size.  The first form uses
+nothing newer than ptx_denoise, so the same script times an older library.
 """
 import argparse
 import csv
@@ -38,7 +48,9 @@ HBM_PEAK = 8.0e12  # B/s, the datasheet figure the bound is quoted against
 # compulsory bytes per pixel: what each kernel must read and write once
 # (temporal: this frame's guide record and colour, one previous guide / history / moments record,
 # the new history and moments; its variance pass reads the guide record, history and moments)
-BYTES = {"guide": 16 + 32, "variance": 48 + 16, "atrous": 48 + 16, "temporal": 32 + 16 + 32 + 16 + 8 + 16 + 8,
+# (upsample: per full-size pixel its guide record and the output; the small image's 48 B per pixel
+# are added by upsample_bound_ms)
+BYTES = {"upsample": 32 + 16, "guide": 16 + 32, "variance": 48 + 16, "atrous": 48 + 16, "temporal": 32 + 16 + 32 + 16 + 8 + 16 + 8,
          "variance_moments": 32 + 16 + 8 + 16}
 
 
@@ -115,6 +127,129 @@ def measure(args):
         sums[n] = round(statistics.median(per_call), 4)
     r.close()
     out["kernel_sum_ms_by_iterations"] = sums
+    return out
+
+
+def upsample_bound_ms(args, kind):
+    px = args.width * args.height
+    return bound_ms(kind, px) + (48 * (px // args.upsample ** 2) / HBM_PEAK * 1e3 if kind == "upsample" else 0.0)
+
+
+def upsample_pair(args, **kw):
+    """(small, full-size): the small handle rendered and denoised, the full-size one with its G-buffer."""
+    from pathtracerdemo_amd import _native as N
+    from pathtracerdemo_amd.renderer import Renderer
+    from pathtracerdemo_amd.scene.world import compile_scene
+    s = args.upsample
+    assert args.width % s == 0 and args.height % s == 0
+    cs = compile_scene(args.scene)
+    lo = Renderer(args.width // s, args.height // s, device=0, pipeline=args.pipeline)
+    hi = Renderer(args.width, args.height, device=0, pipeline=args.pipeline, **kw)
+    for r in (lo, hi):
+        r.Initialize(cs)
+    for _ in range(args.frames):
+        lo.Update()
+        lo.Render()
+    lo.Denoise(iterations=args.iterations)
+    hi.Update()
+    hi.run_pass(N.PTX_PASS_GBUFFER)
+    lo.synchronize()
+    hi.synchronize()
+    return lo, hi
+
+
+def measure_upsample(args):
+    from pathtracerdemo_amd import _native as N
+    bound = upsample_bound_ms(args, "guide") + upsample_bound_ms(args, "upsample")
+    out = {"what": "ptx_upsample", "scale": args.upsample, "width": args.width, "height": args.height, "scene": args.scene,
+           "pipeline": args.pipeline, "calls": args.calls, "warmup": args.warmup, "bound_ms_at_8TBs": round(bound, 4)}
+    if not args.no_events:
+        import torch
+        lo, hi = upsample_pair(args)
+        stream = torch.cuda.Stream()
+        hi.set_stream(stream.cuda_stream)
+        ms = []
+        for i in range(args.warmup + args.calls):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            hi.Upsample(lo)
+            b.record(stream)
+            b.synchronize()
+            if i >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        hi.set_stream(None)
+        for r in (hi, lo):
+            r.close()
+        out["whole_call_ms"] = {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}
+        out["whole_call_fraction_of_bound"] = round(bound / statistics.median(ms), 3)
+    lo, hi = upsample_pair(args, time_launches=True)
+    per_call = []
+    for i in range(args.warmup + args.calls):
+        before = hi.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE]
+        hi.Upsample(lo)
+        hi.synchronize()
+        if i >= args.warmup:
+            per_call.append(hi.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE] - before)
+    for r in (hi, lo):
+        r.close()
+    out["kernel_sum_ms"] = round(statistics.median(per_call), 4)
+    return out
+
+
+def measure_displayed_frame(args):
+    """Host milliseconds per displayed frame under a yawing camera, every frame waited for."""
+    import time
+    from pathtracerdemo_amd import _native as N
+    from pathtracerdemo_amd.renderer import Renderer
+    from pathtracerdemo_amd.scene.world import compile_scene
+    s = args.upsample
+    cs = compile_scene(args.scene)
+    full = Renderer(args.width, args.height, device=0, pipeline=args.pipeline)
+    small = Renderer(args.width // s, args.height // s, device=0, pipeline=args.pipeline) if s else None
+    rs = [r for r in (small, full) if r is not None]
+    for r in rs:
+        r.Initialize(cs)
+    ms = []
+    for i in range(args.warmup + args.calls):
+        t0 = time.perf_counter()
+        for r in rs:
+            r.GetCamera().set_yaw(args.yaw_step * (i + 1))
+            r.ResetFrameCount()
+            r.Update()
+        if s:
+            small.Render()
+            small.Denoise(iterations=args.iterations)
+            full.run_pass(N.PTX_PASS_GBUFFER)
+            full.Upsample(small)
+        else:
+            full.Render()
+            full.Denoise(iterations=args.iterations)
+        for r in rs:
+            r.synchronize()
+        if i >= args.warmup:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    for r in rs:
+        r.close()
+    return {"what": "displayed frame, moving camera", "form": f"1/{s} size + G-buffer pass + ptx_upsample" if s else "full size + ptx_denoise",
+            "yaw_step": args.yaw_step, "width": args.width, "height": args.height, "scene": args.scene, "pipeline": args.pipeline,
+            "iterations": args.iterations, "frames": args.calls, "warmup": args.warmup,
+            "host_ms_per_frame": {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}}
+
+
+def upsample_from_trace(args):
+    """Median duration of the two kernels of a ptx_upsample call (dn_guide, dn_upsample) over the traced calls."""
+    rows = [r for r in csv.DictReader(open(args.trace)) if "dn_" in r["Kernel_Name"]]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    calls = [(a, b) for a, b in zip(rows, rows[1:]) if "dn_guide" in a["Kernel_Name"] and "dn_upsample" in b["Kernel_Name"]][-args.calls:]
+    out = {"what": "ptx_upsample per kernel (rocprofv3 kernel trace)", "scale": args.upsample, "width": args.width,
+           "height": args.height, "calls": len(calls), "kernels": []}
+    for k, kind in enumerate(("guide", "upsample")):
+        us = statistics.median((int(c[k]["End_Timestamp"]) - int(c[k]["Start_Timestamp"])) / 1e3 for c in calls)
+        bound = upsample_bound_ms(args, kind) * 1e3
+        out["kernels"].append({"kernel": calls[0][k]["Kernel_Name"].split("(")[0].replace("void ", ""), "median_us": round(us, 2),
+                               "lds": int(calls[0][k]["LDS_Block_Size"]), "scratch": int(calls[0][k]["Scratch_Size"]),
+                               "bound_us_at_8TBs": round(bound, 2), "fraction_of_bound": round(bound / us, 3)})
+    out["sum_us"] = round(sum(k["median_us"] for k in out["kernels"]), 2)
     return out
 
 
@@ -264,10 +399,18 @@ def main():
     ap.add_argument("--temporal", action="store_true", help="the temporal mode on a frame_color handle")
     ap.add_argument("--yaw-step", type=float, default=0.5, help="--temporal: degrees the camera yaws before every call (0: still)")
     ap.add_argument("--bands", type=int, default=0, help="time ptx_denoise_bands on the frame as this many equal row bands")
+    ap.add_argument("--upsample", type=int, default=0, help="time ptx_upsample from 1/S of --width x --height (S: 2, 3 or 4)")
+    ap.add_argument("--displayed-frame", action="store_true", help="host ms per displayed frame under a yawing camera")
     ap.add_argument("--no-events", action="store_true", help="only the TIME_LAUNCHES handle (the run a profiler traces)")
     ap.add_argument("--trace", help="a rocprofv3 run_kernel_trace.csv of this script: print per-kernel medians")
     args = ap.parse_args()
-    print(json.dumps(from_trace(args) if args.trace else measure_bands(args) if args.bands else measure(args)))
+    if args.displayed_frame:
+        out = measure_displayed_frame(args)
+    elif args.upsample:
+        out = upsample_from_trace(args) if args.trace else measure_upsample(args)
+    else:
+        out = from_trace(args) if args.trace else measure_bands(args) if args.bands else measure(args)
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
