@@ -360,6 +360,39 @@ typedef struct ptx_upsample_params {
     uint32_t reserved[7];  /* zero */
 } ptx_upsample_params;     /* 32 bytes */
 int ptx_upsample(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_params *p /* NULL = defaults */);
+/* ptx_upsample for a frame split into row bands (Upsampling, Bands): n pairs in band
+ * order, lo[i] a band [b0, b1) of the w x h frame after ptx_denoise_bands, hi[i] the band
+ * [s*b0, s*b1) of the s*w x s*h frame on the same device (several pairs may share a GPU); every
+ * hi[i]'s rows of the result equal the whole-image ptx_upsample's bit for bit.  The forms are
+ * ptx_denoise_bands': n pairs of one process whose lo bands continue one another and cover the frame;
+ * n = 1 with two whole-image handles (exactly ptx_upsample(hi[0], lo[0], p)); or, n = 1 with a lo[0]
+ * whose communicator has world > 1, this rank's pair of a frame every rank makes the call for.
+ *   Full-size row y reads small rows y0 - 1 .. y0 + 2, y0 = floor((y + 0.5) / s - 0.5): b0 - 2 for
+ * y = s*b0, b1 + 1 for y = s*b1 - 1.  So one exchange per call brings each pair the last 2 own rows of
+ * the lo band above and the first 2 of the lo band below: their PTX_BUF_DENOISED, 16 B per pixel, into
+ * a buffer hi[i] owns (allocated by the first call, counted in device_bytes).  Either every lo owns a
+ * communicator (one group of sends / receives over them, counted in lo's halo_bytes_sent) or none
+ * (peer copies).  The guide records of those rows are not sent: they are the ones lo[i]'s last
+ * ptx_denoise_bands left in its window (its halo is at least 4 rows).  All positions (x0, ax, y0, ay,
+ * stage 3's y / s) are the frame's.
+ *   Per pair ptx_upsample's preconditions hold (pipelines with a G-buffer, uniform words 4..22 and
+ * triangles, bvh_nodes, instances equal, hi[i] with a scene and a G-buffer pass or frame since its
+ * upload, lo[i] with a denoised image).  PTX_E_INVALID with the reason in hi[0]'s ptx_last_error,
+ * before any GPU work: a null array or handle, n outside 1..64, a handle that appears twice, hi rows
+ * that are not s times lo's, a pair on two devices, pairs that differ in size or pipeline, a gap
+ * between bands or bands that do not cover the image (not in the rank form), a mix of bands with and
+ * without communicators, with more than one band a lo band of fewer than 2 rows, TEST_MCPT, a lo band
+ * without a denoised image (or whose last call was not ptx_denoise_bands), an hi band without a
+ * G-buffer, cameras or scenes that differ, a sigma_plane that is negative or not finite, a non-zero
+ * reserved word.  ptx_upsample itself keeps refusing band handles.
+ *   hi[i]'s PTX_BUF_DENOISED holds its own band_h rows, alpha 1 (its buffers are laid out as a first
+ * ptx_denoise_bands lays them out); launches (hi[i]'s PTX_STAT_DENOISE): 2 per band.  Asynchronous:
+ * hi[i]'s stream waits for the tail of lo[i]'s last denoise and for its neighbours' rows; every
+ * stream lo[i]'s next GPU work can run on waits until hi[i]'s kernels have read it and the
+ * neighbouring pairs have copied its rows.  lo's accumulation, G-buffer, reservoirs, denoiser state
+ * and output and hi's G-buffer keep their bits. */
+int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n,
+                       const ptx_upsample_params *p /* NULL = defaults */);
 /* What ptx_present and ptx_present_async read: PTX_BUF_ACCUM (the default) or PTX_BUF_DENOISED
  * (fails before the first ptx_denoise or ptx_upsample). */
 int ptx_present_source(ptx_handle *h, int which);

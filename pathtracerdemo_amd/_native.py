@@ -51,7 +51,7 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_halo_unpack", "ptx_comm_unique_id", "ptx_comm_init", "ptx_comm_init_all", "ptx_render_bands",
             "ptx_row_census", "ptx_comm_info", "ptx_present", "ptx_present_async", "ptx_present_poll",
             "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands",
-            "ptx_upsample"]
+            "ptx_upsample", "ptx_upsample_bands"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -135,6 +135,7 @@ def load(path: str = LIB_PATH):
     lib.ptx_denoise.argtypes = [H, ctypes.POINTER(PtxDenoiseParams)]
     lib.ptx_denoise_bands.argtypes = [ctypes.POINTER(H), ctypes.c_int, ctypes.POINTER(PtxDenoiseParams)]
     lib.ptx_upsample.argtypes = [H, H, ctypes.POINTER(PtxUpsampleParams)]
+    lib.ptx_upsample_bands.argtypes = [ctypes.POINTER(H), ctypes.POINTER(H), ctypes.c_int, ctypes.POINTER(PtxUpsampleParams)]
     lib.ptx_present_source.argtypes = [H, ctypes.c_int]
     lib.ptx_run_passes.argtypes = [H, P, ctypes.c_int]
     lib.ptx_halo_rows.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),

@@ -1611,6 +1611,8 @@ int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b) {
     }
     if (e != hipSuccess) return fail(h, PTX_E_HIP, "denoiser launch: %s", hipGetErrorString(e));
     h->dn_guide_swapped = c.temporal != 0u;  // (ptx_upsample reads this call's guide records)
+    h->dn_guide_top = b.top;                 // (ptx_upsample_bands: and those of its neighbours' rows)
+    h->dn_guide_bot = b.bot;
     h->dn_stream = st;
     if (c.temporal) {  // this call is the next one's previous call: its guides (no copy), history set and camera
         std::swap(h->d_dn_guide, h->d_dn_guide_prev);
@@ -1623,6 +1625,99 @@ int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b) {
         mat4_inverse(vpinv, h->dn_vp);
         h->dn_hist_valid = true;
     }
+    return PTX_OK;
+}
+
+// ---------------------------------------------------------------- upsampler (ptx_upsample, ptx_upsample_bands)
+int upsample_params(ptx_handle *err, const ptx_upsample_params *p, float &sigma_plane, const char *what) {
+    sigma_plane = 0.02f;
+    if (p) {
+        for (uint32_t r : p->reserved)
+            if (r) return fail(err, PTX_E_INVALID, "%s: a reserved word is not zero", what);
+        if (!std::isfinite(p->sigma_plane) || p->sigma_plane < 0.0f)
+            return fail(err, PTX_E_INVALID, "%s: sigma_plane %g (finite, >= 0)", what, p->sigma_plane);
+        if (p->sigma_plane != 0.0f) sigma_plane = p->sigma_plane;
+    }
+    return PTX_OK;
+}
+
+int upsample_pair_check(ptx_handle *err, ptx_handle *hi, ptx_handle *lo, uint32_t &s, const char *what) {
+    for (ptx_handle *h : {hi, lo})
+        if (h->cfg.pipeline == PTX_PIPELINE_MCPT)
+            return fail(err, PTX_E_INVALID, "%s: the %s handle runs the TEST_MCPT pipeline, which has no G-buffer", what,
+                        h == hi ? "full-size" : "small");
+    if (hi->device != lo->device) return fail(err, PTX_E_INVALID, "%s: the handles are on devices %d and %d", what, hi->device, lo->device);
+    if (!lo->d_denoised.p || !(lo->dn_guide_swapped ? lo->d_dn_guide_prev.p : lo->d_dn_guide.p))
+        return fail(err, PTX_E_INVALID, "%s: the small handle has no denoised image (ptx_denoise first)", what);
+    if (!hi->scene_loaded || !hi->frame_set || !hi->layout_valid || !hi->drawn)
+        return fail(err, PTX_E_INVALID, "%s: the full-size handle has no G-buffer of its scene yet (a G-buffer pass or a frame first)", what);
+    const uint32_t W = hi->cfg.width, H = hi->cfg.height, w = lo->cfg.width, hh = lo->cfg.height;
+    s = W / w;
+    if (s < 2u || s > 4u || W != s * w || H != s * hh)
+        return fail(err, PTX_E_INVALID, "%s: %ux%u is not 2, 3 or 4 times %ux%u", what, W, H, w, hh);
+    if (std::memcmp(hi->uniform + 4, lo->uniform + 4, 19 * sizeof(uint32_t)) != 0)
+        return fail(err, PTX_E_INVALID, "%s: the handles' cameras differ (uniform words 4..22)", what);
+    if (hi->n_tris != lo->n_tris || hi->n_nodes != lo->n_nodes || hi->n_inst != lo->n_inst)
+        return fail(err, PTX_E_INVALID, "%s: the handles' scenes differ (%u / %u triangles, %u / %u BVH nodes, %u / %u instances)", what,
+                    hi->n_tris, lo->n_tris, hi->n_nodes, lo->n_nodes, hi->n_inst, lo->n_inst);
+    return PTX_OK;
+}
+
+hipError_t upsample_launch(ptx_handle *hi, ptx_handle *lo, uint32_t s, float sigma_plane, uint32_t top, uint32_t bot) {
+    const uint32_t W = hi->cfg.width, H = hi->cfg.height, w = lo->cfg.width;
+    const bool band = top || bot || hi->band_h != H;  // (a whole image without halo rows: ptx_upsample's launch)
+    const hipStream_t st = hi->cur().stream;
+    const Scene sc = make_scene(hi);
+    // the denoiser's buffers of a band start dn_cap_top rows above it; lo's window starts `top` rows above its band
+    float4 *guide = (float4 *)hi->d_dn_guide.p + 2u * (size_t)hi->dn_cap_top * W;
+    float4 *out = (float4 *)hi->d_denoised.p + (size_t)hi->dn_cap_top * W;
+    const float4 *lguide = (const float4 *)(lo->dn_guide_swapped ? lo->d_dn_guide_prev.p : lo->d_dn_guide.p) +
+                           2u * (size_t)(lo->dn_cap_top - top) * w;
+    const float4 *lcolor = (const float4 *)lo->d_denoised.p + (size_t)lo->dn_cap_top * w;
+    hipError_t e = denoise_timed(hi, st, hipSuccess, [&] { return launch_denoise_guide(sc, gbuf_band(hi), guide, sigma_plane, st); });
+    e = denoise_timed(hi, st, e, [&] {
+        if (!band) return launch_denoise_upsample(s, W, H, guide, lguide, lcolor, out, st);
+        const UpWin win{lo->cfg.row_begin - top, top + lo->band_h + bot, top, top + lo->band_h, hi->cfg.row_begin, hi->cfg.row_end};
+        return launch_denoise_upsample_win(s, W, H, win, guide, lguide, lcolor, (const float4 *)hi->d_up_halo.p, out, st);
+    });
+    if (e != hipSuccess) return e;
+    hi->dn_guide_swapped = false;  // (this handle's output and the guide records it was written under)
+    hi->dn_guide_top = hi->dn_guide_bot = 0u;
+    hi->dn_stream = st;
+    return hipSuccess;
+}
+
+int upsample_source(ptx_handle *err, ptx_handle *lo) {
+    if (!lo->ev_up_src) HIP_CHECK(err, hipEventCreateWithFlags(&lo->ev_up_src, hipEventDisableTiming));
+    HIP_CHECK(err, hipEventRecord(lo->ev_up_src, lo->dn_stream));
+    return PTX_OK;
+}
+int upsample_done(ptx_handle *err, ptx_handle *hi) {
+    // (recorded whatever was launched: a small handle never waits on a stale event)
+    if (!hi->ev_up_done) HIP_CHECK(err, hipEventCreateWithFlags(&hi->ev_up_done, hipEventDisableTiming));
+    HIP_CHECK(err, hipEventRecord(hi->ev_up_done, hi->cur().stream));
+    return PTX_OK;
+}
+int upsample_release(ptx_handle *err, ptx_handle *lo, ptx_handle *hi) {
+    // lo's next work runs on its current context's stream (a denoise, reset or upload) or on the next
+    // context's (a frame), and frames enqueued since the denoise have moved cur() off dn_stream: every
+    // stream lo's contexts run on waits
+    HIP_CHECK(err, hipStreamWaitEvent(lo->dn_stream, hi->ev_up_done, 0));
+    for (auto &c : lo->ctx)
+        if (c.stream && c.stream != lo->dn_stream) HIP_CHECK(err, hipStreamWaitEvent(c.stream, hi->ev_up_done, 0));
+    return PTX_OK;
+}
+
+int upsample_alloc(ptx_handle *hi, uint32_t halo_rows, uint32_t w) {
+    if (!hi->d_dn_guide.p) {  // (the layout a band's first ptx_denoise_bands would give its buffers: denoise_alloc)
+        hi->dn_cap_top = std::min(dn_reach(6u), hi->cfg.row_begin);
+        hi->dn_cap_bot = std::min(dn_reach(6u), hi->cfg.height - hi->cfg.row_end);
+    }
+    const size_t px = (size_t)(hi->dn_cap_top + hi->band_h + hi->dn_cap_bot) * hi->cfg.width;
+    if (int rc = alloc_buf(hi, hi->d_dn_guide, px * 32u)) return rc;
+    if (int rc = alloc_buf(hi, hi->d_denoised, px * 16u)) return rc;
+    if (halo_rows)  // the neighbours' rows of the small image: 2 above, 2 below
+        if (int rc = alloc_buf(hi, hi->d_up_halo, (size_t)4u * w * 16u)) return rc;
     return PTX_OK;
 }
 
@@ -1985,7 +2080,7 @@ int ptx_get_stats(ptx_handle *h, ptx_stats *out) {
                         c.surf.bytes + h->d_psurf.bytes + c.direct.bytes + h->d_dn_guide.bytes + h->d_dn_work.bytes +
                         h->d_denoised.bytes + h->d_frame_color.bytes + h->d_dn_guide_prev.bytes + h->d_dn_hist[0].bytes +
                         h->d_dn_hist[1].bytes + h->d_dn_mom[0].bytes + h->d_dn_mom[1].bytes + h->d_dn_halo_g.bytes +
-                        h->d_dn_halo_c.bytes;
+                        h->d_dn_halo_c.bytes + h->d_up_halo.bytes;
     return PTX_OK;
 }
 
@@ -2167,62 +2262,24 @@ int ptx_upsample(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_params *p) {
     const char *what = "ptx_upsample";
     // ---- refusals, all before any GPU work
     if (hi == lo) return fail(hi, PTX_E_INVALID, "%s: one handle on both sides", what);
-    float sigma_plane = 0.02f;
-    if (p) {
-        for (uint32_t r : p->reserved)
-            if (r) return fail(hi, PTX_E_INVALID, "%s: a reserved word is not zero", what);
-        if (!std::isfinite(p->sigma_plane) || p->sigma_plane < 0.0f)
-            return fail(hi, PTX_E_INVALID, "%s: sigma_plane %g (finite, >= 0)", what, p->sigma_plane);
-        if (p->sigma_plane != 0.0f) sigma_plane = p->sigma_plane;
-    }
-    for (ptx_handle *h : {hi, lo}) {
-        const char *side = h == hi ? "full-size" : "small";
+    float sigma_plane;
+    if (int rc = upsample_params(hi, p, sigma_plane, what)) return rc;
+    for (ptx_handle *h : {hi, lo})
         if (h->cfg.row_begin != 0 || h->band_h != h->cfg.height)
-            return fail(hi, PTX_E_INVALID, "%s: the %s handle is a band (rows %u..%u)", what, side, h->cfg.row_begin, h->cfg.row_end);
-        if (h->cfg.pipeline == PTX_PIPELINE_MCPT)
-            return fail(hi, PTX_E_INVALID, "%s: the %s handle runs the TEST_MCPT pipeline, which has no G-buffer", what, side);
-    }
-    if (hi->device != lo->device) return fail(hi, PTX_E_INVALID, "%s: the handles are on devices %d and %d", what, hi->device, lo->device);
-    const float4 *lguide = (const float4 *)(lo->dn_guide_swapped ? lo->d_dn_guide_prev.p : lo->d_dn_guide.p);
-    if (!lo->d_denoised.p || !lguide) return fail(hi, PTX_E_INVALID, "%s: the small handle has no denoised image (ptx_denoise first)", what);
-    if (!hi->scene_loaded || !hi->frame_set || !hi->layout_valid || !hi->drawn)
-        return fail(hi, PTX_E_INVALID, "%s: the full-size handle has no G-buffer of its scene yet (a G-buffer pass or a frame first)", what);
-    const uint32_t W = hi->cfg.width, H = hi->cfg.height, w = lo->cfg.width, hh = lo->cfg.height, s = W / w;
-    if (s < 2u || s > 4u || W != s * w || H != s * hh)
-        return fail(hi, PTX_E_INVALID, "%s: %ux%u is not 2, 3 or 4 times %ux%u", what, W, H, w, hh);
-    if (std::memcmp(hi->uniform + 4, lo->uniform + 4, 19 * sizeof(uint32_t)) != 0)
-        return fail(hi, PTX_E_INVALID, "%s: the handles' cameras differ (uniform words 4..22)", what);
-    if (hi->n_tris != lo->n_tris || hi->n_nodes != lo->n_nodes || hi->n_inst != lo->n_inst)
-        return fail(hi, PTX_E_INVALID, "%s: the handles' scenes differ (%u / %u triangles, %u / %u BVH nodes, %u / %u instances)", what,
-                    hi->n_tris, lo->n_tris, hi->n_nodes, lo->n_nodes, hi->n_inst, lo->n_inst);
+            return fail(hi, PTX_E_INVALID, "%s: the %s handle is a band (rows %u..%u): ptx_upsample_bands", what,
+                        h == hi ? "full-size" : "small", h->cfg.row_begin, h->cfg.row_end);
+    uint32_t s = 0;
+    if (int rc = upsample_pair_check(hi, hi, lo, s, what)) return rc;
     // ---- buffers (first call), then: behind the small handle's denoise, the two launches, and the
     // small handle's streams behind them
     HIP_CHECK(hi, hipSetDevice(hi->device));
-    const size_t px = (size_t)W * H;
-    if (int rc = alloc_buf(hi, hi->d_dn_guide, px * 32u)) return rc;
-    if (int rc = alloc_buf(hi, hi->d_denoised, px * 16u)) return rc;
-    for (hipEvent_t *ev : {&lo->ev_up_src, &hi->ev_up_done})
-        if (!*ev) HIP_CHECK(hi, hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    const hipStream_t st = hi->cur().stream;
-    HIP_CHECK(hi, hipEventRecord(lo->ev_up_src, lo->dn_stream));
-    HIP_CHECK(hi, hipStreamWaitEvent(st, lo->ev_up_src, 0));
-    const Scene sc = make_scene(hi);
-    float4 *guide = (float4 *)hi->d_dn_guide.p;
-    hipError_t e = denoise_timed(hi, st, hipSuccess, [&] { return launch_denoise_guide(sc, gbuf_band(hi), guide, sigma_plane, st); });
-    e = denoise_timed(hi, st, e, [&] {
-        return launch_denoise_upsample(s, W, H, guide, lguide, (const float4 *)lo->d_denoised.p, (float4 *)hi->d_denoised.p, st);
-    });
-    // (recorded whatever was launched: the small handle never waits on a stale event)
-    HIP_CHECK(hi, hipEventRecord(hi->ev_up_done, st));
-    // lo's next work runs on its current context's stream (a denoise, reset or upload) or on the next
-    // context's (a frame), and frames enqueued since the denoise have moved cur() off dn_stream: every
-    // stream lo's contexts run on waits
-    HIP_CHECK(hi, hipStreamWaitEvent(lo->dn_stream, hi->ev_up_done, 0));
-    for (auto &c : lo->ctx)
-        if (c.stream && c.stream != lo->dn_stream) HIP_CHECK(hi, hipStreamWaitEvent(c.stream, hi->ev_up_done, 0));
+    if (int rc = upsample_alloc(hi, 0u, lo->cfg.width)) return rc;
+    if (int rc = upsample_source(hi, lo)) return rc;
+    HIP_CHECK(hi, hipStreamWaitEvent(hi->cur().stream, lo->ev_up_src, 0));
+    const hipError_t e = upsample_launch(hi, lo, s, sigma_plane, 0u, 0u);
+    if (int rc = upsample_done(hi, hi)) return rc;
+    if (int rc = upsample_release(hi, lo, hi)) return rc;
     if (e != hipSuccess) return fail(hi, PTX_E_HIP, "%s launch: %s", what, hipGetErrorString(e));
-    hi->dn_guide_swapped = false;  // (this handle's output and the guide records it was written under)
-    hi->dn_stream = st;
     return PTX_OK;
 }
 
@@ -2306,7 +2363,7 @@ int ptx_destroy(ptx_handle *h) {
                       &h->d_insts, &h->d_mats, &h->d_tverts, &h->d_accum, &h->d_counters, &h->d_qrays, &h->d_qhits, &h->d_hist,
                       &h->d_jstate, &h->d_jres, &h->d_psurf, &h->d_census, &h->d_wgt, &h->d_dn_guide, &h->d_dn_work,
                       &h->d_denoised, &h->d_frame_color, &h->d_dn_guide_prev, &h->d_dn_hist[0], &h->d_dn_hist[1], &h->d_dn_mom[0],
-                      &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c})
+                      &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_up_halo})
         free_buf(*b);
     for (auto &c : h->ctx) {
         for (DevBuf *b : {&c.gbuf, &c.res, &c.direct, &c.nbr, &c.tjstate, &c.tjres, &c.surf, &c.wstate, &c.wrays, &c.wres[0],

@@ -15,6 +15,8 @@
 //     when the handles have none.
 // The denoiser of a split frame (ptx_denoise_bands) exchanges a second halo the
 // same two ways: the rows of the neighbours' G-buffer and colours (or temporal state) its filter reaches.
+// The upsampler of a split frame (ptx_upsample_bands) exchanges a third: 2 rows of the neighbours' small
+// denoised image.
 // PTX_FLAG_HALO_OVERLAP splits the spatial pass into the rows whose neighbourhood lies inside
 // the band (run while the halo is in flight) and the edge rows (run when it has landed).
 //
@@ -972,6 +974,173 @@ int ptx_denoise_bands(ptx_handle *const *hs, int n, const ptx_denoise_params *p)
             if (i + 1 < n) HIP_CHECK(hs[i], hipStreamWaitEvent(hs[i]->cur().stream, hs[i + 1]->ev_dn_copied, 0));
         }
     }
+    return PTX_OK;
+}
+
+// ptx_upsample_bands: full-size band i reads small band i's denoised rows and kUpHalo rows of each
+// of its neighbours' (Upsampling, Bands); the neighbours' guide records are the
+// ones the small band's window has held since its ptx_denoise_bands.
+static constexpr uint32_t kUpHalo = 2;
+// the own rows [r0, r0 + kUpHalo) of small band lo's denoised image / where hi keeps the rows from above or below
+static char *up_send_rows(ptx_handle *lo, uint32_t r0) {
+    return (char *)lo->d_denoised.p + ((size_t)lo->dn_cap_top + r0) * lo->cfg.width * 16u;
+}
+static char *up_recv_rows(ptx_handle *hi, uint32_t w, uint32_t top, bool above) {
+    return (char *)hi->d_up_halo.p + (above ? 0u : (size_t)top * w * 16u);
+}
+
+int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n, const ptx_upsample_params *p) {
+    const char *what = "ptx_upsample_bands";
+    if (!hi || !hi[0]) return PTX_E_INVALID;
+    ptx_handle *h0 = hi[0];
+    // ---- refusals, all before any GPU work, all in hi[0]'s message
+    if (!lo || n < 1 || n > 64) return fail(h0, PTX_E_INVALID, "%s: a null array, or %d pairs (1..64)", what, n);
+    for (int i = 0; i < n; ++i)
+        if (!hi[i] || !lo[i]) return fail(h0, PTX_E_INVALID, "%s: pair %d has a null handle", what, i);
+    for (int i = 0; i < 2 * n; ++i)
+        for (int k = 0; k < i; ++k)
+            if ((i < n ? hi[i] : lo[i - n]) == (k < n ? hi[k] : lo[k - n]))
+                return fail(h0, PTX_E_INVALID, "%s: one handle appears twice", what);
+    ptx_handle *l0 = lo[0];
+    const bool nccl = l0->comm != nullptr;
+    // the rank form: one pair of a frame whose other bands are other ranks' (every rank makes the call)
+    const bool rank_form = n == 1 && nccl && l0->world > 1;
+    const auto whole = [](const ptx_handle *h) { return h->cfg.row_begin == 0 && h->band_h == h->cfg.height; };
+    if (n == 1 && !rank_form && whole(h0) && whole(l0)) return ptx_upsample(h0, l0, p);
+    float sigma_plane;
+    if (int rc = upsample_params(h0, p, sigma_plane, what)) return rc;
+    // the frame's geometry first: one size and pipeline per side, one scale, rows that match and continue
+    const uint32_t h = l0->cfg.height, s = h0->cfg.width / l0->cfg.width;
+    if (s < 2u || s > 4u || h0->cfg.width != s * l0->cfg.width || h0->cfg.height != s * h)
+        return fail(h0, PTX_E_INVALID, "%s: %ux%u is not 2, 3 or 4 times %ux%u", what, h0->cfg.width, h0->cfg.height,
+                    l0->cfg.width, h);
+    for (int i = 0; i < n; ++i) {
+        ptx_handle *a = hi[i], *b = lo[i];
+        if (b->cfg.width != l0->cfg.width || b->cfg.height != h || b->cfg.pipeline != l0->cfg.pipeline ||
+            a->cfg.width != h0->cfg.width || a->cfg.height != h0->cfg.height || a->cfg.pipeline != h0->cfg.pipeline)
+            return fail(h0, PTX_E_INVALID, "%s: pair %d differs in size or pipeline", what, i);
+        if ((b->comm != nullptr) != nccl)
+            return fail(h0, PTX_E_INVALID, "%s: either every small band owns a communicator or none", what);
+        if (nccl && !rank_form && (b->rank != i || b->world != n))
+            return fail(h0, PTX_E_INVALID, "%s: small band %d is rank %d of %d", what, i, b->rank, b->world);
+        if (i && lo[i - 1]->cfg.row_end != b->cfg.row_begin)
+            return fail(h0, PTX_E_INVALID, "%s: small band %d does not start where band %d ends", what, i, i - 1);
+        if (a->cfg.row_begin != s * b->cfg.row_begin || a->cfg.row_end != s * b->cfg.row_end)
+            return fail(h0, PTX_E_INVALID, "%s: pair %d: the full-size band has rows %u..%u, %u times the small band's %u..%u are %u..%u",
+                        what, i, a->cfg.row_begin, a->cfg.row_end, s, b->cfg.row_begin, b->cfg.row_end, s * b->cfg.row_begin,
+                        s * b->cfg.row_end);
+    }
+    if (!rank_form && (l0->cfg.row_begin != 0 || lo[n - 1]->cfg.row_end != h))
+        return fail(h0, PTX_E_INVALID, "%s: the small bands cover rows %u..%u of %u: a band needs the rows above and below it",
+                    what, l0->cfg.row_begin, lo[n - 1]->cfg.row_end, h);
+    if (rank_form) {
+        if ((l0->cfg.row_begin != 0) != (l0->rank > 0) || (l0->cfg.row_end != h) != (l0->rank + 1 < l0->world))
+            return fail(h0, PTX_E_INVALID, "%s: rank %d of %d holds rows %u..%u of %u", what, l0->rank, l0->world,
+                        l0->cfg.row_begin, l0->cfg.row_end, h);
+        for (int k = 0; k < 2; ++k) {
+            if (k == 0 ? l0->rank == 0 : l0->rank + 1 == l0->world) continue;
+            const uint32_t rows = l0->nb_rows[k][1] - l0->nb_rows[k][0];
+            if (rows < kUpHalo)
+                return fail(h0, PTX_E_INVALID, "%s: small band %d has %u rows; every band sends %u", what,
+                            k == 0 ? l0->rank - 1 : l0->rank + 1, rows, kUpHalo);
+        }
+    }
+    for (int i = 0; i < n; ++i)
+        if (lo[i]->band_h < kUpHalo)
+            return fail(h0, PTX_E_INVALID, "%s: small band %d has %u rows; every band sends %u", what,
+                        rank_form ? l0->rank : i, lo[i]->band_h, kUpHalo);
+    // then what every pair must share, and a band's halo: kUpHalo rows of the band above and of the band
+    // below, where the frame has them, with the guide records lo's last denoise left around its rows
+    std::vector<uint32_t> top(n), bot(n);
+    for (int i = 0; i < n; ++i) {
+        ptx_handle *b = lo[i];
+        uint32_t si = 0;
+        if (int rc = upsample_pair_check(h0, hi[i], b, si, what)) return rc;
+        top[i] = b->cfg.row_begin ? kUpHalo : 0u;
+        bot[i] = b->cfg.row_end != h ? kUpHalo : 0u;
+        if (b->dn_guide_top < top[i] || b->dn_guide_bot < bot[i])
+            return fail(h0, PTX_E_INVALID, "%s: small band %d has no denoised image with its neighbours' guide records "
+                                           "(ptx_denoise_bands first)", what, rank_form ? b->rank : i);
+    }
+    if (nccl)
+        for (int i = 0; i < n; ++i)
+            if (int rc = comm_health(lo[i])) return rc;
+    // ---- every pair: hi's buffers (first call), and its stream behind the tail of lo's last denoise
+    const size_t w = l0->cfg.width, bytes = (size_t)kUpHalo * w * 16u;
+    for (int i = 0; i < n; ++i) {
+        HIP_CHECK(h0, hipSetDevice(hi[i]->device));
+        if (int rc = upsample_alloc(hi[i], top[i] + bot[i], (uint32_t)w)) return rc;
+        if (int rc = upsample_source(h0, lo[i])) return rc;
+    }
+    for (int i = 0; i < n; ++i) {
+        HIP_CHECK(h0, hipSetDevice(hi[i]->device));
+        HIP_CHECK(h0, hipStreamWaitEvent(hi[i]->cur().stream, lo[i]->ev_up_src, 0));
+    }
+    // ---- the exchange, on hi's streams: lo's first / last rows to its neighbours' pairs
+    if (nccl) {  // one group per call, over the small bands' communicators
+        const Rccl &R = rccl();
+        NCCL_CHECK(l0, R.group_start());
+        int rc = PTX_OK;
+        for (int i = 0; i < n && !rc; ++i) {
+            ptx_handle *a = hi[i], *b = lo[i];
+            const hipStream_t st = a->cur().stream;
+            ncclComm_t cm = (ncclComm_t)b->comm;
+            rc = [&]() -> int {
+                HIP_CHECK(h0, hipSetDevice(a->device));
+                for (int side = 0; side < 2; ++side) {
+                    if (!(side == 0 ? top[i] : bot[i])) continue;
+                    const int peer = side == 0 ? b->rank - 1 : b->rank + 1;
+                    NCCL_CHECK(b, R.send(up_send_rows(b, side == 0 ? 0u : b->band_h - kUpHalo), bytes, ncclUint8, peer, cm, st));
+                    NCCL_CHECK(b, R.recv(up_recv_rows(a, (uint32_t)w, top[i], side == 0), bytes, ncclUint8, peer, cm, st));
+                    b->halo_bytes_sent += bytes;
+                }
+                return PTX_OK;
+            }();
+        }
+        if (rc) {
+            (void)R.group_end();
+            return rc;
+        }
+        if (rank_form) {
+            if (int r2 = group_end_wait(l0)) return r2;
+        } else {
+            NCCL_CHECK(l0, R.group_end());
+        }
+    } else {
+        // peer copies: hi[i]'s stream copies once its neighbours' denoises are complete (their ev_up_src)
+        for (int i = 0; i < n; ++i) {
+            ptx_handle *a = hi[i];
+            HIP_CHECK(h0, hipSetDevice(a->device));
+            const hipStream_t st = a->cur().stream;
+            for (int side = 0; side < 2; ++side) {
+                if (!(side == 0 ? top[i] : bot[i])) continue;
+                ptx_handle *nb = lo[side == 0 ? i - 1 : i + 1];
+                HIP_CHECK(h0, hipStreamWaitEvent(st, nb->ev_up_src, 0));
+                HIP_CHECK(h0, hipMemcpyPeerAsync(up_recv_rows(a, (uint32_t)w, top[i], side == 0), a->device,
+                                                 up_send_rows(nb, side == 0 ? nb->band_h - kUpHalo : 0u), nb->device, bytes, st));
+            }
+        }
+    }
+    // ---- every pair: the two launches, ev_up_done behind them
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n; ++i) {
+        HIP_CHECK(h0, hipSetDevice(hi[i]->device));
+        if (e == hipSuccess) e = upsample_launch(hi[i], lo[i], s, sigma_plane, top[i], bot[i]);
+        if (int rc = upsample_done(h0, hi[i])) return rc;
+    }
+    // ---- a small band's next work waits until its own pair has read it and -- peer copies -- its
+    // neighbours' pairs have copied its rows (a send is complete behind the sending pair's kernels)
+    for (int i = 0; i < n; ++i) {
+        HIP_CHECK(h0, hipSetDevice(lo[i]->device));
+        if (int rc = upsample_release(h0, lo[i], hi[i])) return rc;
+        if (!nccl) {
+            if (i > 0)
+                if (int rc = upsample_release(h0, lo[i], hi[i - 1])) return rc;
+            if (i + 1 < n)
+                if (int rc = upsample_release(h0, lo[i], hi[i + 1])) return rc;
+        }
+    }
+    if (e != hipSuccess) return fail(h0, PTX_E_HIP, "%s launch: %s", what, hipGetErrorString(e));
     return PTX_OK;
 }
 

@@ -11,7 +11,8 @@
 //   dn_atrous    one iteration at step 2^i on the working image (ping-pong); steps 1, 2, 4 stage
 //                the 16x16 tile and its apron in LDS, steps >= 8 gather their taps directly
 //   dn_upsample  (ptx_upsample) a denoised image of 1/S the size, written at full size under the
-//                full-size guide records; the tile's footprint in the small image staged in LDS
+//                full-size guide records; the tile's footprint in the small image staged in LDS;
+//                dn_upsample_win (ptx_upsample_bands): a band of it from a window of the small image
 // Every kernel but dn_guide addresses a row window (DnWin): a W x rows image that is the whole
 // frame, or a band with the halo rows ptx_denoise_bands brought from its neighbours, filtered as if
 // it were the whole image; a launch computes rows [c0, c1) of it.
@@ -408,20 +409,38 @@ __global__ __launch_bounds__(kBlock) void dn_atrous_gather(uint32_t W, const DnW
 // lies in the kUpN x kUpN window staged from (x0 - 1, y0 - 1) of the tile's first pixel.
 constexpr int kUpN = 12;
 constexpr uint32_t kUpOutside = 0xFFFFFFFEu;  // staged key of an entry outside the image: no pixel's key (bit 31), not a miss
-template <int S>
-__global__ __launch_bounds__(kBlock) void dn_upsample(uint32_t W, uint32_t H, uint32_t w, uint32_t h,
-                                                      const float4 *__restrict__ hg, const float4 *__restrict__ lg,
-                                                      const float4 *__restrict__ lc, float4 *__restrict__ out) {
+// WIN (ptx_upsample_bands): the small image is a row window (UpWin, ptx_launch.h) whose colours lie in
+// two buffers, and the full-size rows are a band's.  Every position -- fx, x0, ax, fy, y0, ay, stage
+// 3's y / S -- is the frame's (at S = 3, (float(y) + 0.5f) / 3.0f of a window-relative y rounds
+// differently: tests/upsample_bands_ref.py); the window's offsets enter addresses only.  A row of
+// the frame outside the window is staged like a row outside the frame: with 2 halo rows no pixel of
+// the band has a candidate there.  Without WIN the code is the whole image's, `win` unread.
+template <int S, bool WIN>
+__device__ __forceinline__ void dn_upsample_tile(uint32_t W, uint32_t H, uint32_t w, uint32_t h, const UpWin &win,
+                                                 const float4 *__restrict__ hg, const float4 *__restrict__ lg,
+                                                 const float4 *__restrict__ lc, const float4 *__restrict__ lhalo,
+                                                 float4 *__restrict__ out, float4 *g0, float4 *g1, float4 *cv) {
     static_assert(S >= 2 && S <= 4 && (kDnTile + S - 2) / S + 4 <= kUpN, "the window holds a tile's candidates");
-    __shared__ float4 g0[kUpN * kUpN], g1[kUpN * kUpN], cv[kUpN * kUpN];
     const int tx = (int)(threadIdx.x & 15u), ty = (int)(threadIdx.x >> 4);
-    const uint32_t bx = blockIdx.x * kDnTile, by = blockIdx.y * kDnTile;
+    // the tile's first pixel in the frame; hg and out start at row Y0 of it
+    const uint32_t Y0 = WIN ? win.Y0 : 0u, Y1 = WIN ? win.Y1 : H;
+    const uint32_t bx = blockIdx.x * kDnTile, by = Y0 + blockIdx.y * kDnTile;
     const int ox = (int)__builtin_floorf(((float)bx + 0.5f) / (float)S - 0.5f) - 1;
     const int oy = (int)__builtin_floorf(((float)by + 0.5f) / (float)S - 0.5f) - 1;
     if (threadIdx.x < (uint32_t)(kUpN * kUpN)) {
         const int e = (int)threadIdx.x, gx = ox + e % kUpN, gy = oy + e / kUpN;
         float4 a = make_float4(0.0f, 0.0f, 0.0f, asf(kUpOutside)), b = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = b;
-        if (gx >= 0 && gy >= 0 && gx < (int)w && gy < (int)h) {
+        if (WIN) {
+            // lg starts at the window's row 0 (row win.y0 of the small frame); the window's rows [o0, o1)
+            // are lc's, the rows above and then the rows below them lhalo's
+            const int wy = gy - (int)win.y0;
+            if (gx >= 0 && gy >= 0 && gx < (int)w && gy < (int)h && wy >= 0 && wy < (int)win.rows) {
+                const size_t q = (size_t)wy * w + (size_t)gx;
+                a = lg[2u * q];
+                b = lg[2u * q + 1u];
+                c = dn_load(DnImage{lc, lhalo, win.o0, win.o1}, w, (uint32_t)gx, (uint32_t)wy);
+            }
+        } else if (gx >= 0 && gy >= 0 && gx < (int)w && gy < (int)h) {
             const size_t q = (size_t)gy * w + (size_t)gx;
             a = lg[2u * q];
             b = lg[2u * q + 1u];
@@ -433,8 +452,8 @@ __global__ __launch_bounds__(kBlock) void dn_upsample(uint32_t W, uint32_t H, ui
     }
     __syncthreads();
     const uint32_t x = bx + (uint32_t)tx, y = by + (uint32_t)ty;
-    if (x >= W || y >= H) return;
-    const size_t pix = (size_t)y * W + x;
+    if (x >= W || y >= Y1) return;
+    const size_t pix = (size_t)(y - Y0) * W + x;
     const float4 a = hg[2u * pix], b = hg[2u * pix + 1u];
     const uint32_t key = asu(a.w);
     const f3 Pp = rgb(a), Np = rgb(b);
@@ -477,6 +496,22 @@ __global__ __launch_bounds__(kBlock) void dn_upsample(uint32_t W, uint32_t H, ui
         else o = rgb(cv[min(max((int)(y / (uint32_t)S) - oy, 0), kUpN - 1) * kUpN + min(max((int)(x / (uint32_t)S) - ox, 0), kUpN - 1)]);
     }
     out[pix] = make_float4(o.x, o.y, o.z, 1.0f);
+}
+template <int S>
+__global__ __launch_bounds__(kBlock) void dn_upsample(uint32_t W, uint32_t H, uint32_t w, uint32_t h,
+                                                      const float4 *__restrict__ hg, const float4 *__restrict__ lg,
+                                                      const float4 *__restrict__ lc, float4 *__restrict__ out) {
+    __shared__ float4 g0[kUpN * kUpN], g1[kUpN * kUpN], cv[kUpN * kUpN];
+    dn_upsample_tile<S, false>(W, H, w, h, UpWin{}, hg, lg, lc, nullptr, out, g0, g1, cv);
+}
+// A band of the full-size frame (rows [win.Y0, win.Y1), where hg and out start) from a window of the small one.
+template <int S>
+__global__ __launch_bounds__(kBlock) void dn_upsample_win(uint32_t W, uint32_t H, uint32_t w, uint32_t h, const UpWin win,
+                                                          const float4 *__restrict__ hg, const float4 *__restrict__ lg,
+                                                          const float4 *__restrict__ lc, const float4 *__restrict__ lhalo,
+                                                          float4 *__restrict__ out) {
+    __shared__ float4 g0[kUpN * kUpN], g1[kUpN * kUpN], cv[kUpN * kUpN];
+    dn_upsample_tile<S, true>(W, H, w, h, win, hg, lg, lc, lhalo, out, g0, g1, cv);
 }
 
 // ---------------------------------------------------------------- launches
@@ -539,6 +574,17 @@ hipError_t launch_denoise_upsample(uint32_t s, uint32_t W, uint32_t H, const flo
     if (s == 2u) hipLaunchKernelGGL(dn_upsample<2>, g, bl, 0, st, W, H, w, h, guide_hi, guide_lo, color_lo, out);
     else if (s == 3u) hipLaunchKernelGGL(dn_upsample<3>, g, bl, 0, st, W, H, w, h, guide_hi, guide_lo, color_lo, out);
     else if (s == 4u) hipLaunchKernelGGL(dn_upsample<4>, g, bl, 0, st, W, H, w, h, guide_hi, guide_lo, color_lo, out);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_denoise_upsample_win(uint32_t s, uint32_t W, uint32_t H, const UpWin &win, const float4 *guide_hi,
+                                       const float4 *guide_lo, const float4 *color_lo, const float4 *halo_lo, float4 *out,
+                                       hipStream_t st) {
+    const dim3 g((W + kDnTile - 1) / kDnTile, (win.Y1 - win.Y0 + kDnTile - 1) / kDnTile), bl(kBlock);
+    const uint32_t w = W / s, h = H / s;
+    if (s == 2u) hipLaunchKernelGGL(dn_upsample_win<2>, g, bl, 0, st, W, H, w, h, win, guide_hi, guide_lo, color_lo, halo_lo, out);
+    else if (s == 3u) hipLaunchKernelGGL(dn_upsample_win<3>, g, bl, 0, st, W, H, w, h, win, guide_hi, guide_lo, color_lo, halo_lo, out);
+    else if (s == 4u) hipLaunchKernelGGL(dn_upsample_win<4>, g, bl, 0, st, W, H, w, h, win, guide_hi, guide_lo, color_lo, halo_lo, out);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -198,6 +198,12 @@ struct ptx_handle {
     bool dn_guide_swapped = false, drawn = false;
     hipStream_t dn_stream = nullptr;
     hipEvent_t ev_up_src = nullptr, ev_up_done = nullptr;
+    // ptx_upsample_bands: the halo rows of guide records the last denoise left around this band's (a
+    // small band's window: its neighbours' rows are read from there), and, on a full-size band, the
+    // neighbours' first / last 2 rows of the small denoised image as each call receives them (rows
+    // above, then rows below; allocated by the first call that has any)
+    uint32_t dn_guide_top = 0, dn_guide_bot = 0;
+    DevBuf d_up_halo;
     // the rows [begin, end) of the ranks above and below, as ptx_comm_init's neighbour check received them
     uint32_t nb_rows[2][2] = {{0, 0}, {0, 0}};
     int present_src = PTX_BUF_ACCUM;
@@ -282,6 +288,19 @@ int denoise_alloc(ptx_handle *h, const DnCall &c);
 // a later stage still reads, and the step to the next call's state
 int denoise_front(ptx_handle *h, const DnCall &c, DnBand &b);
 int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b);
+// The upsampler's host side (ptx_api.cpp), shared by ptx_upsample and ptx_upsample_bands (ptx_comm.cpp);
+// refusals go to `err`'s message.  Parameters in range; what a pair must share (pipelines with a
+// G-buffer, device, a denoised image and a G-buffer, the scale s, camera, scene); hi's guide records and
+// output (a band's in the layout of denoise_alloc) and, with halo rows, the buffer they are received in
+int upsample_params(ptx_handle *err, const ptx_upsample_params *p, float &sigma_plane, const char *what);
+int upsample_pair_check(ptx_handle *err, ptx_handle *hi, ptx_handle *lo, uint32_t &s, const char *what);
+int upsample_alloc(ptx_handle *hi, uint32_t halo_rows, uint32_t w);
+// ev_up_src at the tail of lo's last denoise; the two launches on hi's stream (lo's window: its rows
+// and `top` / `bot` of its neighbours'); ev_up_done behind them; every stream of lo waits for hi's
+int upsample_source(ptx_handle *err, ptx_handle *lo);
+hipError_t upsample_launch(ptx_handle *hi, ptx_handle *lo, uint32_t s, float sigma_plane, uint32_t top, uint32_t bot);
+int upsample_done(ptx_handle *err, ptx_handle *hi);
+int upsample_release(ptx_handle *err, ptx_handle *lo, ptx_handle *hi);
 // ptx_comm.cpp: a frame of a band handle that owns a communicator; a band frame without the
 // exchange (PTX_FLAG_HALO_SKIP, timing only); the communicator's teardown
 int render_band_nccl(ptx_handle *h);

@@ -78,6 +78,16 @@ hipError_t launch_denoise_variance_moments(uint32_t W, const DnWin &win, const f
 // `guide_hi` (s: 2, 3 or 4)
 hipError_t launch_denoise_upsample(uint32_t s, uint32_t W, uint32_t H, const float4 *guide_hi, const float4 *guide_lo,
                                    const float4 *color_lo, float4 *out, hipStream_t st);
+// ptx_upsample_bands: rows [Y0, Y1) of the W x H frame (guide_hi and out start at row Y0) from a row
+// window of the small frame: `rows` rows from its row y0 on, where guide_lo starts; the window's rows
+// [o0, o1) are color_lo's (a band's own rows), the rows above and then the rows below them halo_lo's.
+struct UpWin {
+    uint32_t y0, rows, o0, o1;
+    uint32_t Y0, Y1;
+};
+hipError_t launch_denoise_upsample_win(uint32_t s, uint32_t W, uint32_t H, const UpWin &win, const float4 *guide_hi,
+                                       const float4 *guide_lo, const float4 *color_lo, const float4 *halo_lo, float4 *out,
+                                       hipStream_t st);
 
 // closest-hit queries for a ray array (ptx_kernels.hip)
 hipError_t launch_trace_rays(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,

@@ -291,6 +291,24 @@ class Renderer:
                 flat[row:row + r.band_rows] = r.read_denoised()
                 row += r.band_rows
 
+    @staticmethod
+    def upsample_bands(his, los, sigma_plane: float = 0.0) -> None:
+        """Upsample over band pairs of this process (ptx_upsample_bands): los[i] is a band of the small
+        frame after denoise_bands, his[i] the band of s times its rows of the full-size frame on the same
+        device, with a G-buffer; each pair reads 2 rows of its neighbours' denoised images, brought on the
+        device (the small bands' communicators, or peer copies), which gives the whole-image Upsample's
+        result on its rows.  read_denoised works per full-size band."""
+        assert len(his) == len(los)
+        lib = N.load()
+        a = (ctypes.c_void_p * len(his))(*[r._h.value for r in his])
+        b = (ctypes.c_void_p * len(los))(*[r._h.value for r in los])
+        p = N.PtxUpsampleParams(sigma_plane=float(sigma_plane))
+        rc = lib.ptx_upsample_bands(a, b, len(his), ctypes.byref(p))
+        if rc != N.PTX_OK:
+            msgs = [lib.ptx_last_error(r._h) for r in list(his) + list(los)]
+            raise N.PtxError(f"ptx_upsample_bands failed ({rc}): "
+                             + "; ".join(m.decode(errors="replace") for m in msgs if m))
+
     def denoise_clips(self) -> int:
         """Pixels of this band's temporal denoise_bands calls (since the last reset_stats) with a history
         candidate inside the image but outside the rows the band's state covered: not taken.  0 on every

@@ -7,6 +7,7 @@
     python tools/denoise_time.py --temporal [--yaw-step DEG]   # the temporal mode (both forms above take it too)
     python tools/denoise_time.py --bands 8 --width 3840 --height 2160 [--temporal]   # the frame split into row bands
     python tools/denoise_time.py --upsample 2           # ptx_upsample, 960x540 -> 1920x1080 (--no-events / --trace take it too)
+    python tools/denoise_time.py --bands 8 --upsample 2 --width 3840 --height 2160   # ptx_upsample_bands, 8 pairs
     python tools/denoise_time.py --displayed-frame [--upsample 2]   # ms per displayed frame under a yawing camera
 
 The whole call is timed with device events around it on the handle's stream (a torch stream set
@@ -28,6 +29,10 @@ taken with the host clock.
 --upsample S times ptx_upsample the same way (events around the call on the full-size handle's stream):
 a handle of 1/S the size renders --frames frames and denoises once, the full-size handle runs one
 G-buffer pass; --width / --height are the full size.
+--bands N --upsample S times ptx_upsample_bands on N equal pairs on this GPU (peer copies) the way
+--bands times ptx_denoise_bands, against the whole-image ptx_upsample of the same frame on the same
+build: the sum of the bands' kernel times and device events around the call with every full-size
+handle on one stream, and the host's time from the call to its completion on the handles' own streams.
 --displayed-frame times what a host does per displayed frame while the camera moves (it yaws by
 --yaw-step and the frame index restarts before every frame), with the host clock from the first call
 to the completion of the last: a full-size frame + ptx_denoise, or with --upsample S a frame +
@@ -355,6 +360,107 @@ def measure_bands(args):
     return out
 
 
+def measure_upsample_bands(args):
+    """ptx_upsample_bands on --bands equal pairs on this GPU (peer copies) against the whole-image
+    ptx_upsample of the same frame on the same build."""
+    import time
+
+    import torch
+    from pathtracerdemo_amd import _native as N
+    from pathtracerdemo_amd.renderer import Renderer
+    from pathtracerdemo_amd.scene.world import compile_scene
+    s, W, H, n = args.upsample, args.width, args.height, args.iterations
+    assert W % s == 0 and H % s == 0
+    w, h = W // s, H // s
+    cs = compile_scene(args.scene)
+    cuts = [h * i // args.bands for i in range(args.bands + 1)]
+
+    def make(ww, hh, a=0, b=0):
+        r = Renderer(ww, hh, device=0, pipeline=args.pipeline, row_begin=a, row_end=b, time_launches=True)
+        r.Initialize(cs)
+        return r
+
+    one, bands = make(w, h), [make(w, h, a, b) for a, b in zip(cuts, cuts[1:])]
+    for _ in range(args.frames):
+        for r in [one] + bands:
+            r.Update()
+        one.Render()
+        Renderer.render_bands(bands)
+    one.Denoise(iterations=n)
+    Renderer.denoise_bands(bands, iterations=n)
+    hi_one, his = make(W, H), [make(W, H, s * a, s * b) for a, b in zip(cuts, cuts[1:])]
+    for r in [hi_one] + his:
+        r.Update()
+        r.run_pass(N.PTX_PASS_GBUFFER)
+    for r in [one, hi_one] + bands + his:
+        r.synchronize()
+
+    def spent(rs):
+        return sum(r.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE] for r in rs)
+
+    def mmm(v):
+        return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+
+    def timed_calls(stream=None):
+        """Per call: kernel sums and the host's call-to-completion time of the whole image and of the bands;
+        with a stream (every full-size handle runs on it) also device events around each call."""
+        ks_whole, ks_split, wall_whole, wall_split, ev_whole, ev_split = [], [], [], [], [], []
+        for i in range(args.warmup + args.calls):
+            k0, k1 = spent([hi_one]), spent(his)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if stream else None
+            t0 = time.perf_counter()
+            if ev:
+                ev[0].record(stream)
+            hi_one.Upsample(one)
+            if ev:
+                ev[1].record(stream)
+            hi_one.synchronize()
+            t1 = time.perf_counter()
+            if ev:
+                ev[2].record(stream)
+            Renderer.upsample_bands(his, bands)
+            if ev:
+                ev[3].record(stream)
+            for r in his:
+                r.synchronize()
+            t2 = time.perf_counter()
+            if i >= args.warmup:
+                ks_whole.append(spent([hi_one]) - k0)
+                ks_split.append(spent(his) - k1)
+                wall_whole.append((t1 - t0) * 1e3)
+                wall_split.append((t2 - t1) * 1e3)
+                if ev:
+                    ev[3].synchronize()
+                    ev_whole.append(ev[0].elapsed_time(ev[1]))
+                    ev_split.append(ev[2].elapsed_time(ev[3]))
+        return ks_whole, ks_split, wall_whole, wall_split, ev_whole, ev_split
+
+    # the handles' own streams: what a host sees (the bands' kernels share the GPU)
+    _, overlapped, wall_whole, wall_split, _, _ = timed_calls()
+    # one stream for every full-size handle: each launch's events time that kernel alone, and device
+    # events around a call span exactly its copies and kernels
+    shared = torch.cuda.Stream()
+    for r in [hi_one] + his:
+        r.set_stream(shared.cuda_stream)
+    ks_whole, ks_split, _, _, ev_whole, ev_split = timed_calls(shared)
+    same = all((b.read_denoised().view("uint32") == hi_one.read_denoised()[s * a:s * z].view("uint32")).all()
+               for b, a, z in zip(his, cuts, cuts[1:]))
+    out = {"what": "ptx_upsample_bands", "scale": s, "width": W, "height": H, "scene": args.scene, "pipeline": args.pipeline,
+           "iterations": n, "bands": args.bands, "calls": args.calls, "warmup": args.warmup, "equals_whole_image": bool(same),
+           "whole_image_kernel_ms": mmm(ks_whole), "bands_kernel_ms_sum": mmm(ks_split),
+           "kernel_ratio": round(statistics.median(ks_split) / statistics.median(ks_whole), 3),
+           "bands_kernel_ms_sum_on_own_streams_overlapped": mmm(overlapped),
+           "events_around_call_ms_one_stream": {"whole_image": mmm(ev_whole), "bands": mmm(ev_split)},
+           "call_ratio": round(statistics.median(ev_split) / statistics.median(ev_whole), 3),
+           "host_ms_call_to_completion": {"whole_image": mmm(wall_whole), "bands_own_streams": mmm(wall_split)},
+           "halo_bytes_received_per_band": [[(2 if a else 0) * w * 16, (2 if z != h else 0) * w * 16] for a, z in zip(cuts, cuts[1:])]}
+    for r in [hi_one] + his:
+        r.set_stream(None)
+    for r in [one, hi_one] + bands + his:
+        r.close()
+    return out
+
+
 def from_trace(args):
     """Median duration of each kernel of a call (guide, [temporal,] variance, iteration 0..n-1) over the traced
     calls of the last handle (the TIME_LAUNCHES one), warm-up calls dropped."""
@@ -407,7 +513,7 @@ def main():
     if args.displayed_frame:
         out = measure_displayed_frame(args)
     elif args.upsample:
-        out = upsample_from_trace(args) if args.trace else measure_upsample(args)
+        out = upsample_from_trace(args) if args.trace else measure_upsample_bands(args) if args.bands else measure_upsample(args)
     else:
         out = from_trace(args) if args.trace else measure_bands(args) if args.bands else measure(args)
     print(json.dumps(out))
