@@ -78,7 +78,8 @@ extern "C" {
 #define PTX_STAT_PASS_GROUP 10 /* ptx_run_passes calls of the wavefront kernels          */
 #define PTX_STAT_FINAL_FUSED 11 /* count only (no time): PT_4 passes of the reuse pipeline that
                                    walked their replays inside their one logic launch
-                                   (wfinal_one), so none of their queries reached trace_queue */
+                                   (wfinal_one, or wfinal_replay behind a spatial pass that shaded),
+                                   so none of their queries reached trace_queue */
 #define PTX_STAT_DENOISE 12  /* launches of the denoiser's kernels (ms with PTX_FLAG_TIME_LAUNCHES) */
 
 /* buffers for ptx_read_buffer / ptx_write_buffer / ptx_device_pointer */
@@ -93,6 +94,11 @@ extern "C" {
  * candidate inside the image but outside the rows the band's state covers (not taken; see
  * ptx_denoise_bands); zeroed by ptx_reset_stats */
 #define PTX_COUNTER_DENOISE_CLIP 7
+/* PTX_BUF_COUNTERS word 18 (the next free one: 8..17 are diagnostics), every build: pixels of the
+ * reuse pipeline whose spatial output carried no contribution when the spatial pass shaded them
+ * itself (a spatial pass directly followed by PTX_PASS_FINAL in one ptx_render / ptx_run_passes
+ * sequence), so PT_4 replayed their paths; zeroed by ptx_reset_stats */
+#define PTX_COUNTER_REPLAY 18
 #define PTX_BUF_RESERVOIR_HIST 4 /* band_h * W * 32 u32: spatial output = Final's input and the
                                     next frame's temporal history (reuse pipeline)           */
 #define PTX_BUF_DIRECT 5     /* band_h * W * 4 f32: direct light of the GI init pass (GI pipeline) */

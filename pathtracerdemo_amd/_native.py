@@ -31,6 +31,7 @@ PTX_BUF_FRAME_COLOR = 7  # the frame's own radiance (PTX_FLAG_FRAME_COLOR handle
 PTX_BUF_DENOISE_HISTORY = 8  # {C.rgb, n} of the last temporal ptx_denoise (read-only)
 PTX_COUNTER_MOTION_CLIP = 6 # word of PTX_BUF_COUNTERS: pixels a band could not reproject (ptx.h)
 PTX_COUNTER_DENOISE_CLIP = 7  # word of PTX_BUF_COUNTERS: pixels with a history candidate past a band's denoiser state
+PTX_COUNTER_REPLAY = 18  # word of PTX_BUF_COUNTERS: pixels PT_4 replayed behind a shading spatial combine
 PTX_FLAG_COUNT_WORK = 1
 PTX_FLAG_SIMPLE_KERNELS = 2
 PTX_FLAGS_RETIRED = 12  # the removed persistent-lane / tiled A/B variants: ptx_create rejects them

@@ -413,6 +413,10 @@ constexpr int CNT_CULL_MISS = 5;
 // pixel gets no history, where the whole image would have had it (0 keeps bands bit-identical)
 constexpr int CNT_MOTION_CLIP = 6;
 constexpr int CNT_DENOISE_CLIP = 7;  // PTX_COUNTER_DENOISE_CLIP: dn_temporal's clipped pixels (ptx_denoise_bands)
+// PTX_COUNTER_REPLAY: pixels a shading spatial combine listed for PT_4's replay (the word after
+// the SIMD-utilisation profile's 8 .. 8 + 2 * PROF_REGIONS - 1)
+constexpr int CNT_REPLAY = 18;
+static_assert(CNT_REPLAY >= 8 + 2 * PROF_REGIONS && CNT_REPLAY < kCounterWords, "a free counter word");
 __device__ __forceinline__ bool inst_may_hit(const Inst &I, f3 o, f3 winv, float omax, float vy) {
     if (!(I.wpad >= 0.0f)) return true;
     const float p = I.wpad + I.wscale * omax;

@@ -60,6 +60,10 @@ struct ptx_handle {
     // shared by the frames in flight: accumulation, counters; reuse pipeline: spatial output /
     // history, the spatial pass's shift-job state and results
     DevBuf d_accum, d_counters, d_hist, d_jstate, d_jres;
+    // DI reuse: the replay lists of a spatial combine that shades (ReuseArgs::fuse_final) -- one
+    // length per queue slot, then seg_px pixel indices per slot; queue memory like the wave
+    // buffers (sized by wave_buffers), shared by the frames in flight like d_hist
+    DevBuf d_replay;
     // reservoir size in uint4 (8: the reference's 128-byte Reservoir; 4: the GI reservoir)
     uint32_t res_u4 = 8;
     // the caller holds a device pointer to a G-buffer (ptx_device_pointer) and may write it at
@@ -112,6 +116,11 @@ struct ptx_handle {
         // latency-bound traces overlap another's ALU-bound shading
         hipStream_t sub[kMaxSplit] = {nullptr, nullptr, nullptr, nullptr};
         hipEvent_t ev_fork = nullptr, ev_join[kMaxSplit] = {nullptr, nullptr, nullptr, nullptr};
+        // a pipelined DI reuse frame's back chain (launch_back_chain), per launch sequence: its
+        // temporal combine is enqueued (the other sequences' spatial starts gather across the
+        // cut); its spatial combine is enqueued -- the history's hand-off to the next frame
+        hipEvent_t ev_tc[kMaxSplit] = {nullptr, nullptr, nullptr, nullptr};
+        hipEvent_t ev_hand[kMaxSplit] = {nullptr, nullptr, nullptr, nullptr};
         // the wave state holds the PT_1 pass of the reservoirs in `res` (enqueued, nothing since
         // rewrote them): the reuse temporal pass may read its path hits instead of re-tracing
         bool init_state_valid = false;
@@ -132,6 +141,12 @@ struct ptx_handle {
     FrameCtx &cur() { return ctx[ctx_idx]; }
     const FrameCtx &cur() const { return ctx[ctx_idx]; }
     hipEvent_t ev_prev = nullptr;
+    // The last thing enqueued on this handle was a pipelined DI reuse frame whose back chain
+    // recorded hand_n hand-off events (ctx[hand_ctx].ev_hand): the next such frame's temporal
+    // combine waits for those instead of ev_prev (the whole frame, PT_4's replay and the join
+    // included).  Everything else that launches passes clears it (launch_wave_parts, timed_launch):
+    // what it enqueues is ordered by ev_prev alone, as every other user of ev_prev is.
+    int hand_ctx = 0, hand_n = 0;
     // multi-GPU (ptx_comm.cpp): the RCCL communicator this handle owns (ncclComm_t), its
     // rank and world; the halo exchange stream and its fork / done events
     void *comm = nullptr;

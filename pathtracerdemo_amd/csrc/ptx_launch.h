@@ -158,6 +158,10 @@ hipError_t wave_init_round(const Scene &sc, const WaveBufs &w, int round, const 
 // PT_4 of the reuse pipeline in one launch, replays walked inline (scene tables in LDS)
 hipError_t wave_final_one(const Scene &sc, const WaveBufs &w, const uint4 *gbuf, const uint4 *reservoir, float4 *accum,
                           uint32_t depth, hipStream_t s);
+// PT_4 behind a spatial combine that shaded (ReuseArgs::fuse_final): wfinal_one over each
+// segment's replay list only; a workgroup whose list is empty leaves before staging the tables
+hipError_t wave_final_replay(const Scene &sc, const WaveBufs &w, const uint4 *gbuf, const uint4 *reservoir, float4 *accum,
+                             const uint32_t *replay, uint32_t *replay_cnt, uint32_t depth, hipStream_t s);
 hipError_t wave_final_round(const Scene &sc, const WaveBufs &w, int round, const uint4 *gbuf, const uint4 *reservoir,
                             float4 *accum, hipStream_t s);
 hipError_t wave_gbuffer(const Scene &sc, const WaveBufs &w, uint4 *gbuf, uint32_t stack_depth, hipStream_t s);
@@ -206,6 +210,16 @@ struct ReuseArgs {
     const uint4 *psurf;
     int32_t prev_row_lo, prev_row_hi;
     unsigned long long *clip;  // nullptr: not counted
+    // spatial combine followed by PT_4 in one launch sequence: the combine does PT_4's per-pixel
+    // cases itself (wfinal_one's, with the values it holds: the same mix_color into accum and
+    // Scene::frame_color), and a pixel whose contribution is unknown -- the only kind PT_4 has to
+    // replay -- goes to its segment's replay list: replay[slot * seg_px ..] with its length in
+    // replay_cnt[slot] (slot = the segment's physical queue slot; wave_final_replay consumes the
+    // list and zeroes the length), the listed pixels counted in *replay_total
+    uint32_t fuse_final;
+    float4 *accum;
+    uint32_t *replay, *replay_cnt;
+    unsigned long long *replay_total;
 };
 // the motion temporal pass's jobs per pixel: the canonical sample at home, the reprojected
 // history sample here, the canonical sample in the previous frame's domain

@@ -441,8 +441,9 @@ __device__ __forceinline__ SelF stored_f(const uint4 *r) {
     const uint4 r6 = r[6], r7 = r[7];
     return SelF{r7.w == 1u, mk(asf(r6.z), asf(r6.w), asf(r7.z))};
 }
-__device__ __forceinline__ void write_reused(uint4 *out, const uint4 *src, float p_sel, float q_sel, SelF fs,
-                                             float w_sum, uint32_t C) {
+// Returns the sample's path length (word 23).
+__device__ __forceinline__ uint32_t write_reused(uint4 *out, const uint4 *src, float p_sel, float q_sel, SelF fs,
+                                                 float w_sum, uint32_t C) {
     // all loads before the stores: src may be out itself (temporal)
     uint4 a0 = src[0], a5 = src[5];
     const uint4 a1 = src[1], a2 = src[2], a3 = src[3], a4 = src[4];
@@ -454,6 +455,7 @@ __device__ __forceinline__ void write_reused(uint4 *out, const uint4 *src, float
     out[0] = a0; out[1] = a1; out[2] = a2; out[3] = a3; out[4] = a4; out[5] = a5;
     out[6] = make_uint4(asu(p_sel), asu(q_sel), fs.known ? asu(fs.f.x) : 0u, fs.known ? asu(fs.f.y) : 0u);
     out[7] = make_uint4(asu(p_sel > 0.0f ? w_sum / p_sel : 0.0f), C, fs.known ? asu(fs.f.z) : 0u, fs.known ? 1u : 0u);
+    return a5.w;
 }
 
 // The spatial pass's 16-byte neighbour summary of a reservoir (see wnbr_summary below).
@@ -1050,11 +1052,49 @@ __device__ __forceinline__ float neighbour_weight(const CombineCanon &c, float M
     return wn;
 }
 
+// ReuseArgs::fuse_final: PT_4's per-pixel cases (wfinal_one's, the same operations on the same
+// values) for the output reservoir just formed -- confidence C, the sample's length, its
+// contribution and UCW = w_sum / p_sel.  True: the contribution is unknown, PT_4 has to replay
+// the path (the pixel goes to the replay list).
+// hit = false: a pixel without a G-buffer hit gets the environment colour (pass C = 0).
+// t: mix_weight(sc); a: accum[pix], loaded by the caller (ahead of its stores, which the compiler
+// must assume may alias it).
+__device__ __forceinline__ bool shade_reused(const Scene &sc, const ReuseArgs &A, float t, float4 a, uint32_t pix,
+                                             bool hit, uint32_t C, uint32_t length, SelF fs, float ucw) {
+    const bool black = C == 0u || length < 2u;
+    if (hit && !black && !fs.known) return true;
+    // (mix_color's steps written as one path for the three cases: a branch per case has the
+    // compiler keep each case's constants in registers across the combine's loop, which costs
+    // the shuffle kernel its 8 waves per SIMD)
+    const f3 c = black ? mk(0.0f, 0.0f, 0.0f) : fs.f * ucw;
+    const float4 m = mixed_color(a, c, t);
+    A.accum[pix] = hit ? m : make_float4(ENV_C, ENV_C, ENV_C, 1.0f);
+    if (hit && sc.frame_color) sc.frame_color[pix] = make_float4(c.x, c.y, c.z, 1.0f);
+    return false;
+}
+// Append the wave's `replay` pixels to their segment's replay list: one ballot, one atomic per
+// wave that has any.  Every lane of the wave reaches it.
+__device__ __forceinline__ void replay_append(const ReuseArgs &A, const WaveBufs &w, uint32_t pj, bool replay,
+                                              uint32_t pix) {
+    const unsigned long long m = __ballot(replay);
+    if (m == 0ull) return;
+    const uint32_t n = (uint32_t)__popcll(m);
+    uint32_t at = 0u;
+    if (__lane_id() == (uint32_t)__builtin_ctzll(m)) {
+        at = atomicAdd(&A.replay_cnt[pj], n);
+        atomicAdd(A.replay_total, (unsigned long long)n);
+    }
+    at = (uint32_t)__shfl((int)at, __builtin_ctzll(m));
+    at += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (replay && at < w.seg_px) A.replay[(size_t)pj * w.seg_px + at] = pix;  // (a segment lists each pixel once)
+}
+
 // MT = the launch's neighbour count when it is a compile-time constant: every neighbour's
 // summary and job results are gathered up front (one memory round trip instead of 2 MT
 // dependent ones); MT = 0: any count, gathered per neighbour.
+// Returns shade_reused's answer (false without ReuseArgs::fuse_final).
 template <uint32_t MT>
-__device__ __forceinline__ void combine_pixel(const Scene &sc, const ReuseArgs &A, const WaveBufs &w, uint32_t x,
+__device__ __forceinline__ bool combine_pixel(const Scene &sc, const ReuseArgs &A, const WaveBufs &w, uint32_t x,
                                               uint32_t y, uint32_t pix) {
     uint4 *out = A.hist + 8u * (size_t)pix;
     const uint4 *rc = A.cur + 8u * (size_t)pix;
@@ -1137,7 +1177,9 @@ __device__ __forceinline__ void combine_pixel(const Scene &sc, const ReuseArgs &
             if (wrs_update(w_sum, wn, seed)) { src = nidx; p_sel = pf; q_sel = qf; f_sel = fj; }
         }
     }
-    write_reused(out, res_at(A.cur, src), p_sel, q_sel, f_sel, w_sum, Csum);
+    const uint32_t length = write_reused(out, res_at(A.cur, src), p_sel, q_sel, f_sel, w_sum, Csum);
+    return A.fuse_final && shade_reused(sc, A, mix_weight(sc), A.accum[pix], pix, true, Csum, length, f_sel,
+                                        p_sel > 0.0f ? w_sum / p_sel : 0.0f);
 }
 
 // The same combine for M = 3 with four lanes per pixel: lane 0 holds the canonical sample,
@@ -1154,6 +1196,9 @@ __global__ __launch_bounds__(WB) void wspatial_combine_shfl(Scene sc, WaveBufs w
     constexpr uint32_t M = 3u;
     const uint32_t j = w.seg_base + blockIdx.x, np = padded_pixels(sc);
     const uint32_t lane = __lane_id(), r = lane & 3u, base = lane & ~3u;
+    // (the frame's mix weight in a scalar register: as a vector value the compiler keeps it, its
+    // complement and a copy of each for packed math across the loop)
+    const float mix_t = asf((uint32_t)__builtin_amdgcn_readfirstlane((int)asu(mix_weight(sc))));
     for (uint32_t k = 0; k < w.seg_px; k += WB / kShflLanes) {  // workgroup-uniform
         // pixel k + threadIdx.x / 4 of the segment (seg_pixel's tile layout)
         const uint32_t off = k + (threadIdx.x >> 2), sl = off >> 6;
@@ -1214,24 +1259,41 @@ __global__ __launch_bounds__(WB) void wspatial_combine_shfl(Scene sc, WaveBufs w
         const float p_sel = sel ? __shfl(pf, base + sel) : c.pc, q_sel = sel ? __shfl(qf, base + sel) : c.qc;
         const float fx = __shfl(fj.f.x, base + sel), fy = __shfl(fj.f.y, base + sel), fz = __shfl(fj.f.z, base + sel);
         const bool fk = __shfl(fj.known ? 1 : 0, base + sel) != 0;
-        if (!inside) continue;
-        uint4 *out = A.hist + 8u * (size_t)pix;
-        if (!hit) {
-            out[2u * r] = make_uint4(0u, 0u, 0u, 0u);
-            out[2u * r + 1u] = make_uint4(0u, 0u, 0u, 0u);
-            continue;
+        // its path length (word 23 of the source reservoir): the canonical sample's own, a
+        // neighbour's from its summary
+        const uint32_t length = __shfl(r == 0u ? c5.w : nb.length, base + sel);
+        bool replay = false;
+        if (inside) {
+            uint4 *out = A.hist + 8u * (size_t)pix;
+            if (r < 3u) {  // words 8r .. 8r + 7 of the selected sample (zeros without a G-buffer hit)
+                uint4 a0 = make_uint4(0u, 0u, 0u, 0u), a1 = a0;
+                if (hit) {
+                    const uint4 *sv = res_at(A.cur, src);
+                    a0 = sv[2u * r];
+                    a1 = sv[2u * r + 1u];
+                }
+                out[2u * r] = a0;
+                out[2u * r + 1u] = a1;
+            } else {
+                uint4 o6 = make_uint4(0u, 0u, 0u, 0u), o7 = o6;
+                SelF fs{false, mk(0.0f, 0.0f, 0.0f)};
+                float ucw = 0.0f;
+                // (the accumulated texel with the branch's other loads, not behind its stores)
+                const float4 acc = A.fuse_final ? A.accum[pix] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (hit) {
+                    fs = sel ? SelF{fk, mk(fx, fy, fz)} : stored_f(A.cur + 8u * (size_t)pix);
+                    ucw = p_sel > 0.0f ? w_sum / p_sel : 0.0f;
+                    o6 = make_uint4(asu(p_sel), asu(q_sel), fs.known ? asu(fs.f.x) : 0u, fs.known ? asu(fs.f.y) : 0u);
+                    o7 = make_uint4(asu(ucw), Csum, fs.known ? asu(fs.f.z) : 0u, fs.known ? 1u : 0u);
+                }
+                out[6] = o6;
+                out[7] = o7;
+                float t = mix_t;
+                asm volatile("" : "+v"(t));  // (nothing derived from it is computed ahead of the loop)
+                if (A.fuse_final) replay = shade_reused(sc, A, t, acc, pix, hit, hit ? Csum : 0u, length, fs, ucw);
+            }
         }
-        if (r < 3u) {  // words 8r .. 8r + 7 of the selected sample
-            const uint4 *sv = res_at(A.cur, src);
-            const uint4 a0 = sv[2u * r], a1 = sv[2u * r + 1u];
-            out[2u * r] = a0;
-            out[2u * r + 1u] = a1;
-        } else {
-            const SelF fs = sel ? SelF{fk, mk(fx, fy, fz)} : stored_f(A.cur + 8u * (size_t)pix);
-            out[6] = make_uint4(asu(p_sel), asu(q_sel), fs.known ? asu(fs.f.x) : 0u, fs.known ? asu(fs.f.y) : 0u);
-            out[7] = make_uint4(asu(p_sel > 0.0f ? w_sum / p_sel : 0.0f), Csum, fs.known ? asu(fs.f.z) : 0u,
-                                fs.known ? 1u : 0u);
-        }
+        if (A.fuse_final) replay_append(A, w, w.seg_phys + j, replay, pix);  // (wave-uniform: a kernel argument)
     }
 }
 
@@ -1240,16 +1302,23 @@ __global__ __launch_bounds__(WB) void wspatial_combine(Scene sc, WaveBufs w, Reu
     const uint32_t j = w.seg_base + blockIdx.x, np = padded_pixels(sc);
     for (uint32_t k = 0; k < w.seg_px; k += WB) {
         const uint32_t q = seg_pixel(w, j, k);
-        uint32_t x, y;
-        if (q >= np || !tile_xy(sc, q, x, y)) continue;
-        const uint32_t pix = (y - sc.row_begin) * sc.width + x;
-        if (!gdecode(A.gbuf[pix]).valid) {
-            uint4 *out = A.hist + 8u * (size_t)pix;
-            for (int t = 0; t < 8; ++t) out[t] = make_uint4(0u, 0u, 0u, 0u);
-            continue;
+        uint32_t x, y, pix = 0u;
+        bool replay = false;
+        if (q < np && tile_xy(sc, q, x, y)) {
+            pix = (y - sc.row_begin) * sc.width + x;
+            if (!gdecode(A.gbuf[pix]).valid) {
+                uint4 *out = A.hist + 8u * (size_t)pix;
+                for (int t = 0; t < 8; ++t) out[t] = make_uint4(0u, 0u, 0u, 0u);
+                if (A.fuse_final)  // (the environment colour)
+                    (void)shade_reused(sc, A, mix_weight(sc), A.accum[pix], pix, false, 0u, 0u,
+                                       SelF{false, mk(0.0f, 0.0f, 0.0f)}, 0.0f);
+            } else if (A.neighbors == 3u) {
+                replay = combine_pixel<3>(sc, A, w, x, y, pix);
+            } else {
+                replay = combine_pixel<0>(sc, A, w, x, y, pix);
+            }
         }
-        if (A.neighbors == 3u) combine_pixel<3>(sc, A, w, x, y, pix);
-        else combine_pixel<0>(sc, A, w, x, y, pix);
+        if (A.fuse_final) replay_append(A, w, w.seg_phys + j, replay, pix);  // (wave-uniform: a kernel argument)
     }
 }
 

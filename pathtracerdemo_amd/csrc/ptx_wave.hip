@@ -933,6 +933,57 @@ __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(LOGIC_WAVES,
     job_seg_end(w, g, JL);
 }
 
+// wfinal_one's replay of a wave's live pixels (`active`, state `s`, reservoir `resv`): each emits
+// its ray into its own queue slot, the whole wave walks it, the step consumes it.
+template <bool FLAT>
+__device__ __forceinline__ void wfinal_walk(const Scene &sc, const LdsTables &T, const PassEps &eps, uint32_t *stack,
+                                            const CoopLds &coop, float4 *rays, float4 *res, uint32_t slot,
+                                            const uint4 *resv, float4 *accum, uint32_t pix, bool active, WFinal &s) {
+    // (wave-uniform) one replayed vertex per iteration, as many as the queued form's trace
+    // rounds: a path needing more is dropped there, so it is here
+    for (uint32_t it = 0u; it < (uint32_t)kWaveRoundsFinal; ++it) {
+        if (wballot(active) == 0ull) break;
+        if (active) {  // wfinal_emit, into this thread's slot
+            const f3 V = normalize(s.prev - s.cur.pos);
+            if (s.i + 1u < s.length) {
+                uint32_t seed = s.i == 1u ? resv[0].x : s.seed1;
+                uint32_t lobe;
+                const f3 dir = sample_bsdf(seed, s.cur, V, lobe);
+                s.phase = 0u;
+                put_ray(rays, slot, s.cur.pos, dir, -1.0f, Q_CLOSEST);
+            } else {
+                const LightSample XL = load_xl(resv);
+                const f3 L = direction_to_light(s.cur, XL);
+                s.f = s.f * (bsdf(s.cur, L, V) * fabsf(dot(s.cur.nrm, L)));
+                const f3 Le = l_emit<true>(XL, s.cur);
+                s.phase = 1u;
+                const float dist = length(XL.pos - s.cur.pos);
+                put_ray(rays, slot, s.cur.pos, (XL.pos - s.cur.pos) / dist, dist, Q_VIS);
+                res[2u * slot] = make_float4(0.0f, Le.x, Le.y, Le.z);
+            }
+        }
+        // the traversal kernel's walk, every lane of the wave (idle ones with a NaN bound)
+        trace_batch<false, false, false, true, FLAT>(sc, T.subs, T.insts, eps, stack, coop, res, rays, 0u, slot, active);
+        if (active) {  // wfinal_step
+            if (s.phase == 0u) {
+                const Hit h = get_hit(res, slot);
+                const Surface next = h.valid ? surface_at(sc, h.s, h.pos) : get_surface(sc, h.s);
+                const f3 V = normalize(s.prev - s.cur.pos);
+                const f3 L = normalize(next.pos - s.cur.pos);
+                s.f = s.f * (bsdf(s.cur, L, V) * fabsf(dot(s.cur.nrm, L)));
+                s.prev = s.cur.pos;
+                s.cur = next;
+                s.i += 1u;
+            } else {
+                const float4 a = res[2u * slot];
+                s.f = s.f * (mk(a.y, a.z, a.w) * a.x);
+                mix_color(sc, accum, pix, s.f * s.ucw);
+                active = false;
+            }
+        }
+    }
+}
+
 // PT_4 of the reuse pipeline as ONE launch.  Its pixels almost all carry their sample's stored
 // contribution (the spatial combine's), so wfinal_start shades them and the three {trace, step}
 // rounds after it replay next to nothing -- six dependent launches of ~10 us dispatch gap each on
@@ -984,50 +1035,50 @@ void wfinal_one(Scene sc, WaveBufs w, const uint4 *gbuf, const uint4 *reservoir,
                 }
             }
         }
-        const uint4 *resv = reservoir + 8u * (size_t)pix;
-        // (wave-uniform) one replayed vertex per iteration, as many as the queued form's trace
-        // rounds: a path needing more is dropped there, so it is here
-        for (uint32_t it = 0u; it < (uint32_t)kWaveRoundsFinal; ++it) {
-            if (wballot(active) == 0ull) break;
-            if (active) {  // wfinal_emit, into this thread's slot
-                const f3 V = normalize(s.prev - s.cur.pos);
-                if (s.i + 1u < s.length) {
-                    uint32_t seed = s.i == 1u ? resv[0].x : s.seed1;
-                    uint32_t lobe;
-                    const f3 dir = sample_bsdf(seed, s.cur, V, lobe);
-                    s.phase = 0u;
-                    put_ray(rays, slot, s.cur.pos, dir, -1.0f, Q_CLOSEST);
-                } else {
-                    const LightSample XL = load_xl(resv);
-                    const f3 L = direction_to_light(s.cur, XL);
-                    s.f = s.f * (bsdf(s.cur, L, V) * fabsf(dot(s.cur.nrm, L)));
-                    const f3 Le = l_emit<true>(XL, s.cur);
-                    s.phase = 1u;
-                    const float dist = length(XL.pos - s.cur.pos);
-                    put_ray(rays, slot, s.cur.pos, (XL.pos - s.cur.pos) / dist, dist, Q_VIS);
-                    res[2u * slot] = make_float4(0.0f, Le.x, Le.y, Le.z);
-                }
-            }
-            // the traversal kernel's walk, every lane of the wave (idle ones with a NaN bound)
-            trace_batch<false, false, false, true, FLAT>(sc, T.subs, T.insts, eps, stack, coop, res, rays, 0u, slot, active);
-            if (active) {  // wfinal_step
-                if (s.phase == 0u) {
-                    const Hit h = get_hit(res, slot);
-                    const Surface next = h.valid ? surface_at(sc, h.s, h.pos) : get_surface(sc, h.s);
-                    const f3 V = normalize(s.prev - s.cur.pos);
-                    const f3 L = normalize(next.pos - s.cur.pos);
-                    s.f = s.f * (bsdf(s.cur, L, V) * fabsf(dot(s.cur.nrm, L)));
-                    s.prev = s.cur.pos;
-                    s.cur = next;
-                    s.i += 1u;
-                } else {
-                    const float4 a = res[2u * slot];
-                    s.f = s.f * (mk(a.y, a.z, a.w) * a.x);
-                    mix_color(sc, accum, pix, s.f * s.ucw);
-                    active = false;
-                }
-            }
+        wfinal_walk<FLAT>(sc, T, eps, stack, coop, rays, res, slot, reservoir + 8u * (size_t)pix, accum, pix, active, s);
+    }
+}
+
+// PT_4 behind a fused spatial combine (ReuseArgs::fuse_final): that launch shaded every pixel
+// whose contribution it knew and listed the others per segment; this one replays the listed
+// pixels with wfinal_one's code (the same rays, results and arithmetic per pixel; the list's
+// order decides nothing), and zeroes the count it consumed.  An empty list -- practically every
+// segment of every natural frame -- costs its workgroup one load.
+template <bool FLAT>
+__global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(2, 8)))
+void wfinal_replay(Scene sc, WaveBufs w, const uint4 *gbuf, const uint4 *reservoir, float4 *accum,
+                   const uint32_t *replay, uint32_t *replay_cnt, PassEps eps) {
+    PTX_WAVE_TIMER(sc, KID_FINAL_START | (w.seg_base ? 0x80u : 0u));
+    extern __shared__ __attribute__((aligned(16))) uint32_t wstack[];
+    __shared__ unsigned long long c_key[WB];
+    __shared__ uint32_t c_mark[WB];
+    const uint32_t pj = w.seg_phys + w.seg_base + blockIdx.x;
+    const uint32_t n = min(replay_cnt[pj], w.seg_px);  // (workgroup-uniform)
+    if (n == 0u) return;
+    const LdsTables T = stage_tables(sc, wstack);
+    __syncthreads();  // every thread has read the count
+    if (threadIdx.x == 0u) replay_cnt[pj] = 0u;
+    uint32_t *stack = wstack + tables_lds_bytes(sc) / 4u + threadIdx.x;
+    const CoopLds coop{c_key + (threadIdx.x & ~63u), c_mark + (threadIdx.x & ~63u)};
+    float4 *rays = w.rays + 2u * (size_t)pj * w.ray_stride, *res = w.res[0] + 2u * (size_t)pj * w.ray_stride;
+    const uint32_t slot = threadIdx.x;
+    const uint32_t *list = replay + (size_t)pj * w.seg_px;
+    for (uint32_t k = 0; k < n; k += WB) {  // (workgroup-uniform)
+        const uint32_t e = k + threadIdx.x < n ? list[k + threadIdx.x] : w.npix;
+        const bool active = e < w.npix;  // (a band pixel, whatever the list holds)
+        const uint32_t pix = active ? e : 0u;
+        WFinal s;
+        if (active) {  // wfinal_one's replay case
+            const uint4 *rv = reservoir + 8u * (size_t)pix;
+            s.length = rv[5].w;
+            s.seed1 = rv[0].y;
+            s.ucw = asf(rv[7].x);
+            s.prev = x0_of(sc, pix % sc.width, sc.row_begin + pix / sc.width);
+            s.cur = get_surface(sc, gdecode(gbuf[pix]));
+            s.f = mk(1.0f, 1.0f, 1.0f);
+            s.i = 1u;
         }
+        wfinal_walk<FLAT>(sc, T, eps, stack, coop, rays, res, slot, reservoir + 8u * (size_t)pix, accum, pix, active, s);
     }
 }
 
@@ -1359,6 +1410,20 @@ hipError_t wave_final_one(const Scene &sc, const WaveBufs &w, const uint4 *gbuf,
         hipLaunchKernelGGL(wfinal_one<true>, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir, accum, eps);
     else
         hipLaunchKernelGGL(wfinal_one<false>, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir, accum, eps);
+    return hipGetLastError();
+}
+
+hipError_t wave_final_replay(const Scene &sc, const WaveBufs &w, const uint4 *gbuf, const uint4 *reservoir, float4 *accum,
+                             const uint32_t *replay, uint32_t *replay_cnt, uint32_t depth, hipStream_t s) {
+    const PassEps eps{1e-4f, 1e-8f};  // (wave_final_one's)
+    const size_t lds = tables_lds_bytes(sc) + stack_lds_bytes(depth);
+    static const uint32_t flat_min = (uint32_t)ab_knob("FLAT_MIN_INST", (int)kFlatMinInstances);
+    if (PTX_FLAT_INST && sc.n_inst >= flat_min)
+        hipLaunchKernelGGL(wfinal_replay<true>, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir, accum, replay,
+                           replay_cnt, eps);
+    else
+        hipLaunchKernelGGL(wfinal_replay<false>, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir, accum, replay,
+                           replay_cnt, eps);
     return hipGetLastError();
 }
 

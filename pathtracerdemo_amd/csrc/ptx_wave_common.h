@@ -157,10 +157,13 @@ __device__ __forceinline__ Compact gdecode(uint4 g) {
 __device__ __forceinline__ uint4 gencode(const Compact &s) {
     return make_uint4((s.valid << 31) | (s.inst << 16) | s.mat, s.prim, asu(s.bu), asu(s.bv));
 }
+// WriteColor, PT_4:599-606: the frame's weight, and a texel mixed with the frame's colour
+__device__ __forceinline__ float mix_weight(const Scene &sc) { return 1.0f / (float)(sc.U[U_FRAME] + 1u); }
+__device__ __forceinline__ float4 mixed_color(float4 a, f3 c, float t) {
+    return make_float4(mixf(a.x, c.x, t), mixf(a.y, c.y, t), mixf(a.z, c.z, t), 1.0f);
+}
 __device__ __forceinline__ void mix_color(const Scene &sc, float4 *accum, uint32_t i, f3 c) {
-    float t = 1.0f / (float)(sc.U[U_FRAME] + 1u);  // WriteColor, PT_4:599-606
-    float4 a = accum[i];
-    accum[i] = make_float4(mixf(a.x, c.x, t), mixf(a.y, c.y, t), mixf(a.z, c.z, t), 1.0f);
+    accum[i] = mixed_color(accum[i], c, mix_weight(sc));
     if (sc.frame_color) sc.frame_color[i] = make_float4(c.x, c.y, c.z, 1.0f);  // (wave-uniform: a kernel argument)
 }
 // pixel -> (x, y) for the start kernels: 8x8 tiles so a wave's first rays are coherent

@@ -201,7 +201,7 @@ class Renderer:
         self._call("ptx_write_buffer", self._h, which, arr.ctypes.data, arr.nbytes)
 
     def read_counters(self) -> dict:
-        c = np.zeros(8, dtype=np.uint64)
+        c = np.zeros(32, dtype=np.uint64)
         self._call("ptx_read_buffer", self._h, N.PTX_BUF_COUNTERS, c.ctypes.data, c.nbytes)
         # cull_misses: queries of the counting build whose instance cull would have skipped an
         # instance with a root its pre-filter passes (the cull's conservativeness check: always 0)
@@ -209,7 +209,10 @@ class Renderer:
                 "hits": int(c[4]), "cull_misses": int(c[5]),
                 # motion_clips (every build): pixels of a moved camera's frames whose reprojection
                 # fell past a band's motion halo (no history there; 0 keeps bands bit-identical)
-                "motion_clips": int(c[N.PTX_COUNTER_MOTION_CLIP])}
+                "motion_clips": int(c[N.PTX_COUNTER_MOTION_CLIP]),
+                # replays (every build): pixels whose spatial output carried no contribution when
+                # the spatial pass shaded them itself, so PT_4 replayed their paths
+                "replays": int(c[N.PTX_COUNTER_REPLAY])}
 
     def stats(self) -> dict:
         s = N.PtxStats()
