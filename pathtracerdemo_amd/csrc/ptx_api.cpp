@@ -470,6 +470,8 @@ Scene make_scene(ptx_handle *h) {
     sc.insts = (const Inst *)h->d_insts.p;
     sc.mats = (const float4 *)h->d_mats.p;
     sc.tverts = (const float4 *)h->d_tverts.p;
+    sc.lights = sc.S ? sc.S + sc.U[U_OFF_LIGHT] : nullptr;
+    sc.cdf = sc.S ? sc.S + sc.U[U_OFF_CDF] : nullptr;
     sc.n_inst = h->n_inst;
     sc.n_subs = h->n_subs;
     sc.width = h->cfg.width;

@@ -82,6 +82,8 @@ struct Scene {
     const Inst *insts;
     const float4 *mats;   // 2 float4 per sub-mesh (SubRoot numbering): GetMaterial, pre-applied
     const float4 *tverts; // 5 float4 per triangle (triangle-table order): its 3 vertices' position + normal
+    const uint32_t *lights;  // S + U[U_OFF_LIGHT]: STRIDE_LIGHT words per light (get_light)
+    const uint32_t *cdf;     // S + U[U_OFF_CDF]: one float per light (light_cdf)
     uint32_t n_inst, n_subs;
     uint32_t width, height, row_begin, row_end;
     unsigned long long *counters;  // nullptr unless PTX_FLAG_COUNT_WORK
@@ -1037,7 +1039,7 @@ __device__ __forceinline__ Hit trace_core_flat(const Scene &sc, const SubRoot *s
 // Sub-root and instance tables staged in LDS when they fit: every ray tests every root of
 // every instance, ~16 table reads per query otherwise paid as scalar-load round trips.  The
 // tables sit at the start of the kernel's dynamic LDS, sized to the scene (32 B per sub-mesh
-// root, 144 B per instance) up to kLdsTableMax: ~700 sub-meshes, or 100 furnished instances
+// root, 176 B per instance) up to kLdsTableMax: ~700 sub-meshes, or 100 furnished instances
 // of a few sub-meshes each.  Larger scenes read the global tables.
 constexpr uint32_t kLdsTableMax = 24576u;
 __host__ __device__ __forceinline__ uint32_t tables_lds_bytes(const Scene &sc) {
@@ -1058,6 +1060,62 @@ __device__ __forceinline__ LdsTables stage_tables(const Scene &sc, uint32_t *lds
     for (uint32_t i = threadIdx.x; i < sc.n_inst * (uint32_t)(sizeof(Inst) / 4u); i += blockDim.x) li[i] = gi[i];
     __syncthreads();
     return LdsTables{l_subs, l_insts};
+}
+
+// The logic kernels' lookup tables in LDS: instances (get_surface, surface_at, mat_index),
+// materials (material_at), light records (get_light) and the light CDF (sample_nee's binary
+// search).  All are indexed per lane at the end of a chain of dependent loads -- material after
+// surface record, light after its id, each CDF probe after the one before -- so from global
+// memory every lookup is one more round trip of the chain.  3.4 KB on C3, 6.0 KB furnished.
+// Cap: 16 KiB.  Four workgroups per CU (the 4-wave register budget of the kernels that stage)
+// then hold at most 64 KiB of the CU's 160, which leaves the trace workgroups of the other
+// frame in flight their tables and stacks.  (It is also what a kernel with wspatial_start's
+// 24 KiB of bins could add at four workgroups per CU, less its 12 bytes of counters; that kernel
+// does not stage: ptx_reuse.hip.)  Larger scenes read the global tables.
+constexpr uint32_t kShadeLdsMax = 16384u;
+__host__ __device__ __forceinline__ uint32_t shade_sec(unsigned long long bytes) {  // one section, 16-byte aligned
+    return bytes > 0x7fffffffull ? 0x7fffffffu : ((uint32_t)bytes + 15u) & ~15u;
+}
+__host__ __device__ __forceinline__ uint32_t shading_lds_bytes(const Scene &sc) {
+    const unsigned long long nl = sc.U[U_LIGHT_COUNT];
+    const unsigned long long b = (unsigned long long)shade_sec(sc.n_inst * (unsigned long long)sizeof(Inst)) +
+                                 shade_sec(sc.n_subs * 2ull * sizeof(float4)) + shade_sec(nl * STRIDE_LIGHT * 4ull) +
+                                 shade_sec(nl * 4ull);
+    return b > 0x7fffffffull ? 0x7fffffffu : (uint32_t)b;
+}
+__host__ __device__ __forceinline__ bool shading_fits_lds(const Scene &sc) { return shading_lds_bytes(sc) <= kShadeLdsMax; }
+// Returns `sc` with insts, mats, lights and cdf pointing into `lds` (16-byte aligned dynamic
+// LDS of shading_lds_bytes(sc)), in that order.  Called by every thread of the workgroup; with
+// `copy` (workgroup-uniform) the workgroup fills the tables.  It ends WITHOUT a barrier: the
+// caller's next one (seg_begin's) publishes the copy.  A workgroup with nothing to shade passes
+// copy = false and must not read the tables.  Every callee that reads them is __forceinline__,
+// so the compiler sees LDS pointers and emits ds_read, never flat loads.
+__device__ __forceinline__ Scene stage_shading(const Scene &sc, uint32_t *lds, bool copy) {
+    const uint32_t nl = sc.U[U_LIGHT_COUNT];
+    const uint32_t n_i = sc.n_inst * (uint32_t)(sizeof(Inst) / 16u), n_m = sc.n_subs * 2u;  // uint4s
+    const uint32_t n_l = nl * STRIDE_LIGHT, n_c = nl;                                       // words
+    uint4 *l_insts = reinterpret_cast<uint4 *>(lds), *l_mats = l_insts + n_i;
+    uint32_t *l_lights = reinterpret_cast<uint32_t *>(l_mats + n_m), *l_cdf = l_lights + ((n_l + 3u) & ~3u);
+    if (copy) {
+        const uint4 *gi = reinterpret_cast<const uint4 *>(sc.insts), *gm = reinterpret_cast<const uint4 *>(sc.mats);
+        for (uint32_t i = threadIdx.x; i < n_i; i += blockDim.x) l_insts[i] = gi[i];
+        for (uint32_t i = threadIdx.x; i < n_m; i += blockDim.x) l_mats[i] = gm[i];
+        for (uint32_t i = threadIdx.x; i < n_l; i += blockDim.x) l_lights[i] = sc.lights[i];  // (4-byte aligned in S)
+        for (uint32_t i = threadIdx.x; i < n_c; i += blockDim.x) l_cdf[i] = sc.cdf[i];
+    }
+    Scene t = sc;
+    t.insts = reinterpret_cast<const Inst *>(l_insts);
+    t.mats = reinterpret_cast<const float4 *>(l_mats);
+    t.lights = l_lights;
+    t.cdf = l_cdf;
+    return t;
+}
+// The Scene a logic kernel shades with: the LDS tables (LDS_SHADE, chosen by the host where
+// shading_fits_lds) or the global ones.
+template <bool LDS_SHADE>
+__device__ __forceinline__ Scene shading_scene(const Scene &sc, uint32_t *lds, bool copy) {
+    if constexpr (LDS_SHADE) return stage_shading(sc, lds, copy);
+    else return sc;
 }
 
 template <bool COUNT, bool PROF = false>

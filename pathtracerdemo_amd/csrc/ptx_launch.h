@@ -26,6 +26,17 @@ inline int ab_knob(const char *key, int dflt) { return env_knob(key, dflt); }
 constexpr int ab_knob(const char *, int dflt) { return dflt; }
 #endif
 
+// Whether a logic kernel's launch takes the LDS_SHADE instantiation (stage_shading): the scene's
+// shading tables fit, and -- measurement builds only -- the kernel's bit of PTX_AB=SHADE_LDS=mask
+// is set (a kernel alone on the LDS or the global tables; the shipped library stages in all).
+// (bit 8 was wspatial_start: staged it was no faster, profiles/logic_tables/, so it reads the global tables)
+enum : int { SL_INIT_START = 1, SL_INIT_STEP = 2, SL_TEMPORAL_START = 4, SL_JOB_STEP = 16 };
+inline bool shade_from_lds(const Scene &sc, int kernel_bit) {
+    static const int mask = ab_knob("SHADE_LDS", SL_INIT_START | SL_INIT_STEP | SL_TEMPORAL_START | SL_JOB_STEP);
+    return shading_fits_lds(sc) && (mask & kernel_bit) != 0;
+}
+inline size_t shade_lds_bytes(bool staged, const Scene &sc) { return staged ? shading_lds_bytes(sc) : 0u; }
+
 // dynamic LDS bytes for a traversal stack of `depth` entries per thread
 inline size_t stack_lds_bytes(uint32_t depth) { return (size_t)depth * kBlock * sizeof(uint32_t); }
 

@@ -337,9 +337,12 @@ __device__ __forceinline__ void job_finish(const Seg &g, const JobLists &JL, con
 #endif
 // One job step of this workgroup's segment (wjob_step, and the fused spatial rounds below);
 // `lds` = 3 words of LDS.  Returns the segment's ray count for the next trace round.
-__device__ __forceinline__ uint32_t job_step_segment(const Scene &sc, const WaveBufs &w, uint32_t round,
-                                                     const ReuseArgs &A, uint32_t *lds) {
+// LDS_SHADE: the shading tables staged in `shade_lds` (stage_shading; skipped by an empty segment).
+template <bool LDS_SHADE>
+__device__ __forceinline__ uint32_t job_step_segment(const Scene &gsc, const WaveBufs &w, uint32_t round,
+                                                     const ReuseArgs &A, uint32_t *lds, uint32_t *shade_lds) {
     const JobLists JL = job_lists(w, lds);
+    const Scene sc = shading_scene<LDS_SHADE>(gsc, shade_lds, seg_n_in(w, round) != 0u);
     const Seg g = seg_begin(w, round, lds);
     uint32_t nh;
     const uint32_t n = split_count(g, nh);
@@ -402,11 +405,13 @@ __device__ __forceinline__ uint32_t job_step_segment(const Scene &sc, const Wave
     job_seg_end(w, g, JL);
     return *g.l_ray;  // (stable after job_seg_end's barrier)
 }
+template <bool LDS_SHADE>
 __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(JOB_STEP_WAVES, 8)))
 void wjob_step(Scene sc, WaveBufs w, uint32_t round, ReuseArgs A) {
     PTX_WAVE_TIMER(sc, KID_JOB_STEP | (w.seg_base ? 0x80u : 0u));
     __shared__ uint32_t lds[3];
-    (void)job_step_segment(sc, w, round, A, lds);
+    extern __shared__ __attribute__((aligned(16))) uint32_t shade_lds[];
+    (void)job_step_segment<LDS_SHADE>(sc, w, round, A, lds, shade_lds);
 }
 
 __device__ __forceinline__ uint32_t reuse_seed(const Scene &sc, uint32_t x, uint32_t y, uint32_t salt) {
@@ -524,11 +529,14 @@ __device__ __forceinline__ bool temporal_from_init(const Scene &sc, const WaveBu
 }
 
 // (the inlined replay needs more registers than the 4-wave budget: 160 B/lane spilled there)
+template <bool LDS_SHADE>
 __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(2, 8)))
-void wtemporal_start(Scene sc, WaveBufs w, ReuseArgs A) {
-    PTX_WAVE_TIMER(sc, KID_TEMP_START | (w.seg_base ? 0x80u : 0u));
+void wtemporal_start(Scene gsc, WaveBufs w, ReuseArgs A) {
+    PTX_WAVE_TIMER(gsc, KID_TEMP_START | (w.seg_base ? 0x80u : 0u));
     __shared__ uint32_t lds[3];
+    extern __shared__ __attribute__((aligned(16))) uint32_t shade_lds[];
     const JobLists JL = job_lists(w, lds);
+    const Scene sc = shading_scene<LDS_SHADE>(gsc, shade_lds, true);  // (seg_begin's barrier publishes the copy)
     const Seg g = seg_begin(w, 0u, lds);
     const uint32_t np = padded_pixels(sc);
     for (uint32_t k = 0; k < w.seg_px; k += WB) {
@@ -644,11 +652,14 @@ __device__ __forceinline__ MotionHist motion_hist(const Scene &sc, const ReuseAr
 #ifndef MOTION_START_WAVES
 #define MOTION_START_WAVES 3
 #endif
+template <bool LDS_SHADE>
 __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(MOTION_START_WAVES, 8)))
-void wtmotion_start(Scene sc, WaveBufs w, ReuseArgs A) {
-    PTX_WAVE_TIMER(sc, KID_TEMP_START | (w.seg_base ? 0x80u : 0u));
+void wtmotion_start(Scene gsc, WaveBufs w, ReuseArgs A) {
+    PTX_WAVE_TIMER(gsc, KID_TEMP_START | (w.seg_base ? 0x80u : 0u));
     __shared__ uint32_t lds[3];
+    extern __shared__ __attribute__((aligned(16))) uint32_t shade_lds[];
     const JobLists JL = job_lists(w, lds);
+    const Scene sc = shading_scene<LDS_SHADE>(gsc, shade_lds, true);  // (seg_begin's barrier publishes the copy)
     const Seg g = seg_begin(w, 0u, lds);
     const uint32_t np = padded_pixels(sc);
     for (uint32_t k = 0; k < w.seg_px; k += WB) {
@@ -869,6 +880,9 @@ constexpr uint32_t kMaxPrefetch = 3u;  // neighbours whose data wspatial_start g
 // form: 168 VGPRs + 44 B/lane, 3 waves).  A floor of 4 gives 125 VGPRs + 20 B/lane and the same
 // speed (551.8-553.5 Msamples/s against 551.6-552.4, same box, 4 runs each); 5 gives 96 VGPRs +
 // 144 B/lane and loses 2 % (539.6-547.7 against 551.9-553.8): profiles/spatial_bins/.
+// It reads the shading tables from global memory: staged in LDS (stage_shading) it was not faster
+// -- 537-544 us a launch against 536-539, headline 562.95 against 562.91 Msamples/s
+// (profiles/logic_tables/) -- and needed its decide loop trimmed to stay at 4 waves.
 #define SPATIAL_START_WAVES 3
 #endif
 // A bin holds < 64 descriptors between pushes and a push adds <= 64: 128 entries.  24 KiB per
@@ -1334,11 +1348,18 @@ hipError_t wave_reuse_round(const Scene &sc, const WaveBufs &w, int pass_tempora
                             hipStream_t s) {
     const dim3 grid(w.seg_count), blk(WB);
     if (round == 0) {
-        if (pass_temporal && A.motion) hipLaunchKernelGGL(wtmotion_start, grid, blk, 0, s, sc, w, A);
-        else if (pass_temporal) hipLaunchKernelGGL(wtemporal_start, grid, blk, 0, s, sc, w, A);
-        else hipLaunchKernelGGL(wspatial_start, grid, blk, 0, s, sc, w, A);
+        if (pass_temporal) {  // the shading tables from LDS where they fit (stage_shading)
+            const bool staged = shade_from_lds(sc, SL_TEMPORAL_START);
+            auto k = A.motion ? (staged ? wtmotion_start<true> : wtmotion_start<false>)
+                              : (staged ? wtemporal_start<true> : wtemporal_start<false>);
+            hipLaunchKernelGGL(k, grid, blk, shade_lds_bytes(staged, sc), s, sc, w, A);
+        } else {
+            hipLaunchKernelGGL(wspatial_start, grid, blk, 0, s, sc, w, A);
+        }
     } else if (round <= reuse_rounds(pass_temporal, A)) {
-        hipLaunchKernelGGL(wjob_step, grid, blk, 0, s, sc, w, (uint32_t)round, A);
+        const bool staged = shade_from_lds(sc, SL_JOB_STEP);
+        auto k = staged ? wjob_step<true> : wjob_step<false>;
+        hipLaunchKernelGGL(k, grid, blk, shade_lds_bytes(staged, sc), s, sc, w, (uint32_t)round, A);
     } else {
         if (pass_temporal && A.motion) hipLaunchKernelGGL(wtmotion_combine, grid, blk, 0, s, sc, w, A);
         else if (pass_temporal) hipLaunchKernelGGL(wtemporal_combine, grid, blk, 0, s, sc, w, A);

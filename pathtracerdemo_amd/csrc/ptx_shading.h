@@ -83,7 +83,7 @@ struct Light { f3 pos, dir, color, U, V; uint32_t type; float intensity, area; }
 struct LightSample { f3 dir; uint32_t type; f3 pos; int32_t id; f3 Le; float pdf; };
 
 __device__ __forceinline__ Light get_light(const Scene &sc, uint32_t id) {
-    const uint32_t *p = sc.S + sc.U[U_OFF_LIGHT] + STRIDE_LIGHT * id;
+    const uint32_t *p = sc.lights + STRIDE_LIGHT * id;
     Light l;
     l.pos = mk(asf(p[0]), asf(p[1]), asf(p[2]));
     l.dir = mk(asf(p[3]), asf(p[4]), asf(p[5]));
@@ -95,7 +95,7 @@ __device__ __forceinline__ Light get_light(const Scene &sc, uint32_t id) {
     l.area = asf(p[17]);
     return l;
 }
-__device__ __forceinline__ float light_cdf(const Scene &sc, uint32_t i) { return asf(sc.S[sc.U[U_OFF_CDF] + i]); }
+__device__ __forceinline__ float light_cdf(const Scene &sc, uint32_t i) { return asf(sc.cdf[i]); }
 
 // ------------------------------------------------------------------ BSDF (SH/PT_1_InitPass.wgsl:834-929)
 __device__ __forceinline__ float ggx_d(float NdotH, float R) {

@@ -644,10 +644,16 @@ __device__ __forceinline__ void winit_finish(const WInit &s, uint4 *reservoir, u
     out[7] = make_uint4(asu(s.w_sum / s.p_hat_sel), s.C, 0u, 0u);
 }
 
-__global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(LOGIC_WAVES, 8))) void winit_start(Scene sc, WaveBufs w, const uint4 *gbuf, uint4 *reservoir) {
-    PTX_WAVE_TIMER(sc, KID_INIT_START | (w.seg_base ? 0x80u : 0u));
+// LDS_SHADE: the instance, material and light tables read from LDS (stage_shading; dynamic LDS
+// of shading_lds_bytes), the host's choice where shading_fits_lds -- as in winit_step and the
+// reuse passes' start / step kernels.
+template <bool LDS_SHADE>
+__global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(LOGIC_WAVES, 8))) void winit_start(Scene gsc, WaveBufs w, const uint4 *gbuf, uint4 *reservoir) {
+    PTX_WAVE_TIMER(gsc, KID_INIT_START | (w.seg_base ? 0x80u : 0u));
     __shared__ uint32_t lds[3];
+    extern __shared__ __attribute__((aligned(16))) uint32_t shade_lds[];
     const JobLists JL = job_lists(w, lds);
+    const Scene sc = shading_scene<LDS_SHADE>(gsc, shade_lds, true);  // (seg_begin's barrier publishes the copy)
     const Seg g = seg_begin(w, 0u, lds);
     float4 *state = w.state;
     const uint32_t npix = w.npix, np = padded_pixels(sc);
@@ -687,10 +693,14 @@ __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(LOGIC_WAVES,
     job_seg_end(w, g, JL);
 }
 
-__global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(LOGIC_WAVES, 8))) void winit_step(Scene sc, WaveBufs w, uint32_t round, uint4 *reservoir) {
-    PTX_WAVE_TIMER(sc, KID_INIT_STEP | (w.seg_base ? 0x80u : 0u));
+template <bool LDS_SHADE>
+__global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(LOGIC_WAVES, 8))) void winit_step(Scene gsc, WaveBufs w, uint32_t round, uint4 *reservoir) {
+    PTX_WAVE_TIMER(gsc, KID_INIT_STEP | (w.seg_base ? 0x80u : 0u));
     __shared__ uint32_t lds[3];
+    extern __shared__ __attribute__((aligned(16))) uint32_t shade_lds[];
     const JobLists JL = job_lists(w, lds);
+    // (an empty segment copies nothing and reads nothing; it still writes its counts)
+    const Scene sc = shading_scene<LDS_SHADE>(gsc, shade_lds, seg_n_in(w, round) != 0u);
     const Seg g = seg_begin(w, round, lds);
     float4 *state = w.state;
     const float4 *res_in = g.res_in;
@@ -1385,10 +1395,15 @@ hipError_t wave_gbuffer(const Scene &sc, const WaveBufs &w, uint4 *gbuf, uint32_
 // Logic round r consumes the results of trace round r-1 and emits the rays of trace round r.
 hipError_t wave_init_round(const Scene &sc, const WaveBufs &w, int round, const uint4 *gbuf, uint4 *reservoir,
                            hipStream_t s) {
-    if (round == 0)
-        hipLaunchKernelGGL(winit_start, dim3(w.seg_count), dim3(WB), 0, s, sc, w, gbuf, reservoir);
-    else
-        hipLaunchKernelGGL(winit_step, dim3(w.seg_count), dim3(WB), 0, s, sc, w, (uint32_t)round, reservoir);
+    const bool staged = shade_from_lds(sc, round == 0 ? SL_INIT_START : SL_INIT_STEP);
+    const size_t lds = shade_lds_bytes(staged, sc);
+    if (round == 0) {
+        auto k = staged ? winit_start<true> : winit_start<false>;
+        hipLaunchKernelGGL(k, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir);
+    } else {
+        auto k = staged ? winit_step<true> : winit_step<false>;
+        hipLaunchKernelGGL(k, dim3(w.seg_count), dim3(WB), lds, s, sc, w, (uint32_t)round, reservoir);
+    }
     return hipGetLastError();
 }
 

@@ -46,6 +46,11 @@ __device__ __forceinline__ uint32_t res_sel(const WaveBufs &w, uint32_t round) {
     return w.nres == 3u ? round % 3u : round & 1u;
 }
 __device__ __forceinline__ float4 *res_buf(const WaveBufs &w, uint32_t round) { return w.res[res_sel(w, round)]; }
+// This workgroup's input count word of logic round `round` (Seg::n_in; 0 in a start round).
+// A step kernel reads it ahead of seg_begin: an empty segment skips stage_shading's copy.
+__device__ __forceinline__ uint32_t seg_n_in(const WaveBufs &w, uint32_t round) {
+    return round ? w.cnt[(2u * (round - 1u)) * w.cnt_stride + w.seg_phys + w.seg_base + blockIdx.x] : 0u;
+}
 __device__ __forceinline__ Seg seg_begin(const WaveBufs &w, uint32_t round, uint32_t *lds) {
     Seg g;
     g.j = w.seg_base + blockIdx.x;
@@ -58,7 +63,7 @@ __device__ __forceinline__ Seg seg_begin(const WaveBufs &w, uint32_t round, uint
     g.out_sel = res_sel(w, round);
     g.act_out = w.act[round & 1u] + (size_t)g.pj * w.act_stride;
     g.act_in = w.act[(round + 1u) & 1u] + (size_t)g.pj * w.act_stride;
-    g.n_in = round ? w.cnt[(2u * (round - 1u)) * w.cnt_stride + g.pj] : 0u;
+    g.n_in = seg_n_in(w, round);
     g.l_ray = lds;
     g.l_act = lds + 1;
     if (threadIdx.x == 0) { lds[0] = 0u; lds[1] = 0u; }
