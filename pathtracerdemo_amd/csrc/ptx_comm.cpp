@@ -7,16 +7,33 @@
 // (docs/theory/ReSTIR_Pipeline.md:354-462) reads neighbours up to reuse_radius rows away, so
 // a row band needs the G-buffer + reservoir rows of the bands above and below between its
 // temporal and spatial passes.  Here that exchange is device to device on the handle's
-// streams, no host synchronisation anywhere in a frame:
-//   * across processes (one rank per GPU): grouped ncclSend / ncclRecv straight from the
-//     band's first / last rows into the neighbour's halo rows (no pack / unpack copies);
-//   * inside one process (ptx_render_bands, e.g. one Node host driving every GPU, or several
-//     bands on one GPU): the same through the handles' communicators, or hipMemcpyPeerAsync
-//     when the handles have none.
-// The denoiser of a split frame (ptx_denoise_bands) exchanges a second halo the
-// same two ways: the rows of the neighbours' G-buffer and colours (or temporal state) its filter reaches.
-// The upsampler of a split frame (ptx_upsample_bands) exchanges a third: 2 rows of the neighbours' small
-// denoised image.
+// streams, no host synchronisation anywhere in a frame.
+//
+// One exchange moves every halo (exchange_halos).  A band's part of it is data (Halo): per side
+// the messages in order, each a send range of its own rows, a receive range and a byte count,
+// with the handle whose communicator carries them, the device and stream they run on, and the
+// event after which its send ranges may be read.  Four small functions fill it:
+//   * static_halo: G-buffer and PT_1 reservoir rows, between the temporal and the spatial pass;
+//   * motion_halo: history rows, before a moved camera's temporal pass;
+//   * dn_halo (ptx_denoise_bands): texels, colour or temporal state, moments --
+//     the rows the filter reaches;
+//   * up_halo (ptx_upsample_bands): 2 rows of the neighbours' small denoised image.
+// It moves them one of two ways:
+//   * over communicators -- across processes (one rank per GPU: a lone band of the call) or
+//     inside one (ptx_*_bands on handles that own them): grouped ncclSend / ncclRecv straight
+//     from the band's rows into the neighbour's halo rows (no pack / unpack copies);
+//   * by hipMemcpyPeerAsync between the band handles of one process that own none.
+// Ordering.  A send or receive is stream-ordered: it reads the band's rows behind what wrote them
+// on its stream, and what the band enqueues later on that stream runs after it.  Peer copies are
+// pulled by the receiving band's stream, so two events per halo order them against the owner:
+//                 the neighbour reads a band's rows after      the owner rewrites them after
+//   static halo   ev_front (its temporal pass)                 the neighbours' ev_halo (end of ptx_render_bands)
+//   motion halo   ev_prev (its previous frame complete)        the neighbours' ev_mhalo (before its spatial pass)
+//   denoiser      ev_dn_ready (its frame; its dn_temporal)     the neighbours' ev_dn_copied (end of the call)
+//   upsampler     ev_up_src (the small band's last denoise)    the neighbours' pairs' ev_up_done (upsample_release)
+// The left column is Halo::ready, waited for inside the exchange; ev_mhalo and ev_dn_copied are
+// recorded by it behind a band's copies (Halo::copied); the waits of the right column stay with
+// the callers, as do ev_halo (halo_landed: after the halo rows' summaries) and ev_up_done.
 // PTX_FLAG_HALO_OVERLAP splits the spatial pass into the rows whose neighbourhood lies inside
 // the band (run while the halo is in flight) and the edge rows (run when it has landed).
 //
@@ -126,28 +143,26 @@ const Rccl &rccl() {
 // Non-blocking communicators (ptx_comm_init): the init and every group end return at once and
 // complete in the background; their state is polled here until it leaves ncclInProgress or the
 // deadline passes.  A rank whose peers never join (one died before its ncclCommInitRank, or
-// failed inside it) thus gets an error status after `seconds` instead of hanging for ever, and
+// failed inside it) thus gets an error status at the deadline instead of hanging for ever, and
 // the communicator is aborted (PTX_AB=COMM_TIMEOUT_S=n overrides the 120 s default).
 int comm_timeout_s() {
     static const int t = env_knob("COMM_TIMEOUT_S", 120);
     return t > 0 ? t : 120;
 }
-ncclResult_t comm_wait(ncclComm_t c, int seconds) {
-    const auto end = std::chrono::steady_clock::now() + std::chrono::seconds(seconds);
+using Clock = std::chrono::steady_clock;
+Clock::time_point comm_deadline() { return Clock::now() + std::chrono::seconds(comm_timeout_s()); }
+ncclResult_t comm_wait(ncclComm_t c, Clock::time_point end) {
     for (uint32_t spin = 0;; ++spin) {
         ncclResult_t st = ncclSuccess;
         const ncclResult_t r = rccl().async_error(c, &st);
         if (r != ncclSuccess) return r;
         if (st != ncclInProgress) return st;
-        if (std::chrono::steady_clock::now() >= end) return ncclInProgress;  // (the deadline)
+        if (Clock::now() >= end) return ncclInProgress;  // (the deadline)
         if (spin >= 64u) std::this_thread::sleep_for(std::chrono::microseconds(200));
     }
 }
-// ncclGroupEnd on a band handle's communicator: complete (enqueued on the streams) on return.
-int group_end_wait(ptx_handle *h) {
-    ncclResult_t r = rccl().group_end();
-    if (r == ncclInProgress) r = comm_wait((ncclComm_t)h->comm, comm_timeout_s());
-    if (r != ncclSuccess) h->comm_broken = true;
+// What a group end came to (after comm_wait, where it returned ncclInProgress), in h's message.
+int group_status(ptx_handle *h, ncclResult_t r) {
     if (r == ncclInProgress)
         return fail(h, PTX_E_HIP, "RCCL group (rank %d of %d) not enqueued within %d s", h->rank, h->world,
                     comm_timeout_s());
@@ -155,37 +170,125 @@ int group_end_wait(ptx_handle *h) {
     return PTX_OK;
 }
 
-// Byte ranges of the halo-extended G-buffer and reservoir allocations: rows [r0, r0 + rows)
-// (row 0 = the first top-halo row).
-struct Rows {
-    char *g, *r;
-    size_t gb, rb;
-};
-Rows rows_of(ptx_handle *h, uint32_t r0, uint32_t rows) {
-    const size_t W = h->cfg.width, rpx = 16u * h->res_u4;
-    return Rows{(char *)h->cur().gbuf.p + (size_t)r0 * W * 16u, (char *)h->cur().res.p + (size_t)r0 * W * rpx,
-                rows * W * 16u, rows * W * rpx};
-}
-// what this band sends up (its first halo_top rows) / down (its last halo_bot rows), and the
-// halo rows it receives into
-Rows send_up(ptx_handle *h) { return rows_of(h, h->halo_top, h->halo_top); }
-Rows send_down(ptx_handle *h) { return rows_of(h, h->halo_top + h->band_h - h->halo_bot, h->halo_bot); }
-Rows recv_top(ptx_handle *h) { return rows_of(h, 0u, h->halo_top); }
-Rows recv_bottom(ptx_handle *h) { return rows_of(h, h->halo_top + h->band_h, h->halo_bot); }
-// The motion halo: the same rows of the history (the previous frame's spatial output), which a
-// moved camera's temporal pass reprojects into (ReuseArgs::prev_row_lo / hi).
-struct HistRows {
-    char *p;
+// ---- The halo exchange.  One band's part of it, as data: per side (0: the band above, 1: the band
+// below) the messages in the order they are posted -- `bytes` of this band's own rows from `send`
+// to that neighbour, the neighbour's from its facing side into `recv`.
+struct HaloMsg {
+    char *send, *recv;
     size_t bytes;
 };
-HistRows hist_rows_of(ptx_handle *h, uint32_t r0, uint32_t rows) {
-    const size_t W = h->cfg.width, rpx = 16u * h->res_u4;
-    return HistRows{(char *)h->d_hist.p + (size_t)r0 * W * rpx, rows * W * rpx};
+struct Halo {
+    ptx_handle *h = nullptr;    // its communicator and rank carry the messages (a failed post: its message)
+    ptx_handle *err = nullptr;  // a failed HIP call or a refused peer copy: this handle's message
+    int device = 0;
+    hipStream_t stream = nullptr;  // what the sends, receives and copies are enqueued on
+    // peer copies: fired once this band's `send` rows may be read; recorded on `stream` behind this
+    // band's copies (null: nothing is)
+    hipEvent_t ready = nullptr, copied = nullptr;
+    HaloMsg msg[2][3];
+    int nmsg[2] = {0, 0};
+    // `rows` rows of `row_bytes`: row `send_row` of `sbuf` onwards goes out, row `recv_row` of `rbuf` onwards comes in
+    void add(int side, void *sbuf, size_t send_row, void *rbuf, size_t recv_row, size_t rows, size_t row_bytes) {
+        if (!rows) return;
+        msg[side][nmsg[side]++] =
+            HaloMsg{(char *)sbuf + send_row * row_bytes, (char *)rbuf + recv_row * row_bytes, rows * row_bytes};
+    }
+};
+Halo halo_on(ptx_handle *h, hipStream_t st, hipEvent_t ready) {
+    Halo x;
+    x.h = x.err = h;
+    x.device = h->device;
+    x.stream = st;
+    x.ready = ready;
+    return x;
 }
-HistRows hist_send_up(ptx_handle *h) { return hist_rows_of(h, h->halo_top, h->halo_top); }
-HistRows hist_send_down(ptx_handle *h) { return hist_rows_of(h, h->halo_top + h->band_h - h->halo_bot, h->halo_bot); }
-HistRows hist_recv_top(ptx_handle *h) { return hist_rows_of(h, 0u, h->halo_top); }
-HistRows hist_recv_bottom(ptx_handle *h) { return hist_rows_of(h, h->halo_top + h->band_h, h->halo_bot); }
+// The rows of a reuse band's halo-extended buffer `buf` (row 0 = the first top-halo row): its first
+// halo_top own rows go up and its last halo_bot own rows down; the halo rows receive.
+void add_edge_rows(Halo &x, const ptx_handle *h, void *buf, size_t row_bytes) {
+    const size_t end = h->halo_top + h->band_h;
+    x.add(0, buf, h->halo_top, buf, 0u, h->halo_top, row_bytes);
+    x.add(1, buf, end - h->halo_bot, buf, end, h->halo_bot, row_bytes);
+}
+// The static halo: G-buffer and PT_1 reservoir rows between the temporal and the spatial pass, on the
+// stream exchange_stream chose; a band's rows may be read once its temporal pass is done (ev_front).
+Halo static_halo(ptx_handle *h, hipStream_t xs) {
+    Halo x = halo_on(h, xs, h->ev_front);
+    const size_t W = h->cfg.width;
+    add_edge_rows(x, h, h->cur().gbuf.p, W * 16u);
+    add_edge_rows(x, h, h->cur().res.p, W * 16u * h->res_u4);
+    return x;
+}
+// The motion halo: the same rows of the history (the previous frame's spatial output), which a
+// moved camera's temporal pass reprojects into (ReuseArgs::prev_row_lo / hi).  On h->cur().stream
+// after the wait for the previous frame; a band's rows may be read once that frame is complete
+// (ev_prev).  Every rank of a frame moves or none (the same camera): the groups stay matched.
+Halo motion_halo(ptx_handle *h) {
+    Halo x = halo_on(h, h->cur().stream, h->ev_prev);
+    add_edge_rows(x, h, h->d_hist.p, (size_t)h->cfg.width * 16u * h->res_u4);
+    return x;
+}
+
+// Moves the halos of n bands (x[i] is band i; over communicators a lone band is one rank of a frame
+// whose other bands are other ranks').  `name` is the halo's in a refusal.
+//   Over the bands' communicators, when they have them: one group; per band and side the sends in
+// list order, then the receives; the sent bytes are added to halo_bytes_sent.  The group closes in
+// one place whatever failed inside it, and a group end that returns ncclInProgress (non-blocking
+// communicators) is polled to completion on every communicator of the group against the deadline.  A
+// failure leaves every communicator of the group broken: what its peers hold of it is unknown.
+//   By peer copies otherwise: per band and side its stream waits for the neighbour's `ready`, then
+// copies the neighbour's facing send ranges into this band's receive ranges.
+int exchange_halos(const Halo *x, int n, const char *name) {
+    if (!x[0].h->comm) {
+        for (int i = 0; i < n; ++i) {
+            const Halo &me = x[i];
+            HIP_CHECK(me.err, hipSetDevice(me.device));
+            for (int side = 0; side < 2; ++side) {
+                const int k = me.nmsg[side], j = side == 0 ? i - 1 : i + 1;
+                if (!k) continue;
+                bool match = j >= 0 && j < n && x[j].nmsg[1 - side] == k;
+                for (int m = 0; match && m < k; ++m) match = x[j].msg[1 - side][m].bytes == me.msg[side][m].bytes;
+                if (!match) return fail(me.err, PTX_E_INVALID, "%s of band %d does not match band %d", name, i, j);
+                HIP_CHECK(me.err, hipStreamWaitEvent(me.stream, x[j].ready, 0));
+                for (int m = 0; m < k; ++m)
+                    HIP_CHECK(me.err, hipMemcpyPeerAsync(me.msg[side][m].recv, me.device, x[j].msg[1 - side][m].send,
+                                                         x[j].device, me.msg[side][m].bytes, me.stream));
+            }
+            if (me.copied) HIP_CHECK(me.err, hipEventRecord(me.copied, me.stream));
+        }
+        return PTX_OK;
+    }
+    const Rccl &R = rccl();
+    NCCL_CHECK(x[0].h, R.group_start());
+    const int rc = [&]() -> int {
+        for (int i = 0; i < n; ++i) {
+            const Halo &me = x[i];
+            ncclComm_t c = (ncclComm_t)me.h->comm;
+            HIP_CHECK(me.err, hipSetDevice(me.device));
+            for (int side = 0; side < 2; ++side) {
+                const int peer = side == 0 ? me.h->rank - 1 : me.h->rank + 1;
+                for (int m = 0; m < me.nmsg[side]; ++m)
+                    NCCL_CHECK(me.h, R.send(me.msg[side][m].send, me.msg[side][m].bytes, ncclUint8, peer, c, me.stream));
+                for (int m = 0; m < me.nmsg[side]; ++m)
+                    NCCL_CHECK(me.h, R.recv(me.msg[side][m].recv, me.msg[side][m].bytes, ncclUint8, peer, c, me.stream));
+            }
+        }
+        return PTX_OK;
+    }();
+    ncclResult_t r = R.group_end();  // (every path out of the open group comes through here)
+    if (rc == PTX_OK && r == ncclInProgress) {
+        const Clock::time_point end = comm_deadline();
+        r = ncclSuccess;
+        for (int i = 0; i < n && r == ncclSuccess; ++i) r = comm_wait((ncclComm_t)x[i].h->comm, end);
+    }
+    if (rc != PTX_OK || r != ncclSuccess) {
+        for (int i = 0; i < n; ++i) x[i].h->comm_broken = true;
+        return rc != PTX_OK ? rc : group_status(x[0].h, r);
+    }
+    for (int i = 0; i < n; ++i)
+        for (int side = 0; side < 2; ++side)
+            for (int m = 0; m < x[i].nmsg[side]; ++m) x[i].h->halo_bytes_sent += x[i].msg[side][m].bytes;
+    return PTX_OK;
+}
 
 bool overlap(const ptx_handle *h) { return (h->cfg.flags & PTX_FLAG_HALO_OVERLAP) != 0; }
 
@@ -315,49 +418,6 @@ int exchange_stream(ptx_handle *h, hipStream_t &xs) {
     return PTX_OK;
 }
 
-// Enqueue this band's sends / receives on its communicator (inside a group).
-int nccl_halo(ptx_handle *h, hipStream_t xs) {
-    const Rccl &R = rccl();
-    ncclComm_t c = (ncclComm_t)h->comm;
-    if (h->halo_top) {
-        const Rows s = send_up(h), r = recv_top(h);
-        NCCL_CHECK(h, R.send(s.g, s.gb, ncclUint8, h->rank - 1, c, xs));
-        NCCL_CHECK(h, R.send(s.r, s.rb, ncclUint8, h->rank - 1, c, xs));
-        NCCL_CHECK(h, R.recv(r.g, r.gb, ncclUint8, h->rank - 1, c, xs));
-        NCCL_CHECK(h, R.recv(r.r, r.rb, ncclUint8, h->rank - 1, c, xs));
-    }
-    if (h->halo_bot) {
-        const Rows s = send_down(h), r = recv_bottom(h);
-        NCCL_CHECK(h, R.send(s.g, s.gb, ncclUint8, h->rank + 1, c, xs));
-        NCCL_CHECK(h, R.send(s.r, s.rb, ncclUint8, h->rank + 1, c, xs));
-        NCCL_CHECK(h, R.recv(r.g, r.gb, ncclUint8, h->rank + 1, c, xs));
-        NCCL_CHECK(h, R.recv(r.r, r.rb, ncclUint8, h->rank + 1, c, xs));
-    }
-    return PTX_OK;
-}
-
-// A moved camera's motion halo over the communicator, on h->cur().stream after the wait for the previous
-// frame (its spatial output is complete there, and this frame's spatial pass comes after):
-// this band's first / last rows of the history to the neighbours, theirs into its halo rows.
-// Every rank of a frame moves or none (the same camera): the groups stay matched.
-int nccl_motion_halo(ptx_handle *h) {
-    const Rccl &R = rccl();
-    ncclComm_t c = (ncclComm_t)h->comm;
-    if (h->halo_top) {
-        const HistRows s = hist_send_up(h), r = hist_recv_top(h);
-        NCCL_CHECK(h, R.send(s.p, s.bytes, ncclUint8, h->rank - 1, c, h->cur().stream));
-        NCCL_CHECK(h, R.recv(r.p, r.bytes, ncclUint8, h->rank - 1, c, h->cur().stream));
-        h->halo_bytes_sent += s.bytes;
-    }
-    if (h->halo_bot) {
-        const HistRows s = hist_send_down(h), r = hist_recv_bottom(h);
-        NCCL_CHECK(h, R.send(s.p, s.bytes, ncclUint8, h->rank + 1, c, h->cur().stream));
-        NCCL_CHECK(h, R.recv(r.p, r.bytes, ncclUint8, h->rank + 1, c, h->cur().stream));
-        h->halo_bytes_sent += s.bytes;
-    }
-    return PTX_OK;
-}
-
 // After the halo landed on xs: the halo rows' neighbour summaries, then ev_halo.
 int halo_landed(ptx_handle *h, hipStream_t xs) {
     if (overlap(h)) {
@@ -437,7 +497,12 @@ int check_neighbours(ptx_handle *h) {
         h->comm_broken = true;
         return done(fail(h, PTX_E_HIP, "neighbour check: %s", R.error_string(r)));
     }
-    if (int rc = group_end_wait(h)) return done(rc);
+    r = R.group_end();
+    if (r == ncclInProgress) r = comm_wait(c, comm_deadline());
+    if (r != ncclSuccess) {
+        h->comm_broken = true;
+        return done(group_status(h, r));
+    }
     e = hipMemcpyAsync(got, d + 6, sizeof got, hipMemcpyDeviceToHost, h->cur().stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->cur().stream);
     if (e != hipSuccess) {
@@ -467,57 +532,109 @@ int check_neighbours(ptx_handle *h) {
 // spatial mode, its accumulated colour, in temporal mode the {C, n} and {m1, m2} its dn_temporal
 // just wrote.  All are contiguous rows of buffers the neighbour holds: its last `rows` own rows
 // (for the band below it) or its first (for the band above).
-struct DnRows {
-    char *g, *c, *m;   // texels, colour or history, moments (temporal mode)
-    size_t gb, cb, mb;
-};
-// the own rows [r0, r0 + rows) of band h that a neighbour reads
-DnRows dn_send_rows(ptx_handle *h, const DnCall &c, const DnBand &b, uint32_t r0, uint32_t rows) {
-    const size_t W = h->cfg.width, n = (size_t)rows * W, own = ((size_t)h->dn_cap_top + r0) * W;
-    DnRows r{(char *)gbuf_band(h) + (size_t)r0 * W * 16u, nullptr, nullptr, n * 16u, n * 16u, 0};
-    if (c.temporal) {
-        r.c = (char *)h->d_dn_hist[b.wr].p + own * 16u;
-        r.m = (char *)h->d_dn_mom[b.wr].p + own * 8u;
-        r.mb = n * 8u;
-    } else {
-        r.c = (char *)h->d_accum.p + (size_t)r0 * W * 16u;
-    }
-    return r;
-}
-// where band h receives its top (above = true) or bottom halo rows
-DnRows dn_recv_rows(ptx_handle *h, const DnCall &c, const DnBand &b, bool above) {
-    const size_t W = h->cfg.width, rows = above ? b.top : b.bot, n = rows * W;
-    const size_t hrow = above ? 0u : b.top;  // (the received texels and colours: top rows, then bottom rows)
-    const size_t srow = above ? h->dn_cap_top - b.top : h->dn_cap_top + h->band_h;  // (the state's halo rows)
-    DnRows r{(char *)h->d_dn_halo_g.p + hrow * W * 16u, nullptr, nullptr, n * 16u, n * 16u, 0};
-    if (c.temporal) {
-        r.c = (char *)h->d_dn_hist[b.wr].p + srow * W * 16u;
-        r.m = (char *)h->d_dn_mom[b.wr].p + srow * W * 8u;
-        r.mb = n * 8u;
-    } else {
-        r.c = (char *)h->d_dn_halo_c.p + hrow * W * 16u;
-    }
-    return r;
-}
-// Enqueue band h's sends / receives on its communicator (inside a group), on its stream: behind its
-// frame and its dn_temporal, ahead of the rest of its call.  Per neighbour the messages go in one
-// order on both sides (texels, colour or history, moments).
-int nccl_dn_halo(ptx_handle *h, const DnCall &c, const DnBand &b) {
-    const Rccl &R = rccl();
-    ncclComm_t cm = (ncclComm_t)h->comm;
-    const hipStream_t st = h->cur().stream;
+// It goes on the band's stream, behind its frame and its dn_temporal (where ev_dn_ready is recorded
+// for peer copies) and ahead of the rest of its call.  Every band's halo is the call's reach: the
+// rows it receives from a side it also sends there.  The buffers of the temporal state hold
+// dn_cap_top rows above the band's own; the received texels and colours lie top rows, then bottom rows.
+Halo dn_halo(ptx_handle *h, const DnCall &c, const DnBand &b) {
+    Halo x = halo_on(h, h->cur().stream, h->ev_dn_ready);
+    const size_t W = h->cfg.width, cap = h->dn_cap_top;
     for (int side = 0; side < 2; ++side) {
-        const uint32_t rows = side == 0 ? b.top : b.bot;  // (every band's halo is the call's reach: what it receives it sends)
-        if (!rows) continue;
-        const int peer = side == 0 ? h->rank - 1 : h->rank + 1;
-        const DnRows s = dn_send_rows(h, c, b, side == 0 ? 0u : h->band_h - rows, rows), r = dn_recv_rows(h, c, b, side == 0);
-        NCCL_CHECK(h, R.send(s.g, s.gb, ncclUint8, peer, cm, st));
-        NCCL_CHECK(h, R.send(s.c, s.cb, ncclUint8, peer, cm, st));
-        if (s.mb) NCCL_CHECK(h, R.send(s.m, s.mb, ncclUint8, peer, cm, st));
-        NCCL_CHECK(h, R.recv(r.g, r.gb, ncclUint8, peer, cm, st));
-        NCCL_CHECK(h, R.recv(r.c, r.cb, ncclUint8, peer, cm, st));
-        if (r.mb) NCCL_CHECK(h, R.recv(r.m, r.mb, ncclUint8, peer, cm, st));
-        h->halo_bytes_sent += s.gb + s.cb + s.mb;
+        const size_t rows = side == 0 ? b.top : b.bot;
+        const size_t own = side == 0 ? 0u : h->band_h - rows;                // the own rows sent
+        const size_t hrow = side == 0 ? 0u : b.top;                          // the received rows' place
+        const size_t srow = side == 0 ? cap - b.top : cap + h->band_h;       // ... and in the state's buffers
+        x.add(side, gbuf_band(h), own, h->d_dn_halo_g.p, hrow, rows, W * 16u);
+        if (c.temporal) {
+            x.add(side, h->d_dn_hist[b.wr].p, cap + own, h->d_dn_hist[b.wr].p, srow, rows, W * 16u);
+            x.add(side, h->d_dn_mom[b.wr].p, cap + own, h->d_dn_mom[b.wr].p, srow, rows, W * 8u);
+        } else {
+            x.add(side, h->d_accum.p, own, h->d_dn_halo_c.p, hrow, rows, W * 16u);
+        }
+    }
+    return x;
+}
+
+// ---- ptx_upsample_bands: the upsampler's halo.  Full-size band hi reads small band lo's denoised
+// rows and kUpHalo rows of each of lo's neighbours' (Upsampling, Bands).  lo's
+// communicator and rows carry it; it runs on hi's device and stream, where the rows are used.  lo's
+// rows may be read once its last denoise is complete (ev_up_src); hi keeps the rows from above, then
+// the rows from below.
+constexpr uint32_t kUpHalo = 2;
+Halo up_halo(ptx_handle *hi, ptx_handle *lo, ptx_handle *err, uint32_t top, uint32_t bot) {
+    Halo x = halo_on(lo, hi->cur().stream, lo->ev_up_src);
+    x.err = err;
+    x.device = hi->device;
+    const size_t own = lo->dn_cap_top, row_bytes = (size_t)lo->cfg.width * 16u;
+    x.add(0, lo->d_denoised.p, own, hi->d_up_halo.p, 0u, top, row_bytes);
+    x.add(1, lo->d_denoised.p, own + lo->band_h - kUpHalo, hi->d_up_halo.p, top, bot, row_bytes);
+    return x;
+}
+
+// ---- What ptx_render_bands, ptx_denoise_bands and ptx_upsample_bands refuse alike, before any GPU
+// work: the bands hs[0..n) whose rows and communicators carry the exchange (ptx_upsample_bands: the
+// small bands).  err receives every message (null: the band at fault does).  The entry points call
+// the checks in the order their refusals have always had, their own checks in between.
+struct BandSet {
+    const char *what;  // the entry point's name
+    ptx_handle *const *hs;
+    int n;
+    ptx_handle *err;
+    bool pairs;      // ptx_upsample_bands' wording: "pair", "small band"
+    bool rank_form;  // one band of a frame whose other bands are other ranks' (every rank makes the call)
+    ptx_handle *to(int i) const { return err ? err : hs[i]; }
+    const char *band() const { return pairs ? "small band" : "band"; }
+};
+bool all_handles(ptx_handle *const *hs, int n) {
+    if (!hs || n < 1 || n > 64) return false;
+    for (int i = 0; i < n; ++i)
+        if (!hs[i]) return false;
+    return true;
+}
+bool is_rank_form(ptx_handle *const *hs, int n) { return n == 1 && hs[0]->comm && hs[0]->world > 1; }
+// band i: band 0's size and pipeline; a communicator if band 0 has one, as rank i of n; rows that continue
+int band_joins(const BandSet &s, int i) {
+    const ptx_handle *h = s.hs[i], *h0 = s.hs[0];
+    if (h->cfg.width != h0->cfg.width || h->cfg.height != h0->cfg.height || h->cfg.pipeline != h0->cfg.pipeline)
+        return fail(s.to(i), PTX_E_INVALID, "%s: %s %d differs in size or pipeline", s.what, s.pairs ? "pair" : "band", i);
+    if ((h->comm != nullptr) != (h0->comm != nullptr))
+        return fail(s.to(i), PTX_E_INVALID, "%s: either every %s owns a communicator or none", s.what, s.band());
+    if (h->comm && !s.rank_form && (h->rank != i || h->world != s.n))
+        return fail(s.to(i), PTX_E_INVALID, "%s: %s %d is rank %d of %d", s.what, s.band(), i, h->rank, h->world);
+    if (i && s.hs[i - 1]->cfg.row_end != h->cfg.row_begin)
+        return fail(s.to(i), PTX_E_INVALID, "%s: %s %d does not start where band %d ends", s.what, s.band(), i, i - 1);
+    return PTX_OK;
+}
+// the bands together are the frame (the rank form: rank_rows)
+int bands_cover(const BandSet &s) {
+    const uint32_t H = s.hs[0]->cfg.height, lo = s.hs[0]->cfg.row_begin, hi = s.hs[s.n - 1]->cfg.row_end;
+    if (!s.rank_form && (lo != 0 || hi != H))
+        return fail(s.to(0), PTX_E_INVALID, "%s: the %ss cover rows %u..%u of %u: a %s needs the rows above and below it",
+                    s.what, s.band(), lo, hi, H, s.pairs ? "band" : "window");
+    return PTX_OK;
+}
+// A band's halo comes from the bands next to it alone: band i has the `need` rows it sends;
+// few(handle, band, rows) words the refusal.
+template <class Few>
+int band_rows(const BandSet &s, int i, uint32_t need, Few few) {
+    if ((s.n > 1 || s.rank_form) && s.hs[i]->band_h < need)
+        return few(s.to(i), s.rank_form ? s.hs[0]->rank : i, s.hs[i]->band_h);
+    return PTX_OK;
+}
+// the rank form: the rank's rows touch the frame's ends where it has no neighbour and only there, and
+// the neighbours' rows (nb_rows, from ptx_comm_init's neighbour check) are `need` at least
+template <class Few>
+int rank_rows(const BandSet &s, uint32_t need, Few few) {
+    if (!s.rank_form) return PTX_OK;
+    const ptx_handle *h = s.hs[0];
+    const uint32_t H = h->cfg.height;
+    if ((h->cfg.row_begin != 0) != (h->rank > 0) || (h->cfg.row_end != H) != (h->rank + 1 < h->world))
+        return fail(s.to(0), PTX_E_INVALID, "%s: rank %d of %d holds rows %u..%u of %u", s.what, h->rank, h->world,
+                    h->cfg.row_begin, h->cfg.row_end, H);
+    for (int k = 0; k < 2; ++k) {
+        if (k == 0 ? h->rank == 0 : h->rank + 1 == h->world) continue;
+        const uint32_t rows = h->nb_rows[k][1] - h->nb_rows[k][0];
+        if (rows < need) return few(s.to(0), k == 0 ? h->rank - 1 : h->rank + 1, rows);
     }
     return PTX_OK;
 }
@@ -535,27 +652,15 @@ int render_band_nccl(ptx_handle *h) {
     TimedLaunch *ft = nullptr;
     if (int rc = band_front(h, sc, w, ft, pipe, moved)) return rc;
     if (xchg) {
-        NCCL_CHECK(h, rccl().group_start());
-        const int rc = nccl_motion_halo(h);
-        if (rc) {
-            (void)rccl().group_end();
-            return rc;
-        }
-        if (int r2 = group_end_wait(h)) return r2;
+        const Halo x = motion_halo(h);
+        if (int rc = exchange_halos(&x, 1, "motion halo")) return rc;
     }
     if (int rc = band_temporal(h, sc, w, pipe, moved)) return rc;
     hipStream_t xs;
     if (int rc = exchange_stream(h, xs)) return rc;
-    NCCL_CHECK(h, rccl().group_start());
-    const int rc = nccl_halo(h, xs);
-    if (rc) {
-        (void)rccl().group_end();
-        return rc;
-    }
-    if (int r2 = group_end_wait(h)) return r2;
-    if (h->halo_top) h->halo_bytes_sent += send_up(h).gb + send_up(h).rb;
-    if (h->halo_bot) h->halo_bytes_sent += send_down(h).gb + send_down(h).rb;
-    if (int r2 = halo_landed(h, xs)) return r2;
+    const Halo x = static_halo(h, xs);
+    if (int rc = exchange_halos(&x, 1, "halo")) return rc;
+    if (int rc = halo_landed(h, xs)) return rc;
     return band_back(h, sc, w, ft);
 }
 
@@ -572,16 +677,11 @@ __global__ void halo_proxy_wait(uint32_t us) {
     }
 }
 static int halo_proxy(ptx_handle *h, hipStream_t xs, uint32_t us) {
-    if (h->halo_top) {
-        const Rows s = send_up(h), r = recv_top(h);
-        HIP_CHECK(h, hipMemcpyAsync(r.g, s.g, s.gb, hipMemcpyDeviceToDevice, xs));
-        HIP_CHECK(h, hipMemcpyAsync(r.r, s.r, s.rb, hipMemcpyDeviceToDevice, xs));
-    }
-    if (h->halo_bot) {
-        const Rows s = send_down(h), r = recv_bottom(h);
-        HIP_CHECK(h, hipMemcpyAsync(r.g, s.g, s.gb, hipMemcpyDeviceToDevice, xs));
-        HIP_CHECK(h, hipMemcpyAsync(r.r, s.r, s.rb, hipMemcpyDeviceToDevice, xs));
-    }
+    const Halo x = static_halo(h, xs);
+    for (int side = 0; side < 2; ++side)
+        for (int m = 0; m < x.nmsg[side]; ++m)
+            HIP_CHECK(h, hipMemcpyAsync(x.msg[side][m].recv, x.msg[side][m].send, x.msg[side][m].bytes,
+                                        hipMemcpyDeviceToDevice, xs));
     hipLaunchKernelGGL(halo_proxy_wait, dim3(1), dim3(64), 0, xs, us);
     HIP_CHECK(h, hipGetLastError());
     return PTX_OK;
@@ -645,7 +745,7 @@ int ptx_comm_init(ptx_handle *h, const void *unique_id, size_t bytes, int rank, 
         ncclConfig_t config = NCCL_CONFIG_INITIALIZER;
         config.blocking = 0;
         ncclResult_t r = R.init_rank_config(&c, world, id, rank, &config);
-        if (r == ncclSuccess || r == ncclInProgress) r = comm_wait(c, comm_timeout_s());
+        if (r == ncclSuccess || r == ncclInProgress) r = comm_wait(c, comm_deadline());
         if (r != ncclSuccess) {
             if (c) (void)R.abort(c);
             if (r == ncclInProgress)
@@ -714,25 +814,19 @@ int ptx_comm_init_all(ptx_handle *const *hs, int n) {
 }
 
 int ptx_render_bands(ptx_handle *const *hs, int n, float *rgba_out) {
-    if (!hs || n < 1 || n > 64) return PTX_E_INVALID;
-    for (int i = 0; i < n; ++i)
-        if (!hs[i]) return PTX_E_INVALID;
+    if (!all_handles(hs, n)) return PTX_E_INVALID;
     ptx_handle *h0 = hs[0];
     const bool nccl = h0->comm != nullptr;
+    const BandSet s{"ptx_render_bands", hs, n, nullptr, false, false};
+    const auto few = [&](ptx_handle *to, int band, uint32_t) {
+        return fail(to, PTX_E_INVALID, "%s: band %d has fewer rows than the reuse radius", s.what, band);
+    };
     for (int i = 0; i < n; ++i) {
         ptx_handle *h = hs[i];
-        if (h->cfg.width != h0->cfg.width || h->cfg.height != h0->cfg.height || h->cfg.pipeline != h0->cfg.pipeline)
-            return fail(h, PTX_E_INVALID, "ptx_render_bands: band %d differs in size or pipeline", i);
-        if ((h->comm != nullptr) != nccl)
-            return fail(h, PTX_E_INVALID, "ptx_render_bands: either every band owns a communicator or none");
-        if (nccl && (h->rank != i || h->world != n))
-            return fail(h, PTX_E_INVALID, "ptx_render_bands: band %d is rank %d of %d", i, h->rank, h->world);
-        if (i && hs[i - 1]->cfg.row_end != h->cfg.row_begin)
-            return fail(h, PTX_E_INVALID, "ptx_render_bands: band %d does not start where band %d ends", i, i - 1);
+        if (int rc = band_joins(s, i)) return rc;
         if ((i == 0 && h->halo_top) || (i == n - 1 && h->halo_bot))
-            return fail(h, PTX_E_INVALID, "ptx_render_bands: the bands do not cover the halo rows of the ends");
-        if (h->band_h < h->reuse_radius && n > 1)
-            return fail(h, PTX_E_INVALID, "ptx_render_bands: band %d has fewer rows than the reuse radius", i);
+            return fail(h, PTX_E_INVALID, "%s: the bands do not cover the halo rows of the ends", s.what);
+        if (int rc = band_rows(s, i, h->reuse_radius, few)) return rc;
     }
     // the bands agree on the motion halo before any of them enqueues work (motion_exchange)
     const bool xchg = motion_exchange(h0);
@@ -754,76 +848,29 @@ int ptx_render_bands(ptx_handle *const *hs, int n, float *rgba_out) {
         moved[i] = m;
         if (int rc = band_front(hs[i], sc[i], w[i], ft[i], p, m)) return rc;
     }
-    if (xchg) {  // the motion halo: the neighbours' rows of the previous frame's spatial output
-        if (nccl) {
-            NCCL_CHECK(h0, rccl().group_start());
-            int rc = PTX_OK;
-            for (int i = 0; i < n && !rc; ++i) rc = nccl_motion_halo(hs[i]);
-            NCCL_CHECK(h0, rccl().group_end());
-            if (rc) return rc;
-        } else {
-            // peer copies once the neighbour's previous frame is complete (its ev_prev); the
-            // neighbours' spatial passes, which rewrite those rows, wait for ev_mhalo (below)
-            for (int i = 0; i < n; ++i) {
-                ptx_handle *h = hs[i];
-                HIP_CHECK(h, hipSetDevice(h->device));
-                if (i > 0 && h->halo_top) {
-                    ptx_handle *a = hs[i - 1];
-                    const HistRows s = hist_send_down(a), r = hist_recv_top(h);
-                    if (s.bytes != r.bytes) return fail(h, PTX_E_INVALID, "motion halo of band %d does not match band %d", i, i - 1);
-                    HIP_CHECK(h, hipStreamWaitEvent(h->cur().stream, a->ev_prev, 0));
-                    HIP_CHECK(h, hipMemcpyPeerAsync(r.p, h->device, s.p, a->device, r.bytes, h->cur().stream));
-                }
-                if (i + 1 < n && h->halo_bot) {
-                    ptx_handle *b = hs[i + 1];
-                    const HistRows s = hist_send_up(b), r = hist_recv_bottom(h);
-                    if (s.bytes != r.bytes) return fail(h, PTX_E_INVALID, "motion halo of band %d does not match band %d", i, i + 1);
-                    HIP_CHECK(h, hipStreamWaitEvent(h->cur().stream, b->ev_prev, 0));
-                    HIP_CHECK(h, hipMemcpyPeerAsync(r.p, h->device, s.p, b->device, r.bytes, h->cur().stream));
-                }
-                if (!h->ev_mhalo) HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_mhalo, hipEventDisableTiming));
-                HIP_CHECK(h, hipEventRecord(h->ev_mhalo, h->cur().stream));
-            }
+    std::vector<Halo> x(n);
+    if (xchg) {
+        // the motion halo: the neighbours' rows of the previous frame's spatial output.  Peer copies:
+        // the neighbours' spatial passes, which rewrite those rows, wait for ev_mhalo (below)
+        for (int i = 0; i < n; ++i) {
+            ptx_handle *h = hs[i];
+            x[i] = motion_halo(h);
+            if (nccl) continue;
+            HIP_CHECK(h, hipSetDevice(h->device));
+            if (!h->ev_mhalo) HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_mhalo, hipEventDisableTiming));
+            x[i].copied = h->ev_mhalo;
         }
+        if (int rc = exchange_halos(x.data(), n, "motion halo")) return rc;
     }
     for (int i = 0; i < n; ++i) {
         HIP_CHECK(hs[i], hipSetDevice(hs[i]->device));
         if (int rc = band_temporal(hs[i], sc[i], w[i], pipe[i], moved[i])) return rc;
     }
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
         if (int rc = exchange_stream(hs[i], xs[i])) return rc;
-    if (nccl) {
-        NCCL_CHECK(h0, rccl().group_start());
-        int rc = PTX_OK;
-        for (int i = 0; i < n && !rc; ++i) rc = nccl_halo(hs[i], xs[i]);
-        NCCL_CHECK(h0, rccl().group_end());
-        if (rc) return rc;
-    } else {
-        // peer copies: band i pulls its halo rows from its neighbours' band rows once their
-        // front passes are done
-        for (int i = 0; i < n; ++i) {
-            ptx_handle *h = hs[i];
-            HIP_CHECK(hs[i], hipSetDevice(h->device));
-            if (i > 0 && h->halo_top) {
-                ptx_handle *a = hs[i - 1];
-                const Rows s = send_down(a), r = recv_top(h);
-                if (a->halo_bot != h->halo_top || s.gb != r.gb || s.rb != r.rb)
-                    return fail(h, PTX_E_INVALID, "halo of band %d does not match band %d", i, i - 1);
-                HIP_CHECK(h, hipStreamWaitEvent(xs[i], a->ev_front, 0));
-                HIP_CHECK(h, hipMemcpyPeerAsync(r.g, h->device, s.g, a->device, r.gb, xs[i]));
-                HIP_CHECK(h, hipMemcpyPeerAsync(r.r, h->device, s.r, a->device, r.rb, xs[i]));
-            }
-            if (i + 1 < n && h->halo_bot) {
-                ptx_handle *b = hs[i + 1];
-                const Rows s = send_up(b), r = recv_bottom(h);
-                if (b->halo_top != h->halo_bot || s.gb != r.gb || s.rb != r.rb)
-                    return fail(h, PTX_E_INVALID, "halo of band %d does not match band %d", i, i + 1);
-                HIP_CHECK(h, hipStreamWaitEvent(xs[i], b->ev_front, 0));
-                HIP_CHECK(h, hipMemcpyPeerAsync(r.g, h->device, s.g, b->device, r.gb, xs[i]));
-                HIP_CHECK(h, hipMemcpyPeerAsync(r.r, h->device, s.r, b->device, r.rb, xs[i]));
-            }
-        }
+        x[i] = static_halo(hs[i], xs[i]);
     }
+    if (int rc = exchange_halos(x.data(), n, "halo")) return rc;
     for (int i = 0; i < n; ++i) {
         HIP_CHECK(hs[i], hipSetDevice(hs[i]->device));
         if (int rc = halo_landed(hs[i], xs[i])) return rc;
@@ -856,51 +903,27 @@ int ptx_render_bands(ptx_handle *const *hs, int n, float *rgba_out) {
 }
 
 int ptx_denoise_bands(ptx_handle *const *hs, int n, const ptx_denoise_params *p) {
-    if (!hs || n < 1 || n > 64) return PTX_E_INVALID;
-    for (int i = 0; i < n; ++i)
-        if (!hs[i]) return PTX_E_INVALID;
+    if (!all_handles(hs, n)) return PTX_E_INVALID;
     ptx_handle *h0 = hs[0];
     const char *what = "ptx_denoise_bands";
     // ---- refusals, all before any GPU work
     DnCall c;
     if (int rc = denoise_params(h0, p, c, what)) return rc;
-    const bool nccl = h0->comm != nullptr;
-    // the rank form: one band of a frame whose other bands are other ranks' (every rank makes the call)
-    const bool rank_form = n == 1 && nccl && h0->world > 1;
+    const bool nccl = h0->comm != nullptr, rank_form = is_rank_form(hs, n);
     const uint32_t R = dn_reach(c.n), H = h0->cfg.height;
+    const BandSet s{what, hs, n, nullptr, false, rank_form};
+    const auto few = [&](ptx_handle *to, int band, uint32_t rows) {
+        return fail(to, PTX_E_INVALID, "%s: band %d has %u rows; %u iterations need %u rows of every band", what, band,
+                    rows, c.n, R);
+    };
     for (int i = 0; i < n; ++i) {
-        ptx_handle *h = hs[i];
-        if (h->cfg.width != h0->cfg.width || h->cfg.height != H || h->cfg.pipeline != h0->cfg.pipeline)
-            return fail(h, PTX_E_INVALID, "%s: band %d differs in size or pipeline", what, i);
-        if ((h->comm != nullptr) != nccl) return fail(h, PTX_E_INVALID, "%s: either every band owns a communicator or none", what);
-        if (nccl && !rank_form && n > 1 && (h->rank != i || h->world != n))
-            return fail(h, PTX_E_INVALID, "%s: band %d is rank %d of %d", what, i, h->rank, h->world);
-        if (i && hs[i - 1]->cfg.row_end != h->cfg.row_begin)
-            return fail(h, PTX_E_INVALID, "%s: band %d does not start where band %d ends", what, i, i - 1);
-        if (int rc = denoise_check(h, c, what)) return rc;
+        if (int rc = band_joins(s, i)) return rc;
+        if (int rc = denoise_check(hs[i], c, what)) return rc;
     }
-    if (!rank_form && (h0->cfg.row_begin != 0 || hs[n - 1]->cfg.row_end != H))
-        return fail(h0, PTX_E_INVALID, "%s: the bands cover rows %u..%u of %u: a window needs the rows above and below it",
-                    what, h0->cfg.row_begin, hs[n - 1]->cfg.row_end, H);
-    if (n > 1 || rank_form) {  // a band's halo comes from the bands next to it alone
-        for (int i = 0; i < n; ++i)
-            if (hs[i]->band_h < R)
-                return fail(hs[i], PTX_E_INVALID, "%s: band %d has %u rows; %u iterations need %u rows of every band",
-                            what, rank_form ? h0->rank : i, hs[i]->band_h, c.n, R);
-    }
-    if (rank_form) {
-        ptx_handle *h = h0;
-        if ((h->cfg.row_begin != 0) != (h->rank > 0) || (h->cfg.row_end != H) != (h->rank + 1 < h->world))
-            return fail(h, PTX_E_INVALID, "%s: rank %d of %d holds rows %u..%u of %u", what, h->rank, h->world,
-                        h->cfg.row_begin, h->cfg.row_end, H);
-        for (int k = 0; k < 2; ++k) {
-            if (k == 0 ? h->rank == 0 : h->rank + 1 == h->world) continue;
-            const uint32_t rows = h->nb_rows[k][1] - h->nb_rows[k][0];
-            if (rows < R)
-                return fail(h, PTX_E_INVALID, "%s: band %d has %u rows; %u iterations need %u rows of every band", what,
-                            k == 0 ? h->rank - 1 : h->rank + 1, rows, c.n, R);
-        }
-    }
+    if (int rc = bands_cover(s)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = band_rows(s, i, R, few)) return rc;
+    if (int rc = rank_rows(s, R, few)) return rc;
     if (nccl)
         for (int i = 0; i < n; ++i)
             if (int rc = comm_health(hs[i])) return rc;
@@ -915,50 +938,22 @@ int ptx_denoise_bands(ptx_handle *const *hs, int n, const ptx_denoise_params *p)
         if (int rc = denoise_front(h, c, b[i])) return rc;
     }
     // ---- the exchange
-    if (nccl && (n > 1 || rank_form)) {  // one group per call
-        NCCL_CHECK(h0, rccl().group_start());
-        int rc = PTX_OK;
-        for (int i = 0; i < n && !rc; ++i) {
-            HIP_CHECK(hs[i], hipSetDevice(hs[i]->device));
-            rc = nccl_dn_halo(hs[i], c, b[i]);
-        }
-        if (rc) {
-            (void)rccl().group_end();
-            return rc;
-        }
-        if (rank_form) {
-            if (int r2 = group_end_wait(h0)) return r2;
-        } else {
-            NCCL_CHECK(h0, rccl().group_end());
-        }
-    } else if (n > 1) {
-        // peer copies, ordered as ptx_render_bands orders its halo: a band's rows are ready behind its
+    if (n > 1 || rank_form) {
+        // peer copies are ordered as ptx_render_bands orders its halo: a band's rows are ready behind its
         // frame (temporal mode: behind its dn_temporal); a band copies once its neighbours' are ready ...
+        std::vector<Halo> x(n);
         for (int i = 0; i < n; ++i) {
             ptx_handle *h = hs[i];
-            HIP_CHECK(h, hipSetDevice(h->device));
-            if (!h->ev_dn_ready) HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_dn_ready, hipEventDisableTiming));
-            if (!h->ev_dn_copied) HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_dn_copied, hipEventDisableTiming));
-            HIP_CHECK(h, hipEventRecord(h->ev_dn_ready, h->cur().stream));
-        }
-        for (int i = 0; i < n; ++i) {
-            ptx_handle *h = hs[i];
-            HIP_CHECK(h, hipSetDevice(h->device));
-            const hipStream_t st = h->cur().stream;
-            for (int side = 0; side < 2; ++side) {
-                const uint32_t rows = side == 0 ? b[i].top : b[i].bot;
-                if (!rows) continue;
-                ptx_handle *a = hs[side == 0 ? i - 1 : i + 1];
-                const DnBand &ab = b[side == 0 ? i - 1 : i + 1];
-                const DnRows s = dn_send_rows(a, c, ab, side == 0 ? a->band_h - rows : 0u, rows),
-                             r = dn_recv_rows(h, c, b[i], side == 0);
-                HIP_CHECK(h, hipStreamWaitEvent(st, a->ev_dn_ready, 0));
-                HIP_CHECK(h, hipMemcpyPeerAsync(r.g, h->device, s.g, a->device, r.gb, st));
-                HIP_CHECK(h, hipMemcpyPeerAsync(r.c, h->device, s.c, a->device, r.cb, st));
-                if (r.mb) HIP_CHECK(h, hipMemcpyPeerAsync(r.m, h->device, s.m, a->device, r.mb, st));
+            if (!nccl) {
+                HIP_CHECK(h, hipSetDevice(h->device));
+                if (!h->ev_dn_ready) HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_dn_ready, hipEventDisableTiming));
+                if (!h->ev_dn_copied) HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_dn_copied, hipEventDisableTiming));
+                HIP_CHECK(h, hipEventRecord(h->ev_dn_ready, h->cur().stream));
             }
-            HIP_CHECK(h, hipEventRecord(h->ev_dn_copied, st));
+            x[i] = dn_halo(h, c, b[i]);
+            if (!nccl) x[i].copied = h->ev_dn_copied;
         }
+        if (int rc = exchange_halos(x.data(), n, "denoiser halo")) return rc;
     }
     // ---- every band: the rest of its call on its window
     for (int i = 0; i < n; ++i) {
@@ -980,15 +975,6 @@ int ptx_denoise_bands(ptx_handle *const *hs, int n, const ptx_denoise_params *p)
 // ptx_upsample_bands: full-size band i reads small band i's denoised rows and kUpHalo rows of each
 // of its neighbours' (Upsampling, Bands); the neighbours' guide records are the
 // ones the small band's window has held since its ptx_denoise_bands.
-static constexpr uint32_t kUpHalo = 2;
-// the own rows [r0, r0 + kUpHalo) of small band lo's denoised image / where hi keeps the rows from above or below
-static char *up_send_rows(ptx_handle *lo, uint32_t r0) {
-    return (char *)lo->d_denoised.p + ((size_t)lo->dn_cap_top + r0) * lo->cfg.width * 16u;
-}
-static char *up_recv_rows(ptx_handle *hi, uint32_t w, uint32_t top, bool above) {
-    return (char *)hi->d_up_halo.p + (above ? 0u : (size_t)top * w * 16u);
-}
-
 int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n, const ptx_upsample_params *p) {
     const char *what = "ptx_upsample_bands";
     if (!hi || !hi[0]) return PTX_E_INVALID;
@@ -1002,9 +988,7 @@ int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n, cons
             if ((i < n ? hi[i] : lo[i - n]) == (k < n ? hi[k] : lo[k - n]))
                 return fail(h0, PTX_E_INVALID, "%s: one handle appears twice", what);
     ptx_handle *l0 = lo[0];
-    const bool nccl = l0->comm != nullptr;
-    // the rank form: one pair of a frame whose other bands are other ranks' (every rank makes the call)
-    const bool rank_form = n == 1 && nccl && l0->world > 1;
+    const bool nccl = l0->comm != nullptr, rank_form = is_rank_form(lo, n);
     const auto whole = [](const ptx_handle *h) { return h->cfg.row_begin == 0 && h->band_h == h->cfg.height; };
     if (n == 1 && !rank_form && whole(h0) && whole(l0)) return ptx_upsample(h0, l0, p);
     float sigma_plane;
@@ -1014,41 +998,24 @@ int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n, cons
     if (s < 2u || s > 4u || h0->cfg.width != s * l0->cfg.width || h0->cfg.height != s * h)
         return fail(h0, PTX_E_INVALID, "%s: %ux%u is not 2, 3 or 4 times %ux%u", what, h0->cfg.width, h0->cfg.height,
                     l0->cfg.width, h);
+    const BandSet set{what, lo, n, h0, true, rank_form};
+    const auto few = [&](ptx_handle *to, int band, uint32_t rows) {
+        return fail(to, PTX_E_INVALID, "%s: small band %d has %u rows; every band sends %u", what, band, rows, kUpHalo);
+    };
     for (int i = 0; i < n; ++i) {
         ptx_handle *a = hi[i], *b = lo[i];
-        if (b->cfg.width != l0->cfg.width || b->cfg.height != h || b->cfg.pipeline != l0->cfg.pipeline ||
-            a->cfg.width != h0->cfg.width || a->cfg.height != h0->cfg.height || a->cfg.pipeline != h0->cfg.pipeline)
+        if (a->cfg.width != h0->cfg.width || a->cfg.height != h0->cfg.height || a->cfg.pipeline != h0->cfg.pipeline)
             return fail(h0, PTX_E_INVALID, "%s: pair %d differs in size or pipeline", what, i);
-        if ((b->comm != nullptr) != nccl)
-            return fail(h0, PTX_E_INVALID, "%s: either every small band owns a communicator or none", what);
-        if (nccl && !rank_form && (b->rank != i || b->world != n))
-            return fail(h0, PTX_E_INVALID, "%s: small band %d is rank %d of %d", what, i, b->rank, b->world);
-        if (i && lo[i - 1]->cfg.row_end != b->cfg.row_begin)
-            return fail(h0, PTX_E_INVALID, "%s: small band %d does not start where band %d ends", what, i, i - 1);
+        if (int rc = band_joins(set, i)) return rc;  // (the small bands: the same words for a pair's size)
         if (a->cfg.row_begin != s * b->cfg.row_begin || a->cfg.row_end != s * b->cfg.row_end)
             return fail(h0, PTX_E_INVALID, "%s: pair %d: the full-size band has rows %u..%u, %u times the small band's %u..%u are %u..%u",
                         what, i, a->cfg.row_begin, a->cfg.row_end, s, b->cfg.row_begin, b->cfg.row_end, s * b->cfg.row_begin,
                         s * b->cfg.row_end);
     }
-    if (!rank_form && (l0->cfg.row_begin != 0 || lo[n - 1]->cfg.row_end != h))
-        return fail(h0, PTX_E_INVALID, "%s: the small bands cover rows %u..%u of %u: a band needs the rows above and below it",
-                    what, l0->cfg.row_begin, lo[n - 1]->cfg.row_end, h);
-    if (rank_form) {
-        if ((l0->cfg.row_begin != 0) != (l0->rank > 0) || (l0->cfg.row_end != h) != (l0->rank + 1 < l0->world))
-            return fail(h0, PTX_E_INVALID, "%s: rank %d of %d holds rows %u..%u of %u", what, l0->rank, l0->world,
-                        l0->cfg.row_begin, l0->cfg.row_end, h);
-        for (int k = 0; k < 2; ++k) {
-            if (k == 0 ? l0->rank == 0 : l0->rank + 1 == l0->world) continue;
-            const uint32_t rows = l0->nb_rows[k][1] - l0->nb_rows[k][0];
-            if (rows < kUpHalo)
-                return fail(h0, PTX_E_INVALID, "%s: small band %d has %u rows; every band sends %u", what,
-                            k == 0 ? l0->rank - 1 : l0->rank + 1, rows, kUpHalo);
-        }
-    }
+    if (int rc = bands_cover(set)) return rc;
+    if (int rc = rank_rows(set, kUpHalo, few)) return rc;
     for (int i = 0; i < n; ++i)
-        if (lo[i]->band_h < kUpHalo)
-            return fail(h0, PTX_E_INVALID, "%s: small band %d has %u rows; every band sends %u", what,
-                        rank_form ? l0->rank : i, lo[i]->band_h, kUpHalo);
+        if (int rc = band_rows(set, i, kUpHalo, few)) return rc;
     // then what every pair must share, and a band's halo: kUpHalo rows of the band above and of the band
     // below, where the frame has them, with the guide records lo's last denoise left around its rows
     std::vector<uint32_t> top(n), bot(n);
@@ -1066,10 +1033,9 @@ int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n, cons
         for (int i = 0; i < n; ++i)
             if (int rc = comm_health(lo[i])) return rc;
     // ---- every pair: hi's buffers (first call), and its stream behind the tail of lo's last denoise
-    const size_t w = l0->cfg.width, bytes = (size_t)kUpHalo * w * 16u;
     for (int i = 0; i < n; ++i) {
         HIP_CHECK(h0, hipSetDevice(hi[i]->device));
-        if (int rc = upsample_alloc(hi[i], top[i] + bot[i], (uint32_t)w)) return rc;
+        if (int rc = upsample_alloc(hi[i], top[i] + bot[i], l0->cfg.width)) return rc;
         if (int rc = upsample_source(h0, lo[i])) return rc;
     }
     for (int i = 0; i < n; ++i) {
@@ -1077,50 +1043,9 @@ int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n, cons
         HIP_CHECK(h0, hipStreamWaitEvent(hi[i]->cur().stream, lo[i]->ev_up_src, 0));
     }
     // ---- the exchange, on hi's streams: lo's first / last rows to its neighbours' pairs
-    if (nccl) {  // one group per call, over the small bands' communicators
-        const Rccl &R = rccl();
-        NCCL_CHECK(l0, R.group_start());
-        int rc = PTX_OK;
-        for (int i = 0; i < n && !rc; ++i) {
-            ptx_handle *a = hi[i], *b = lo[i];
-            const hipStream_t st = a->cur().stream;
-            ncclComm_t cm = (ncclComm_t)b->comm;
-            rc = [&]() -> int {
-                HIP_CHECK(h0, hipSetDevice(a->device));
-                for (int side = 0; side < 2; ++side) {
-                    if (!(side == 0 ? top[i] : bot[i])) continue;
-                    const int peer = side == 0 ? b->rank - 1 : b->rank + 1;
-                    NCCL_CHECK(b, R.send(up_send_rows(b, side == 0 ? 0u : b->band_h - kUpHalo), bytes, ncclUint8, peer, cm, st));
-                    NCCL_CHECK(b, R.recv(up_recv_rows(a, (uint32_t)w, top[i], side == 0), bytes, ncclUint8, peer, cm, st));
-                    b->halo_bytes_sent += bytes;
-                }
-                return PTX_OK;
-            }();
-        }
-        if (rc) {
-            (void)R.group_end();
-            return rc;
-        }
-        if (rank_form) {
-            if (int r2 = group_end_wait(l0)) return r2;
-        } else {
-            NCCL_CHECK(l0, R.group_end());
-        }
-    } else {
-        // peer copies: hi[i]'s stream copies once its neighbours' denoises are complete (their ev_up_src)
-        for (int i = 0; i < n; ++i) {
-            ptx_handle *a = hi[i];
-            HIP_CHECK(h0, hipSetDevice(a->device));
-            const hipStream_t st = a->cur().stream;
-            for (int side = 0; side < 2; ++side) {
-                if (!(side == 0 ? top[i] : bot[i])) continue;
-                ptx_handle *nb = lo[side == 0 ? i - 1 : i + 1];
-                HIP_CHECK(h0, hipStreamWaitEvent(st, nb->ev_up_src, 0));
-                HIP_CHECK(h0, hipMemcpyPeerAsync(up_recv_rows(a, (uint32_t)w, top[i], side == 0), a->device,
-                                                 up_send_rows(nb, side == 0 ? nb->band_h - kUpHalo : 0u), nb->device, bytes, st));
-            }
-        }
-    }
+    std::vector<Halo> x(n);
+    for (int i = 0; i < n; ++i) x[i] = up_halo(hi[i], lo[i], h0, top[i], bot[i]);
+    if (int rc = exchange_halos(x.data(), n, "upsampler halo")) return rc;
     // ---- every pair: the two launches, ev_up_done behind them
     hipError_t e = hipSuccess;
     for (int i = 0; i < n; ++i) {
@@ -1161,7 +1086,7 @@ void comm_destroy(ptx_handle *h) {
             gone = true;
         } else if (R.finalize) {
             ncclResult_t r = R.finalize(c);
-            if (r == ncclInProgress) r = comm_wait(c, comm_timeout_s());
+            if (r == ncclInProgress) r = comm_wait(c, comm_deadline());
             if (r != ncclSuccess && R.abort) {
                 (void)R.abort(c);
                 gone = true;

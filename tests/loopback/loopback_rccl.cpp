@@ -19,6 +19,12 @@
 // one thread may post every rank's ops in a single group (ptx_render_bands).  An op still
 // unmatched after LOOPBACK_TIMEOUT_MS (default 20000) fails the group with ncclSystemError and
 // marks the communicator's async error (a rank whose peer never renders).
+//
+// LOOPBACK_GROUP_IN_PROGRESS (read at each call; set and non-empty) makes the group end of a
+// non-blocking communicator: an outermost ncclGroupEnd whose operations all matched returns
+// ncclInProgress, and ncclCommGetAsyncError on each communicator of that group then reports
+// ncclInProgress for its next two calls, ncclSuccess after them.  Nested group ends and failures are
+// as without it.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -37,6 +43,7 @@ struct ncclComm {
     std::string clique;
     int nranks = 0, rank = 0;
     ncclResult_t error = ncclSuccess;
+    int in_progress = 0;  // async-error calls that still report ncclInProgress (LOOPBACK_GROUP_IN_PROGRESS)
     std::map<int, uint64_t> sent, received;  // ops posted per peer (channel sequence numbers)
 };
 
@@ -79,6 +86,11 @@ int timeout_ms() {
     const char *e = std::getenv("LOOPBACK_TIMEOUT_MS");
     const int v = e ? std::atoi(e) : 0;
     return v > 0 ? v : 20000;
+}
+
+bool group_in_progress() {
+    const char *e = std::getenv("LOOPBACK_GROUP_IN_PROGRESS");
+    return e && *e;
 }
 
 // (under g_mu) match every pending send with its recv and enqueue the transfers
@@ -188,6 +200,10 @@ ncclResult_t ncclGroupEnd() {
         if (o->ready) (void)hipEventDestroy(o->ready);
         o->ready = nullptr;
     }
+    if (rc == ncclSuccess && group_in_progress()) {
+        for (auto &o : mine) o->comm->in_progress = 2;
+        rc = ncclInProgress;
+    }
     return rc;
 }
 
@@ -242,6 +258,10 @@ ncclResult_t ncclCommGetAsyncError(ncclComm_t comm, ncclResult_t *err) {
     if (!comm || !err) return ncclInvalidArgument;
     std::lock_guard<std::mutex> lk(g_mu);
     *err = comm->error;
+    if (*err == ncclSuccess && comm->in_progress > 0) {
+        --comm->in_progress;
+        *err = ncclInProgress;
+    }
     return ncclSuccess;
 }
 

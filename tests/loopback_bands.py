@@ -91,22 +91,35 @@ def scenario_split(cs, out):
     bands = [make(cs, W, H, R, a, b) for a, b in zip(cuts, cuts[1:])]
     connect(bands)
     frames = []
+    last = [None]
+
+    def sent():
+        return [b.comm_info()["halo_bytes_sent"] for b in bands]
+
+    def account(before, this_pose):
+        """Halo bytes each band's communicator sent for the frame; whether the pose differs from the last frame's."""
+        changed = last[0] is not None and this_pose != last[0]
+        last[0] = this_pose
+        return {"sent": [a - b for a, b in zip(sent(), before)], "pose_changed": changed}
+
     for f, (loc, yaw, pitch) in enumerate(PATH, start=1):
         pose(one, loc, yaw, pitch)
         one.Render()
         for b in bands:
             pose(b, loc, yaw, pitch)
+        before = sent()
         errs = run_threads([b.Render for b in bands])
         assert not any(errs), errs
-        frames.append({"frame": f, **compare(one, bands)})
+        frames.append({"frame": f, **account(before, (loc, yaw, pitch)), **compare(one, bands)})
     for f, (loc, yaw, pitch) in enumerate([((0.1, 0.05, 5.7), 2.0, 6.0), ((0.1, 0.05, 5.7), 2.0, 6.0),
                                            ((0.0, 0.0, 5.9), 0.0, 0.0)], start=len(PATH) + 1):
         pose(one, loc, yaw, pitch)
         one.Render()
         for b in bands:
             pose(b, loc, yaw, pitch)
+        before = sent()
         Renderer.render_bands(bands)
-        frames.append({"frame": f, "render_bands": True, **compare(one, bands)})
+        frames.append({"frame": f, "render_bands": True, **account(before, (loc, yaw, pitch)), **compare(one, bands)})
     out["split"] = {"frames": frames,
                     "clips_bands": int(sum(b.read_counters()["motion_clips"] for b in bands)),
                     "clips_one": int(one.read_counters()["motion_clips"]),
@@ -188,6 +201,36 @@ def scenario_dead_peer(cs, out, stats):
                         "destroys_healthy": after[3] - mid[3], "finalizes_healthy": after[5] - mid[5]}
 
 
+def scenario_group_in_progress(cs, out, stats):
+    """Non-blocking communicators: every group end returns ncclInProgress and the communicators
+    report it for two more polls (the stub's LOOPBACK_GROUP_IN_PROGRESS).  ptx_render_bands polls
+    them to completion: a still, a moved and a still frame equal one handle, nothing is aborted."""
+    W, H, R = 64, 64, 8
+    one = make(cs, W, H, R)
+    bands = [make(cs, W, H, R, 0, 32), make(cs, W, H, R, 32, 64)]
+    connect(bands)
+    before = stats()
+    frames, err = [], None
+    os.environ["LOOPBACK_GROUP_IN_PROGRESS"] = "1"
+    try:
+        for f, (loc, yaw, pitch) in enumerate([PATH[0], PATH[1], PATH[1]], start=1):
+            pose(one, loc, yaw, pitch)
+            one.Render()
+            for b in bands:
+                pose(b, loc, yaw, pitch)
+            Renderer.render_bands(bands)
+            frames.append({"frame": f, **compare(one, bands)})
+    except Exception as e:  # noqa: BLE001 -- reported to the parent
+        err = f"{type(e).__name__}: {e}"
+    finally:
+        del os.environ["LOOPBACK_GROUP_IN_PROGRESS"]
+    for r in [one] + bands:
+        r.close()
+    after = stats()
+    out["group_in_progress"] = {"error": err, "frames": frames, "aborts": after[4] - before[4],
+                                "destroys": after[3] - before[3]}
+
+
 def main():
     lib = ctypes.CDLL(os.environ["PTX_RCCL_LIB"])
     buf = (ctypes.c_ulonglong * 6)()
@@ -201,6 +244,7 @@ def main():
     scenario_split(cs, out)
     scenario_gi_split(cs, out)
     scenario_reset_one_rank(cs, out)
+    scenario_group_in_progress(cs, out, stats)
     scenario_dead_peer(cs, out, stats)
     out["stub"] = dict(zip(["groups", "pairs", "bytes", "destroys", "aborts", "finalizes"], stats()))
     print(json.dumps(out))

@@ -15,7 +15,11 @@ ptx_render_bands' communicator branch, the 4-band split equals one handle bit fo
 output, spatial output, radiance) after every frame; both count the same clipped pixels; a rank
 that reset its history while the camera moves does not desynchronise the exchange; ReSTIR GI's
 motion pass over three communicator bands equals one handle too; a rank whose peer never renders
-gets an error status within the deadline and its communicator is aborted.
+gets an error status within the deadline and its communicator is aborted.  Every band's
+halo_bytes_sent grows per frame by the static halo's bytes, and the motion halo's on a moved
+frame, through ptx_render and ptx_render_bands alike.  With group ends that return ncclInProgress
+(the stub's LOOPBACK_GROUP_IN_PROGRESS: non-blocking communicators) ptx_render_bands' frames
+still equal one handle and no communicator is aborted.
 """
 import json
 import os
@@ -43,6 +47,22 @@ def test_loopback_communicator_bands():
     assert sp["clips_one"] > 0 and sp["clips_bands"] == sp["clips_one"]
     assert sp["hist_used"] > 0.2
     assert all(c["world"] == 4 and c["halo_bytes_sent"] > 0 for c in sp["comm"])
+    # byte accounting, one rule for ptx_render from threads and for ptx_render_bands: a band with k
+    # neighbours sends k * R rows of G-buffer texels (16 B) and reservoirs (16 * res_u4 = 128 B) per
+    # frame, and k * R rows of history reservoirs more when the camera words differ from the last frame's
+    W, R, texel, reservoir = 96, 12, 16, 16 * 8
+    assert [fr["pose_changed"] for fr in sp["frames"]] == [f not in (1, 7, 10, 12) for f in range(1, 14)]
+    for fr in sp["frames"]:
+        rows = [k * R * W for k in (1, 2, 2, 1)]
+        want = [n * (texel + reservoir) + (n * reservoir if fr["pose_changed"] else 0) for n in rows]
+        assert fr["sent"] == want, (fr, want)
+    # group ends that return ncclInProgress (non-blocking communicators) are polled to completion
+    ip = out["group_in_progress"]
+    assert ip["error"] is None, ip
+    assert len(ip["frames"]) == 3
+    for fr in ip["frames"]:
+        assert fr["history"] == fr["temporal"] == fr["radiance"] == 0, fr
+    assert ip["aborts"] == 0 and ip["destroys"] == 2, ip
     gi = out["gi_split"]
     for fr in gi["frames"]:
         assert fr["history"] == fr["temporal"] == fr["radiance"] == 0, fr
