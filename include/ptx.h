@@ -109,6 +109,9 @@ extern "C" {
 #define PTX_BUF_DENOISE_HISTORY 8 /* band_h * W * 4 f32 {C.rgb, n}: the temporally integrated colour and the history
                                      length (0..255; 0 = no primary hit) of the last temporal ptx_denoise
                                      (read-only; exists after the first temporal call) */
+#define PTX_BUF_UPSAMPLE_HISTORY 9 /* H * W * 4 f32 {H.rgb, n}: the colour ptx_upsample_temporal integrated and the number
+                                      of own samples in it (0..255) after its last call on this (full-size) handle
+                                      (read-only; exists after the first call) */
 
 #define PTX_FLAG_COUNT_WORK 1u     /* count rays / AABB / triangle tests on device (slower)   */
 #define PTX_FLAG_SIMPLE_KERNELS 2u   /* A/B: one thread per pixel, no ray exchange            */
@@ -399,8 +402,65 @@ int ptx_upsample(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_params *p /*
  * and output and hi's G-buffer keep their bits. */
 int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n,
                        const ptx_upsample_params *p /* NULL = defaults */);
+/* Temporal upsampling (Temporal upsampling): super-resolution from small frames whose
+ * sample positions cycle through the s x s full-size pixels of every block.
+ *   ptx_phase_uniform (host arithmetic only: no handle, no GPU) makes the uniform of the W/s x H/s frame
+ * whose pixel (i, j) looks through pixel (s*i + px, s*j + py) of hi_uniform's W x H frame: words 0, 1
+ * become W/s, H/s, the translation column t of the inverse view-projection (words 16..19) becomes
+ * (t + dx*c0) + dy*c1 per component, c0 and c1 its x and y columns (words 4..7, 8..11),
+ * dx = float(2*px - (s-1)) / float(W), dy = float(2*py - (s-1)) / float(H), f32 without contraction;
+ * every other word is copied, and so are words 16..19 when dx = dy = 0 (the centred phase of s = 3:
+ * ptx_upsample's contract).  s in 2, 3, 4, px, py < s, W and H non-zero multiples of s, no null
+ * pointer: PTX_E_INVALID otherwise.  The two arrays may be the same.
+ *   ptx_upsample_temporal is ptx_upsample for a `lo` rendered and denoised through such a uniform, with a
+ * history on `hi`.  ptx_upsample's preconditions hold with one change: lo's uniform words 4..22 equal,
+ * bit for bit, those ptx_phase_uniform makes of hi's current uniform for (s, px, py).  hi pixel (x, y)
+ * sits at fx = float(int(x) - int(px)) / float(s), x0 = floor(fx), ax = fx - x0 (y likewise) of lo:
+ *   current estimate u   ptx_upsample's stages 1 and 2 at these positions; stage 3 is lo's pixel
+ *                        (clamp(x0 + (ax >= 0.5), 0, w-1), clamp(y0 + (ay >= 0.5), 0, h-1));
+ *   own sample d         where (x - px) and (y - py) are multiples of s and lo's pixel
+ *                        ((x - px) / s, (y - py) / s) has hi's key (or neither has a primary hit): that
+ *                        pixel's denoised rgb, and the pixel is "sampled";
+ *   history H_h, n_h     only with the previous call's state on hi (its guide records, its {H, n} and its
+ *                        uniform words 4..22 with their VP): ptx_denoise's temporal lookup -- the same
+ *                        pixel when words 4..22 are that call's bit for bit, else the four pixels around
+ *                        the hit point's projection with bilinear weights; a tap counts inside the image
+ *                        with the same key, any n' >= 0, normals within dot >= 0.9 and within the plane
+ *                        distance r -- H_h = sum(w * H') / sum(w) when a tap counted and sum(w) > 0,
+ *                        n_h = min n'.  A pixel without a primary hit looks only at itself, only when
+ *                        the words are equal, and only its key is compared;
+ *   integration          sampled, history:  n = min(n_h + 1, 255), H = mix(H_h, d, max(1 / n, alpha_min))
+ *                        sampled, none:     H = d, n = 1
+ *                        not sampled, history with n_h >= 1:  H = mix(H_h, u, alpha_fill), n = n_h
+ *                        otherwise:         H = u, n = 0
+ *                        (mix(a, b, t) = a * (1 - t) + b * t).
+ * hi's PTX_BUF_DENOISED is {H.rgb, 1}, PTX_BUF_UPSAMPLE_HISTORY {H.rgb, n}; with this call's guide
+ * records and words 4..22 it is the next call's history (two sets, one read, one written: 96 bytes per
+ * pixel beside the 16 of the output, allocated by the first call, counted in device_bytes).
+ * ptx_upload_scene, ptx_reset_accumulation, ptx_upsample, ptx_upsample_bands, ptx_denoise and
+ * ptx_denoise_bands on hi drop the history (the next call is a first call); ptx_set_frame never does.
+ * After the call hi is no source of a ptx_upsample until it has been denoised or upsampled itself.
+ *   PTX_E_INVALID with the reason in hi's ptx_last_error, before any GPU work: everything ptx_upsample
+ * refuses (band handles: this call has no band form), a phase not below s, a lo whose camera is not that
+ * phase's (the unshifted camera at s = 2 and s = 4 included), an alpha_min that is not 0 or finite and
+ * in (0, 1], an alpha_fill that is not negative-and-finite (the default) or in [0, 1], a non-zero
+ * reserved word.
+ *   Ordering is ptx_upsample's: hi's stream waits for the tail of lo's last denoise, every stream lo can
+ * next run on waits for hi's kernels.  Nothing of lo changes its bits; of hi only these buffers do.
+ * Launches (hi's PTX_STAT_DENOISE): 2 (guide records, dn_upsample_temporal). */
+int ptx_phase_uniform(const uint32_t hi_uniform[PTX_UNIFORM_WORDS], uint32_t s, uint32_t px, uint32_t py,
+                      uint32_t lo_uniform_out[PTX_UNIFORM_WORDS]);
+typedef struct ptx_upsample_temporal_params {
+    float sigma_plane;    /* as ptx_upsample; 0 = default 0.02 */
+    uint32_t px, py;      /* phase of lo's frame, < s */
+    float alpha_min;      /* least weight of a new own sample; 0 = default 0.02 */
+    float alpha_fill;     /* weight of the interpolated estimate on a pixel not sampled this call that has
+                             sampled history; negative = default 0.05, 0 keeps the history as it is */
+    uint32_t reserved[3]; /* zero */
+} ptx_upsample_temporal_params; /* 32 bytes */
+int ptx_upsample_temporal(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_temporal_params *p /* NULL = defaults, phase (0, 0) */);
 /* What ptx_present and ptx_present_async read: PTX_BUF_ACCUM (the default) or PTX_BUF_DENOISED
- * (fails before the first ptx_denoise or ptx_upsample). */
+ * (fails before the first ptx_denoise, ptx_upsample or ptx_upsample_temporal). */
 int ptx_present_source(ptx_handle *h, int which);
 /* What this libptx.so is, as one JSON object in `out` (NUL-terminated, truncated to `bytes`):
  * {"abi": 5, "build": "product" | "ab" (every PTX_AB switch live: the measurement build) | "wgt"

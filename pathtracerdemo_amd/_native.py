@@ -29,6 +29,7 @@ PTX_BUF_DIRECT = 5
 PTX_BUF_DENOISED = 6  # ptx_denoise's output (read-only)
 PTX_BUF_FRAME_COLOR = 7  # the frame's own radiance (PTX_FLAG_FRAME_COLOR handles; read-only)
 PTX_BUF_DENOISE_HISTORY = 8  # {C.rgb, n} of the last temporal ptx_denoise (read-only)
+PTX_BUF_UPSAMPLE_HISTORY = 9  # {H.rgb, n} of the last ptx_upsample_temporal on the full-size handle (read-only)
 PTX_COUNTER_MOTION_CLIP = 6 # word of PTX_BUF_COUNTERS: pixels a band could not reproject (ptx.h)
 PTX_COUNTER_DENOISE_CLIP = 7  # word of PTX_BUF_COUNTERS: pixels with a history candidate past a band's denoiser state
 PTX_COUNTER_REPLAY = 18  # word of PTX_BUF_COUNTERS: pixels PT_4 replayed behind a shading spatial combine
@@ -52,7 +53,7 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_halo_unpack", "ptx_comm_unique_id", "ptx_comm_init", "ptx_comm_init_all", "ptx_render_bands",
             "ptx_row_census", "ptx_comm_info", "ptx_present", "ptx_present_async", "ptx_present_poll",
             "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands",
-            "ptx_upsample", "ptx_upsample_bands"]
+            "ptx_upsample", "ptx_upsample_bands", "ptx_phase_uniform", "ptx_upsample_temporal"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -76,6 +77,11 @@ class PtxDenoiseParams(ctypes.Structure):
 
 class PtxUpsampleParams(ctypes.Structure):
     _fields_ = [("sigma_plane", ctypes.c_float), ("reserved", ctypes.c_uint32 * 7)]
+
+
+class PtxUpsampleTemporalParams(ctypes.Structure):
+    _fields_ = [("sigma_plane", ctypes.c_float), ("px", ctypes.c_uint32), ("py", ctypes.c_uint32),
+                ("alpha_min", ctypes.c_float), ("alpha_fill", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
 
 
 class PtxError(RuntimeError):
@@ -137,6 +143,8 @@ def load(path: str = LIB_PATH):
     lib.ptx_denoise_bands.argtypes = [ctypes.POINTER(H), ctypes.c_int, ctypes.POINTER(PtxDenoiseParams)]
     lib.ptx_upsample.argtypes = [H, H, ctypes.POINTER(PtxUpsampleParams)]
     lib.ptx_upsample_bands.argtypes = [ctypes.POINTER(H), ctypes.POINTER(H), ctypes.c_int, ctypes.POINTER(PtxUpsampleParams)]
+    lib.ptx_phase_uniform.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]
+    lib.ptx_upsample_temporal.argtypes = [H, H, ctypes.POINTER(PtxUpsampleTemporalParams)]
     lib.ptx_present_source.argtypes = [H, ctypes.c_int]
     lib.ptx_run_passes.argtypes = [H, P, ctypes.c_int]
     lib.ptx_halo_rows.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
@@ -171,6 +179,21 @@ def build_info(lib=None) -> dict:
     lib.ptx_build_info(buf, len(buf))
     out = json.loads(buf.value.decode())
     out["path"] = getattr(lib, "_name", LIB_PATH)
+    return out
+
+
+def phase_uniform(hi_uniform, s: int, px: int, py: int, lib=None):
+    """ptx_phase_uniform: the 33-word uniform of the W/s x H/s frame whose pixel (i, j) looks through pixel
+    (s*i + px, s*j + py) of `hi_uniform`'s frame (host arithmetic only; include/ptx.h)."""
+    import numpy as np
+    lib = lib or load()
+    hi = np.ascontiguousarray(hi_uniform, dtype=np.uint32)
+    if hi.shape != (33,) or min(int(s), int(px), int(py)) < 0:
+        raise PtxError("ptx_phase_uniform: a 33-word uniform and non-negative s, px, py")
+    out = np.zeros(33, np.uint32)
+    rc = lib.ptx_phase_uniform(hi.ctypes.data, int(s), int(px), int(py), out.ctypes.data)
+    if rc != PTX_OK:
+        raise PtxError(f"ptx_phase_uniform failed ({rc}): s {s}, phase ({px}, {py}), frame {int(hi[0])}x{int(hi[1])}")
     return out
 
 

@@ -1573,6 +1573,7 @@ static bool buffer_view(ptx_handle *h, int which, DevBuf &v) {
         v.p = h->d_dn_hist[h->dn_set].p ? (char *)h->d_dn_hist[h->dn_set].p + (size_t)h->dn_cap_top * h->cfg.width * 16u : nullptr;
         v.bytes = px * 16u;
         return v.p != nullptr;
+    case PTX_BUF_UPSAMPLE_HISTORY: v.p = h->d_ut_hist[h->ut_set].p; v.bytes = px * 16u; return v.p != nullptr;
     default: return false;
     }
 }
@@ -1746,6 +1747,8 @@ int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b) {
     }
     if (e != hipSuccess) return fail(h, PTX_E_HIP, "denoiser launch: %s", hipGetErrorString(e));
     h->dn_guide_swapped = c.temporal != 0u;  // (ptx_upsample reads this call's guide records)
+    h->dn_guide_stale = false;
+    h->ut_valid = false;  // (PTX_BUF_DENOISED is no longer ptx_upsample_temporal's)
     h->dn_guide_top = b.top;                 // (ptx_upsample_bands: and those of its neighbours' rows)
     h->dn_guide_bot = b.bot;
     h->dn_stream = st;
@@ -1776,12 +1779,15 @@ int upsample_params(ptx_handle *err, const ptx_upsample_params *p, float &sigma_
     return PTX_OK;
 }
 
-int upsample_pair_check(ptx_handle *err, ptx_handle *hi, ptx_handle *lo, uint32_t &s, const char *what) {
+int upsample_pair_check(ptx_handle *err, ptx_handle *hi, ptx_handle *lo, uint32_t &s, const char *what, bool same_camera) {
     for (ptx_handle *h : {hi, lo})
         if (h->cfg.pipeline == PTX_PIPELINE_MCPT)
             return fail(err, PTX_E_INVALID, "%s: the %s handle runs the TEST_MCPT pipeline, which has no G-buffer", what,
                         h == hi ? "full-size" : "small");
     if (hi->device != lo->device) return fail(err, PTX_E_INVALID, "%s: the handles are on devices %d and %d", what, hi->device, lo->device);
+    if (lo->dn_guide_stale)
+        return fail(err, PTX_E_INVALID, "%s: the small handle's denoised image is ptx_upsample_temporal's output, which is no "
+                                        "source (ptx_denoise first)", what);
     if (!lo->d_denoised.p || !(lo->dn_guide_swapped ? lo->d_dn_guide_prev.p : lo->d_dn_guide.p))
         return fail(err, PTX_E_INVALID, "%s: the small handle has no denoised image (ptx_denoise first)", what);
     if (!hi->scene_loaded || !hi->frame_set || !hi->layout_valid || !hi->drawn)
@@ -1790,7 +1796,7 @@ int upsample_pair_check(ptx_handle *err, ptx_handle *hi, ptx_handle *lo, uint32_
     s = W / w;
     if (s < 2u || s > 4u || W != s * w || H != s * hh)
         return fail(err, PTX_E_INVALID, "%s: %ux%u is not 2, 3 or 4 times %ux%u", what, W, H, w, hh);
-    if (std::memcmp(hi->uniform + 4, lo->uniform + 4, 19 * sizeof(uint32_t)) != 0)
+    if (same_camera && std::memcmp(hi->uniform + 4, lo->uniform + 4, 19 * sizeof(uint32_t)) != 0)
         return fail(err, PTX_E_INVALID, "%s: the handles' cameras differ (uniform words 4..22)", what);
     if (hi->n_tris != lo->n_tris || hi->n_nodes != lo->n_nodes || hi->n_inst != lo->n_inst)
         return fail(err, PTX_E_INVALID, "%s: the handles' scenes differ (%u / %u triangles, %u / %u BVH nodes, %u / %u instances)", what,
@@ -1817,6 +1823,8 @@ hipError_t upsample_launch(ptx_handle *hi, ptx_handle *lo, uint32_t s, float sig
     });
     if (e != hipSuccess) return e;
     hi->dn_guide_swapped = false;  // (this handle's output and the guide records it was written under)
+    hi->dn_guide_stale = false;
+    hi->ut_valid = false;  // (PTX_BUF_DENOISED is no longer ptx_upsample_temporal's)
     hi->dn_guide_top = hi->dn_guide_bot = 0u;
     hi->dn_stream = st;
     return hipSuccess;
@@ -1994,6 +2002,7 @@ int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const
     h->drawn = false;
     h->hist_valid = false;
     h->dn_hist_valid = false;  // (the denoiser's history shows the old scene)
+    h->ut_valid = false;       // (and ptx_upsample_temporal's)
     h->cur().init_state_valid = false;
     h->cur().nbr_valid = false;
     for (auto &c : h->ctx) c.surf_valid = false;
@@ -2186,6 +2195,7 @@ int ptx_reset_accumulation(ptx_handle *h) {
     HIP_CHECK(h, hipMemsetAsync(h->d_accum.p, 0, h->d_accum.bytes, h->cur().stream));
     h->hist_valid = false;
     h->dn_hist_valid = false;
+    h->ut_valid = false;
     return PTX_OK;
 }
 
@@ -2215,7 +2225,8 @@ int ptx_get_stats(ptx_handle *h, ptx_stats *out) {
                         c.surf.bytes + h->d_psurf.bytes + c.direct.bytes + h->d_dn_guide.bytes + h->d_dn_work.bytes +
                         h->d_denoised.bytes + h->d_frame_color.bytes + h->d_dn_guide_prev.bytes + h->d_dn_hist[0].bytes +
                         h->d_dn_hist[1].bytes + h->d_dn_mom[0].bytes + h->d_dn_mom[1].bytes + h->d_dn_halo_g.bytes +
-                        h->d_dn_halo_c.bytes + h->d_up_halo.bytes;
+                        h->d_dn_halo_c.bytes + h->d_up_halo.bytes + h->d_ut_guide[0].bytes + h->d_ut_guide[1].bytes +
+                        h->d_ut_hist[0].bytes + h->d_ut_hist[1].bytes;
     return PTX_OK;
 }
 
@@ -2290,6 +2301,8 @@ int ptx_write_buffer(ptx_handle *h, int which, const void *host_src, size_t byte
     if (which == PTX_BUF_DENOISED) return fail(h, PTX_E_INVALID, "the denoised image is ptx_denoise's output: read-only");
     if (which == PTX_BUF_FRAME_COLOR || which == PTX_BUF_DENOISE_HISTORY)
         return fail(h, PTX_E_INVALID, "buffer %d is the renderer's / ptx_denoise's output: read-only", which);
+    if (which == PTX_BUF_UPSAMPLE_HISTORY)
+        return fail(h, PTX_E_INVALID, "buffer %d is ptx_upsample_temporal's output: read-only", which);
     if (!buffer_view(h, which, b) || bytes > b.bytes)
         return fail(h, PTX_E_INVALID, "write of %zu bytes to buffer %d", bytes, which);
     HIP_CHECK(h, copy_sync(h, b.p, host_src, bytes, hipMemcpyHostToDevice));
@@ -2418,6 +2431,116 @@ int ptx_upsample(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_params *p) {
     return PTX_OK;
 }
 
+// The uniform of the W/s x H/s frame that looks through pixel (px, py) of every s x s block of hi's
+// frame: NDC of lo's pixel centre i is hi's of s i + px minus (2 px - (s - 1)) / W, so the translation
+// column of VP^-1 moves by that much of its x column (y likewise); f32, one rounding per operation.
+int ptx_phase_uniform(const uint32_t hi_uniform[PTX_UNIFORM_WORDS], uint32_t s, uint32_t px, uint32_t py,
+                      uint32_t lo_uniform_out[PTX_UNIFORM_WORDS]) {
+    if (!hi_uniform || !lo_uniform_out) return PTX_E_INVALID;
+    if (s < 2u || s > 4u || px >= s || py >= s) return PTX_E_INVALID;
+    const uint32_t W = hi_uniform[0], H = hi_uniform[1];
+    if (W == 0u || H == 0u || W % s != 0u || H % s != 0u) return PTX_E_INVALID;
+    uint32_t u[PTX_UNIFORM_WORDS];
+    std::memcpy(u, hi_uniform, sizeof u);
+    u[0] = W / s;
+    u[1] = H / s;
+    const float dx = (float)(2 * (int)px - ((int)s - 1)) / (float)W, dy = (float)(2 * (int)py - ((int)s - 1)) / (float)H;
+    if (dx != 0.0f || dy != 0.0f) {  // (the centred phase of s = 3 copies the words: t + 0 * c0 would lose a -0)
+#pragma clang fp contract(off)
+        float m[16];
+        std::memcpy(m, u + 4, sizeof m);
+        for (int k = 0; k < 4; ++k) {
+            const float a = dx * m[k], b = dy * m[4 + k];
+            const float t = m[12 + k] + a;
+            m[12 + k] = t + b;
+        }
+        std::memcpy(u + 4, m, sizeof m);
+    }
+    std::memcpy(lo_uniform_out, u, sizeof u);
+    return PTX_OK;
+}
+
+int ptx_upsample_temporal(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_temporal_params *p) {
+    if (!hi || !lo) return PTX_E_INVALID;
+    const char *what = "ptx_upsample_temporal";
+    // ---- refusals, all before any GPU work
+    if (hi == lo) return fail(hi, PTX_E_INVALID, "%s: one handle on both sides", what);
+    float sigma_plane = 0.02f, alpha_min = 0.02f, alpha_fill = 0.05f;
+    uint32_t px = 0u, py = 0u;
+    if (p) {
+        for (uint32_t r : p->reserved)
+            if (r) return fail(hi, PTX_E_INVALID, "%s: a reserved word is not zero", what);
+        if (!std::isfinite(p->sigma_plane) || p->sigma_plane < 0.0f)
+            return fail(hi, PTX_E_INVALID, "%s: sigma_plane %g (finite, >= 0)", what, p->sigma_plane);
+        if (p->sigma_plane != 0.0f) sigma_plane = p->sigma_plane;
+        if (!std::isfinite(p->alpha_min) || p->alpha_min < 0.0f || p->alpha_min > 1.0f)
+            return fail(hi, PTX_E_INVALID, "%s: alpha_min %g (0 = default, else finite and in (0, 1])", what, p->alpha_min);
+        if (p->alpha_min != 0.0f) alpha_min = p->alpha_min;
+        if (!std::isfinite(p->alpha_fill) || p->alpha_fill > 1.0f)
+            return fail(hi, PTX_E_INVALID, "%s: alpha_fill %g (negative = default, else finite and in [0, 1])", what, p->alpha_fill);
+        if (p->alpha_fill >= 0.0f) alpha_fill = p->alpha_fill + 0.0f;  // (a -0 counts as 0)
+        px = p->px;
+        py = p->py;
+    }
+    for (ptx_handle *h : {hi, lo})
+        if (h->cfg.row_begin != 0 || h->band_h != h->cfg.height)
+            return fail(hi, PTX_E_INVALID, "%s: the %s handle is a band (rows %u..%u): bands are not supported by this call", what,
+                        h == hi ? "full-size" : "small", h->cfg.row_begin, h->cfg.row_end);
+    // what a pair must share, but for the camera: lo's is hi's seen through the phase
+    uint32_t s = 0;
+    if (int rc = upsample_pair_check(hi, hi, lo, s, what, false)) return rc;
+    const uint32_t W = hi->cfg.width, H = hi->cfg.height, w = lo->cfg.width;
+    if (px >= s || py >= s) return fail(hi, PTX_E_INVALID, "%s: phase (%u, %u) of a %u x %u block", what, px, py, s, s);
+    uint32_t want[PTX_UNIFORM_WORDS];
+    if (ptx_phase_uniform(hi->uniform, s, px, py, want) != PTX_OK)
+        return fail(hi, PTX_E_INVALID, "%s: no phase uniform of the full-size handle's frame", what);
+    if (std::memcmp(want + 4, lo->uniform + 4, 19 * sizeof(uint32_t)) != 0)
+        return fail(hi, PTX_E_INVALID, "%s: the small handle's camera (uniform words 4..22) is not ptx_phase_uniform's of the "
+                                       "full-size handle's for phase (%u, %u)", what, px, py);
+    // ---- buffers (first call): the output and two sets of {guide records, history}
+    HIP_CHECK(hi, hipSetDevice(hi->device));
+    const size_t npx = (size_t)W * H;
+    if (int rc = alloc_buf(hi, hi->d_denoised, npx * 16u)) return rc;
+    for (int k = 0; k < 2; ++k) {
+        if (int rc = alloc_buf(hi, hi->d_ut_guide[k], npx * 32u)) return rc;
+        if (int rc = alloc_buf(hi, hi->d_ut_hist[k], npx * 16u)) return rc;
+    }
+    // ---- behind the small handle's denoise, the two launches, and the small handle's streams behind
+    // them.  On the current frame's stream, where ptx_denoise enqueues: the state a call on another
+    // frame context's stream left is read after a frame that waited for ev_prev, recorded behind that call.
+    if (int rc = upsample_source(hi, lo)) return rc;
+    const hipStream_t st = hi->cur().stream;
+    HIP_CHECK(hi, hipStreamWaitEvent(st, lo->ev_up_src, 0));
+    const int rd = hi->ut_set, wr = hi->ut_set ^ 1;
+    const uint32_t mode = !hi->ut_valid ? 0u : std::memcmp(hi->ut_camera, hi->uniform + 4, sizeof hi->ut_camera) == 0 ? 1u : 2u;
+    hi->ut_valid = false;  // (until both launches are enqueued)
+    const Scene sc = make_scene(hi);
+    float4 *guide = (float4 *)hi->d_ut_guide[wr].p;
+    const float4 *lguide = (const float4 *)(lo->dn_guide_swapped ? lo->d_dn_guide_prev.p : lo->d_dn_guide.p) +
+                           2u * (size_t)lo->dn_cap_top * w;
+    const float4 *lcolor = (const float4 *)lo->d_denoised.p + (size_t)lo->dn_cap_top * w;
+    hipError_t e = denoise_timed(hi, st, hipSuccess, [&] { return launch_denoise_guide(sc, gbuf_band(hi), guide, sigma_plane, st); });
+    e = denoise_timed(hi, st, e, [&] {
+        return launch_denoise_upsample_temporal(s, W, H, px, py, alpha_min, alpha_fill, mode, hi->ut_vp, guide, lguide, lcolor,
+                                                (const float4 *)hi->d_ut_guide[rd].p, (const float4 *)hi->d_ut_hist[rd].p,
+                                                (float4 *)hi->d_ut_hist[wr].p, (float4 *)hi->d_denoised.p, st);
+    });
+    if (e == hipSuccess) {  // this call is the next one's previous call
+        hi->ut_set = wr;
+        std::memcpy(hi->ut_camera, hi->uniform + 4, sizeof hi->ut_camera);
+        float vpinv[16];
+        std::memcpy(vpinv, hi->ut_camera, sizeof vpinv);
+        mat4_inverse(vpinv, hi->ut_vp);
+        hi->ut_valid = true;
+        hi->dn_guide_stale = true;  // (PTX_BUF_DENOISED's guide records are in the state, not in d_dn_guide)
+        hi->dn_stream = st;
+    }
+    if (int rc = upsample_done(hi, hi)) return rc;
+    if (int rc = upsample_release(hi, lo, hi)) return rc;
+    if (e != hipSuccess) return fail(hi, PTX_E_HIP, "%s launch: %s", what, hipGetErrorString(e));
+    return PTX_OK;
+}
+
 int ptx_present_source(ptx_handle *h, int which) {
     if (!h) return PTX_E_INVALID;
     if (which != PTX_BUF_ACCUM && which != PTX_BUF_DENOISED)
@@ -2498,7 +2621,8 @@ int ptx_destroy(ptx_handle *h) {
                       &h->d_insts, &h->d_mats, &h->d_tverts, &h->d_accum, &h->d_counters, &h->d_qrays, &h->d_qhits, &h->d_hist,
                       &h->d_jstate, &h->d_jres, &h->d_replay, &h->d_psurf, &h->d_census, &h->d_wgt, &h->d_dn_guide, &h->d_dn_work,
                       &h->d_denoised, &h->d_frame_color, &h->d_dn_guide_prev, &h->d_dn_hist[0], &h->d_dn_hist[1], &h->d_dn_mom[0],
-                      &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_up_halo})
+                      &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_up_halo, &h->d_ut_guide[0], &h->d_ut_guide[1],
+                      &h->d_ut_hist[0], &h->d_ut_hist[1]})
         free_buf(*b);
     for (auto &c : h->ctx) {
         for (DevBuf *b : {&c.gbuf, &c.res, &c.direct, &c.nbr, &c.tjstate, &c.tjres, &c.surf, &c.wstate, &c.wrays, &c.wres[0],

@@ -13,6 +13,9 @@
 //   dn_upsample  (ptx_upsample) a denoised image of 1/S the size, written at full size under the
 //                full-size guide records; the tile's footprint in the small image staged in LDS;
 //                dn_upsample_win (ptx_upsample_bands): a band of it from a window of the small image
+//   dn_upsample_temporal  (ptx_upsample_temporal) the same inputs, the small image rendered through one
+//                phase of the S x S block: the own sample and the interpolated estimate integrated with
+//                the previous call's history {H.rgb, n}, gathered like dn_temporal's
 // Every kernel but dn_guide addresses a row window (DnWin): a W x rows image that is the whole
 // frame, or a band with the halo rows ptx_denoise_bands brought from its neighbours, filtered as if
 // it were the whole image; a launch computes rows [c0, c1) of it.
@@ -514,6 +517,181 @@ __global__ __launch_bounds__(kBlock) void dn_upsample_win(uint32_t W, uint32_t H
     dn_upsample_tile<S, true>(W, H, w, h, win, hg, lg, lc, lhalo, out, g0, g1, cv);
 }
 
+// ---------------------------------------------------------------- temporal upsampling (ptx_upsample_temporal)
+// The small image was rendered through phase (px, py): its pixel (i, j) looked through full-size pixel
+// (S i + px, S j + py) (ptx_phase_uniform).  Per full-size pixel: the current estimate u -- dn_upsample's
+// stages 1 and 2 at fx = float(x - px) / S, stage 3 the nearest small pixel --, the pixel's own sample d
+// where the phase's grid has one with its key, and the history {H, n} of the previous call, looked up as
+// dn_temporal looks its history up (a tap counts with any n' >= 0; a pixel without a hit looks only at
+// itself, and only under the same camera); then the table of DESIGN.md §4.5, Temporal upsampling
+// (tests/upsample_temporal_ref.py).  16 consecutive x - px have at most (16 + S - 2) / S + 1 values of
+// x0 = floor((x - px) / S), and every candidate lies in x0 - 1 .. x0 + 2: the staged window is
+// kN x kN from (x0 - 1, y0 - 1) of the tile's first pixel, kN = (16 + S - 2) / S + 4 (12, 9, 8).
+struct UpHistory {
+    float vp[16];  // the previous call's VP (mat4_inverse of the full-size uniform words 4..19 it saw)
+    float alpha_min, alpha_fill;
+    uint32_t mode;  // 0 no history, 1 that call's camera words are this one's, 2 reproject through vp
+    uint32_t px, py;
+};
+__device__ __forceinline__ int up_floor_div(int a, int s) { return a >= 0 ? a / s : -((-a + s - 1) / s); }
+
+template <int S>
+__global__ __launch_bounds__(kBlock) void dn_upsample_temporal(uint32_t W, uint32_t H, uint32_t w, uint32_t h, const UpHistory Hs,
+                                                               const float4 *__restrict__ hg, const float4 *__restrict__ lg,
+                                                               const float4 *__restrict__ lc, const float4 *__restrict__ pguide,
+                                                               const float4 *__restrict__ phist, float4 *__restrict__ hist,
+                                                               float4 *__restrict__ out) {
+    static_assert(S >= 2 && S <= 4, "scales 2, 3, 4");
+    constexpr int kN = (kDnTile + S - 2) / S + 4;
+    static_assert(kN * kN <= kBlock, "one lane per staged entry");
+    __shared__ float4 g0[kN * kN], g1[kN * kN], cv[kN * kN];
+    const int tx = (int)(threadIdx.x & 15u), ty = (int)(threadIdx.x >> 4);
+    const uint32_t bx = blockIdx.x * kDnTile, by = blockIdx.y * kDnTile;
+    const uint32_t x = bx + (uint32_t)tx, y = by + (uint32_t)ty;
+    const bool live = x < W && y < H;
+    const size_t pix = live ? (size_t)y * W + x : 0u;  // (a lane outside the image loads pixel 0, unused)
+    const float4 a = hg[2u * pix], b = hg[2u * pix + 1u];
+    const uint32_t key = asu(a.w);
+    const f3 Pp = rgb(a), Np = rgb(b);
+    // ---- the history's taps k = 2 j + i (j outer), all loads issued ahead of the staging and the tests
+    size_t q[4];
+    float wq[4];
+    bool in[4];
+    float4 qa[4], qb[4], qh[4];
+    if (Hs.mode == 1u) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { q[k] = pix; wq[k] = 1.0f; in[k] = k == 0; }
+    } else if (Hs.mode == 2u) {
+        const float *vp = Hs.vp;
+        const float cx = ((vp[0] * Pp.x + vp[4] * Pp.y) + vp[8] * Pp.z) + vp[12];
+        const float cy = ((vp[1] * Pp.x + vp[5] * Pp.y) + vp[9] * Pp.z) + vp[13];
+        const float cw = ((vp[3] * Pp.x + vp[7] * Pp.y) + vp[11] * Pp.z) + vp[15];
+        const float hx = ((cx / cw + 1.0f) * 0.5f) * (float)W - 0.5f, hy = ((cy / cw + 1.0f) * 0.5f) * (float)H - 0.5f;
+        const float hx0 = __builtin_floorf(hx), hy0 = __builtin_floorf(hy);
+        const float bx1 = hx - hx0, by1 = hy - hy0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = k & 1, j = k >> 1;
+            const float qx = hx0 + (float)i, qy = hy0 + (float)j;
+            // (a NaN or infinite projection compares false: outside)
+            in[k] = key != kDnMiss && cw > 0.0f && qx >= 0.0f && qx < (float)W && qy >= 0.0f && qy < (float)H;
+            q[k] = in[k] ? (size_t)(int)qy * W + (size_t)(int)qx : pix;  // (an outside tap loads the centre, unused)
+            wq[k] = (i ? bx1 : 1.0f - bx1) * (j ? by1 : 1.0f - by1);
+        }
+    }
+    if (Hs.mode != 0u) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            qa[k] = pguide[2u * q[k]];
+            qb[k] = pguide[2u * q[k] + 1u];
+            qh[k] = phist[q[k]];
+        }
+    }
+    // ---- the tile's footprint in the small image
+    const int ox = up_floor_div((int)bx - (int)Hs.px, S) - 1, oy = up_floor_div((int)by - (int)Hs.py, S) - 1;
+    if (threadIdx.x < (uint32_t)(kN * kN)) {
+        const int e = (int)threadIdx.x, gx = ox + e % kN, gy = oy + e / kN;
+        float4 sa = make_float4(0.0f, 0.0f, 0.0f, asf(kUpOutside)), sb = make_float4(0.0f, 0.0f, 0.0f, 0.0f), sc4 = sb;
+        if (gx >= 0 && gy >= 0 && gx < (int)w && gy < (int)h) {
+            const size_t lq = (size_t)gy * w + (size_t)gx;
+            sa = lg[2u * lq];
+            sb = lg[2u * lq + 1u];
+            sc4 = lc[lq];
+        }
+        g0[e] = sa;
+        g1[e] = sb;
+        cv[e] = sc4;
+    }
+    __syncthreads();
+    if (!live) return;
+    // ---- the current estimate u
+    const int dxi = (int)x - (int)Hs.px, dyi = (int)y - (int)Hs.py;
+    const float fx = (float)dxi / (float)S, fy = (float)dyi / (float)S;
+    const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
+    const float ax = fx - x0, ay = fy - y0;
+    // (x0, y0) in the window: 1 .. kN - 3 by the bound above (clamped: no LDS index depends on it holding)
+    const int lx = min(max((int)x0 - ox, 1), kN - 3), ly = min(max((int)y0 - oy, 1), kN - 3);
+    f3 u;
+    float sw = 0.0f;
+    f3 sc = mk(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e = (ly + j) * kN + (lx + i);
+            const float4 ga = g0[e];
+            if (asu(ga.w) != key) continue;
+            const float bw = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
+            const float gm = key == kDnMiss ? 1.0f : dn_gamma(Pp, Np, b.w, rgb(ga), rgb(g1[e]));
+            const float wt = bw * gm;
+            sw += wt;
+            sc = sc + rgb(cv[e]) * wt;
+        }
+    if (sw > 0.0f) {
+        u = sc / sw;
+    } else {
+        uint32_t cnt = 0u;
+        sc = mk(0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int j = -1; j < 3; ++j)
+#pragma unroll
+            for (int i = -1; i < 3; ++i) {
+                const int e = (ly + j) * kN + (lx + i);
+                if (asu(g0[e].w) != key) continue;
+                cnt += 1u;
+                sc = sc + rgb(cv[e]);
+            }
+        if (cnt > 0u) {
+            u = sc / (float)cnt;
+        } else {
+            const int nx = min(max((int)x0 + (ax >= 0.5f ? 1 : 0), 0), (int)w - 1);
+            const int ny = min(max((int)y0 + (ay >= 0.5f ? 1 : 0), 0), (int)h - 1);
+            u = rgb(cv[min(max(ny - oy, 0), kN - 1) * kN + min(max(nx - ox, 0), kN - 1)]);
+        }
+    }
+    // ---- the own sample: on the phase's grid x0 is the small pixel that looked through this one
+    const int es = ly * kN + lx;
+    const bool sampled = dxi >= 0 && dyi >= 0 && dxi % S == 0 && dyi % S == 0 && asu(g0[es].w) == key;
+    const f3 d = rgb(cv[es]);
+    // ---- the history
+    float hw = 0.0f, nh = __builtin_inff();
+    f3 hC = mk(0.0f, 0.0f, 0.0f);
+    bool any = false;
+    if (Hs.mode != 0u) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!in[k] || asu(qa[k].w) != key || !(qh[k].w >= 0.0f)) continue;
+            if (key != kDnMiss) {
+                if (!(dot(Np, rgb(qb[k])) >= 0.9f)) continue;
+                if (!(__builtin_fabsf(dot(Np, rgb(qa[k]) - Pp)) <= b.w)) continue;
+            }
+            hw += wq[k];
+            hC = hC + rgb(qh[k]) * wq[k];
+            nh = fminf(nh, qh[k].w);
+            any = true;
+        }
+    }
+    const bool have = any && hw > 0.0f;
+    // ---- integration
+    f3 Hn;
+    float n;
+    if (sampled && have) {
+        n = fminf(nh + 1.0f, kDnNMax);
+        Hn = mix3(hC / hw, d, fmaxf(1.0f / n, Hs.alpha_min));
+    } else if (sampled) {
+        Hn = d;
+        n = 1.0f;
+    } else if (have && nh >= 1.0f) {
+        Hn = mix3(hC / hw, u, Hs.alpha_fill);
+        n = nh;
+    } else {
+        Hn = u;
+        n = 0.0f;
+    }
+    out[pix] = make_float4(Hn.x, Hn.y, Hn.z, 1.0f);
+    hist[pix] = make_float4(Hn.x, Hn.y, Hn.z, n);
+}
+
 // ---------------------------------------------------------------- launches
 static dim3 dn_grid(uint32_t W, const DnWin &win) {
     return dim3((W + kDnTile - 1) / kDnTile, (win.c1 - win.c0 + kDnTile - 1) / kDnTile);
@@ -574,6 +752,26 @@ hipError_t launch_denoise_upsample(uint32_t s, uint32_t W, uint32_t H, const flo
     if (s == 2u) hipLaunchKernelGGL(dn_upsample<2>, g, bl, 0, st, W, H, w, h, guide_hi, guide_lo, color_lo, out);
     else if (s == 3u) hipLaunchKernelGGL(dn_upsample<3>, g, bl, 0, st, W, H, w, h, guide_hi, guide_lo, color_lo, out);
     else if (s == 4u) hipLaunchKernelGGL(dn_upsample<4>, g, bl, 0, st, W, H, w, h, guide_hi, guide_lo, color_lo, out);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_denoise_upsample_temporal(uint32_t s, uint32_t W, uint32_t H, uint32_t px, uint32_t py, float alpha_min,
+                                            float alpha_fill, uint32_t mode, const float *vp_prev, const float4 *guide_hi,
+                                            const float4 *guide_lo, const float4 *color_lo, const float4 *guide_prev,
+                                            const float4 *hist_prev, float4 *hist, float4 *out, hipStream_t st) {
+    const dim3 g((W + kDnTile - 1) / kDnTile, (H + kDnTile - 1) / kDnTile), bl(kBlock);
+    const uint32_t w = W / s, h = H / s;
+    if (px >= s || py >= s || W != s * w || H != s * h) return hipErrorInvalidValue;  // (the staged window's bound)
+    UpHistory Hs{};
+    for (int i = 0; i < 16; ++i) Hs.vp[i] = vp_prev[i];
+    Hs.alpha_min = alpha_min;
+    Hs.alpha_fill = alpha_fill;
+    Hs.mode = mode;
+    Hs.px = px;
+    Hs.py = py;
+    if (s == 2u) hipLaunchKernelGGL(dn_upsample_temporal<2>, g, bl, 0, st, W, H, w, h, Hs, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
+    else if (s == 3u) hipLaunchKernelGGL(dn_upsample_temporal<3>, g, bl, 0, st, W, H, w, h, Hs, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
+    else if (s == 4u) hipLaunchKernelGGL(dn_upsample_temporal<4>, g, bl, 0, st, W, H, w, h, Hs, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -219,6 +219,17 @@ struct ptx_handle {
     // above, then rows below; allocated by the first call that has any)
     uint32_t dn_guide_top = 0, dn_guide_bot = 0;
     DevBuf d_up_halo;
+    // ptx_upsample_temporal (allocated by its first call on the full-size handle): two sets of guide
+    // records and history {H.rgb, n}; a call reads set ut_set, which the previous call wrote with its
+    // uniform words 4..22 (ut_camera, their VP in ut_vp), and writes the other.  ut_valid: that set is a
+    // history (dropped by an upload, a reset and every other call that writes PTX_BUF_DENOISED).
+    // dn_guide_stale: PTX_BUF_DENOISED is that call's output, whose guide records are not in d_dn_guide
+    // (this handle is no ptx_upsample source until a denoise or ptx_upsample of its own)
+    DevBuf d_ut_guide[2], d_ut_hist[2];
+    int ut_set = 0;
+    bool ut_valid = false, dn_guide_stale = false;
+    uint32_t ut_camera[19] = {0};
+    float ut_vp[16] = {0};
     // the rows [begin, end) of the ranks above and below, as ptx_comm_init's neighbour check received them
     uint32_t nb_rows[2][2] = {{0, 0}, {0, 0}};
     int present_src = PTX_BUF_ACCUM;
@@ -308,7 +319,8 @@ int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b);
 // G-buffer, device, a denoised image and a G-buffer, the scale s, camera, scene); hi's guide records and
 // output (a band's in the layout of denoise_alloc) and, with halo rows, the buffer they are received in
 int upsample_params(ptx_handle *err, const ptx_upsample_params *p, float &sigma_plane, const char *what);
-int upsample_pair_check(ptx_handle *err, ptx_handle *hi, ptx_handle *lo, uint32_t &s, const char *what);
+// (same_camera = false: ptx_upsample_temporal, whose small camera is the full-size one's seen through a phase)
+int upsample_pair_check(ptx_handle *err, ptx_handle *hi, ptx_handle *lo, uint32_t &s, const char *what, bool same_camera = true);
 int upsample_alloc(ptx_handle *hi, uint32_t halo_rows, uint32_t w);
 // ev_up_src at the tail of lo's last denoise; the two launches on hi's stream (lo's window: its rows
 // and `top` / `bot` of its neighbours'); ev_up_done behind them; every stream of lo waits for hi's

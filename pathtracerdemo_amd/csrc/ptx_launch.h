@@ -89,6 +89,13 @@ hipError_t launch_denoise_variance_moments(uint32_t W, const DnWin &win, const f
 // `guide_hi` (s: 2, 3 or 4)
 hipError_t launch_denoise_upsample(uint32_t s, uint32_t W, uint32_t H, const float4 *guide_hi, const float4 *guide_lo,
                                    const float4 *color_lo, float4 *out, hipStream_t st);
+// ptx_upsample_temporal: the same inputs, `color_lo` rendered through phase (px, py) of the s x s block,
+// integrated with the previous call's guide records and history {H.rgb, n} (mode: 0 none, 1 the same
+// camera words, 2 reprojected through vp_prev) into `hist` and, with alpha 1, `out`
+hipError_t launch_denoise_upsample_temporal(uint32_t s, uint32_t W, uint32_t H, uint32_t px, uint32_t py, float alpha_min,
+                                            float alpha_fill, uint32_t mode, const float *vp_prev, const float4 *guide_hi,
+                                            const float4 *guide_lo, const float4 *color_lo, const float4 *guide_prev,
+                                            const float4 *hist_prev, float4 *hist, float4 *out, hipStream_t st);
 // ptx_upsample_bands: rows [Y0, Y1) of the W x H frame (guide_hi and out start at row Y0) from a row
 // window of the small frame: `rows` rows from its row y0 on, where guide_lo starts; the window's rows
 // [o0, o1) are color_lo's (a band's own rows), the rows above and then the rows below them halo_lo's.

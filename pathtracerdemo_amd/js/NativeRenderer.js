@@ -41,7 +41,7 @@ const PIPELINE = { restir: 0, mcpt: 1, reuse: 2, gi: 3 };
 const PASS = { GBUFFER: 0, INIT: 1, FINAL: 2, MCPT: 3, TRACE: 4, WAVE_TRACE: 5, WAVE_LOGIC: 6, FRAME: 7,
   TEMPORAL: 8, SPATIAL: 9, PASS_GROUP: 10 };
 const BUF = { GBUFFER: 0, RESERVOIR: 1, ACCUM: 2, COUNTERS: 3, RESERVOIR_HIST: 4, DIRECT: 5, DENOISED: 6, FRAME_COLOR: 7,
-  DENOISE_HISTORY: 8 };
+  DENOISE_HISTORY: 8, UPSAMPLE_HISTORY: 9 };
 const FLAGS = { COUNT_WORK: 1, SIMPLE_KERNELS: 2, TIME_LAUNCHES: 16, FRAME_COLOR: 512 };
 const UNIFORM_WORDS = 33;
 
@@ -228,6 +228,34 @@ class NativeRenderer {
   Upsample(lo, opts) {
     addon.upsample(this.Handle, lo.Handle, opts || {});
     this.paintDenoised();
+  }
+
+  /**
+   * ptx_upsample_temporal (include/ptx.h): Upsample for a `lo` whose frame was rendered through phase
+   * (px, py) of every s x s block of this renderer's pixels -- lo.SetPhaseOf(this, s, px, py) instead of
+   * its Update() -- integrated over the calls: each small pixel's value goes where it was sampled, the
+   * rest is interpolated, the history follows camera moves.  {px, py, sigmaPlane, alphaMin, alphaFill},
+   * every field optional.  With the source 'denoised' the canvas is painted from the result.
+   */
+  UpsampleTemporal(lo, opts) {
+    addon.upsampleTemporal(this.Handle, lo.Handle, opts || {});
+    this.paintDenoised();
+  }
+
+  /**
+   * ptx_phase_uniform: this (small) renderer's frame looks through pixel (px, py) of every s x s block
+   * of `hi`'s current frame (its Uniform, frame index included); call it where Update() would be.
+   */
+  SetPhaseOf(hi, s, px, py) {
+    this.Uniform = addon.phaseUniform(hi.Uniform, s, px, py);
+    addon.setFrame(this.Handle, this.Uniform);
+  }
+
+  /** {H.rgb, n} of the last UpsampleTemporal(): the integrated colour and own-sample count, RGBA f32. */
+  ReadUpsampleHistory(out) {
+    const img = out || new Float32Array((this.RowEnd - this.RowBegin) * this.Width * 4);
+    addon.readBuffer(this.Handle, BUF.UPSAMPLE_HISTORY, img);
+    return img;
   }
 
   paintDenoised() {

@@ -793,6 +793,75 @@ static napi_value js_upsample(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* upsampleTemporal(hiHandle, loHandle, {px, py, sigmaPlane, alphaMin, alphaFill}): ptx_upsample_temporal --
+ * loHandle's denoised image, rendered through phase (px, py) (phaseUniform), integrated at hiHandle's size
+ * with hiHandle's history (include/ptx.h; px, py default 0, sigmaPlane and alphaMin 0 = the defaults,
+ * alphaFill absent or negative = the default) */
+static napi_value js_upsample_temporal(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    Handle *L = argc >= 2 ? get_handle(env, argv[1]) : NULL;
+    if (!L) return NULL;
+    ptx_upsample_temporal_params p;
+    memset(&p, 0, sizeof p);
+    p.alpha_fill = -1.0f;
+    napi_valuetype t = napi_undefined;
+    if (argc >= 3) napi_typeof(env, argv[2], &t);
+    if (t == napi_object) {
+        bool has_fill = false;
+        float fill = 0.0f;
+        napi_value fv;
+        napi_valuetype ft = napi_undefined;
+        if (napi_has_named_property(env, argv[2], "alphaFill", &has_fill) == napi_ok && has_fill &&
+            napi_get_named_property(env, argv[2], "alphaFill", &fv) == napi_ok)
+            napi_typeof(env, fv, &ft);
+        has_fill = has_fill && ft != napi_undefined && ft != napi_null;
+        if (get_u32_prop(env, argv[2], "px", 0, &p.px) || get_u32_prop(env, argv[2], "py", 0, &p.py) ||
+            get_f32_prop(env, argv[2], "sigmaPlane", &p.sigma_plane) || get_f32_prop(env, argv[2], "alphaMin", &p.alpha_min) ||
+            get_f32_prop(env, argv[2], "alphaFill", &fill)) {
+            napi_throw_type_error(env, NULL, "upsampleTemporal(hiHandle, loHandle, {px, py, sigmaPlane, alphaMin, alphaFill})");
+            return NULL;
+        }
+        if (has_fill) p.alpha_fill = fill;
+    } else if (t != napi_undefined && t != napi_null) {
+        napi_throw_type_error(env, NULL, "upsampleTemporal(hiHandle, loHandle, options): options must be an object");
+        return NULL;
+    }
+    int rc = ptx_upsample_temporal(H->h, L->h, &p);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_upsample_temporal");
+    return NULL;
+}
+
+/* phaseUniform(hiUniform: Uint32Array(33), s, px, py) -> Uint32Array(33): ptx_phase_uniform, the uniform of
+ * the frame of 1/s the size that looks through pixel (px, py) of every s x s block (no handle, no GPU) */
+static napi_value js_phase_uniform(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    void *src;
+    size_t n, es;
+    napi_typedarray_type tt;
+    int32_t v[3] = {0, 0, 0};
+    if (argc < 4 || typed_view(env, argv[0], &src, &n, &es, &tt) || tt != napi_uint32_array || n != PTX_UNIFORM_WORDS ||
+        napi_get_value_int32(env, argv[1], &v[0]) != napi_ok || napi_get_value_int32(env, argv[2], &v[1]) != napi_ok ||
+        napi_get_value_int32(env, argv[3], &v[2]) != napi_ok || v[0] < 0 || v[1] < 0 || v[2] < 0) {
+        napi_throw_type_error(env, NULL, "phaseUniform(hiUniform: Uint32Array(33), s, px, py)");
+        return NULL;
+    }
+    uint32_t out[PTX_UNIFORM_WORDS];
+    int rc = ptx_phase_uniform((const uint32_t *)src, (uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2], out);
+    if (rc != PTX_OK) return throw_ptx(env, NULL, rc, "ptx_phase_uniform");
+    napi_value ab, ta;
+    void *dst;
+    CHECK_NAPI(env, napi_create_arraybuffer(env, sizeof out, &dst, &ab));
+    memcpy(dst, out, sizeof out);
+    CHECK_NAPI(env, napi_create_typedarray(env, napi_uint32_array, PTX_UNIFORM_WORDS, ab, 0, &ta));
+    return ta;
+}
+
 /* presentSource(handle, which): what present / presentAsync show, PTX_BUF_ACCUM (2) or PTX_BUF_DENOISED (6) */
 static napi_value js_present_source(napi_env env, napi_callback_info info) {
     size_t argc = 2;
@@ -851,6 +920,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"denoise", NULL, js_denoise, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"presentSource", NULL, js_present_source, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"upsample", NULL, js_upsample, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"upsampleTemporal", NULL, js_upsample_temporal, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"phaseUniform", NULL, js_phase_uniform, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
     };
     if (napi_define_properties(env, exports, sizeof later / sizeof later[0], later) != napi_ok) return NULL;
     return exports;

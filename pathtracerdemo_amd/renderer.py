@@ -19,6 +19,12 @@ from .scene.camera import Camera
 from .scene.world import CompiledScene, World, serialize_world
 
 
+def phase_uniform(hi_uniform: np.ndarray, s: int, px: int, py: int) -> np.ndarray:
+    """The uniform of the frame of 1/s the size whose pixel (i, j) looks through pixel (s*i + px, s*j + py) of
+    `hi_uniform`'s frame (ptx_phase_uniform: host arithmetic, no renderer and no GPU needed)."""
+    return N.phase_uniform(hi_uniform, s, px, py)
+
+
 class Renderer:
     def __init__(self, width: int, height: int, device: int = -1, pipeline: str = "restir",
                  row_begin: int = 0, row_end: int = 0, count_work: bool = False, variant: str = "wave",
@@ -266,6 +272,27 @@ class Renderer:
         0 = 0.02).  read_denoised() or Present with source "denoised" show the result."""
         p = N.PtxUpsampleParams(sigma_plane=float(sigma_plane))
         self._call("ptx_upsample", self._h, lo._h, ctypes.byref(p))
+
+    def UpsampleTemporal(self, lo: "Renderer", px: int, py: int, sigma_plane: float = 0.0, alpha_min: float = 0.0,
+                         alpha_fill: float = -1.0) -> None:
+        """Upsample for a `lo` whose frame was rendered through phase (px, py) of every s x s block of this
+        renderer's pixels (lo.set_phase_of(self, s, px, py) before its frame), integrated over the calls:
+        each small pixel's value goes where it was sampled, the rest is interpolated, and the history
+        follows camera moves (ptx_upsample_temporal).  alpha_min (0 = 0.02): the least weight of a new own
+        sample; alpha_fill (negative = 0.05, 0 = none): the weight of the interpolated estimate on a pixel
+        not sampled this call.  read_denoised() / read_upsample_history() show the result."""
+        p = N.PtxUpsampleTemporalParams(sigma_plane=float(sigma_plane), px=int(px), py=int(py), alpha_min=float(alpha_min),
+                                        alpha_fill=float(alpha_fill))
+        self._call("ptx_upsample_temporal", self._h, lo._h, ctypes.byref(p))
+
+    def set_phase_of(self, hi: "Renderer", s: int, px: int, py: int) -> None:
+        """Set this (small) renderer's uniform to the one that looks through pixel (px, py) of every s x s
+        block of `hi`'s current frame (ptx_phase_uniform); the frame index is hi's."""
+        self.set_uniform(N.phase_uniform(hi.uniform, s, px, py, self._lib))
+
+    def read_upsample_history(self) -> np.ndarray:
+        """The last UpsampleTemporal's integrated colour and own-sample count (H, W, 4) f32 {H.rgb, n}."""
+        return self._read(N.PTX_BUF_UPSAMPLE_HISTORY, np.float32, 4)
 
     @staticmethod
     def denoise_bands(renderers, out: np.ndarray | None = None, iterations: int = 0, sigma_lum: float = 0.0,

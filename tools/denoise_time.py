@@ -9,6 +9,8 @@
     python tools/denoise_time.py --upsample 2           # ptx_upsample, 960x540 -> 1920x1080 (--no-events / --trace take it too)
     python tools/denoise_time.py --bands 8 --upsample 2 --width 3840 --height 2160   # ptx_upsample_bands, 8 pairs
     python tools/denoise_time.py --displayed-frame [--upsample 2]   # ms per displayed frame under a yawing camera
+    python tools/denoise_time.py --upsample 2 --phases  # ptx_upsample_temporal, the phases cycling (--displayed-frame,
+                                                        # --no-events and --trace take --phases too)
 
 The whole call is timed with device events around it on the handle's stream (a torch stream set
 with ptx_set_stream): the median of --calls calls after --warmup.  The same calls on a
@@ -55,7 +57,8 @@ HBM_PEAK = 8.0e12  # B/s, the datasheet figure the bound is quoted against
 # the new history and moments; its variance pass reads the guide record, history and moments)
 # (upsample: per full-size pixel its guide record and the output; the small image's 48 B per pixel
 # are added by upsample_bound_ms)
-BYTES = {"upsample": 32 + 16, "guide": 16 + 32, "variance": 48 + 16, "atrous": 48 + 16, "temporal": 32 + 16 + 32 + 16 + 8 + 16 + 8,
+# (upsample_temporal: this call's and the previous call's guide records, the history read and written, the output)
+BYTES = {"upsample_temporal": 32 + 32 + 16 + 16 + 16, "upsample": 32 + 16, "guide": 16 + 32, "variance": 48 + 16, "atrous": 48 + 16, "temporal": 32 + 16 + 32 + 16 + 8 + 16 + 8,
          "variance_moments": 32 + 16 + 8 + 16}
 
 
@@ -137,7 +140,27 @@ def measure(args):
 
 def upsample_bound_ms(args, kind):
     px = args.width * args.height
-    return bound_ms(kind, px) + (48 * (px // args.upsample ** 2) / HBM_PEAK * 1e3 if kind == "upsample" else 0.0)
+    return bound_ms(kind, px) + (48 * (px // args.upsample ** 2) / HBM_PEAK * 1e3 if kind.startswith("upsample") else 0.0)
+
+
+def phase_of(args, i):
+    """The phase of call i: every phase of the s x s block in turn, the diagonal first."""
+    s = args.upsample
+    ph = sorted(((px, py) for py in range(s) for px in range(s)), key=lambda p: (p[0] != p[1], p))
+    return ph[i % len(ph)]
+
+
+def upsample_call(args, lo, hi, i):
+    """Call i on the pair: ptx_upsample, or with --phases a small frame through the call's phase, denoised and
+    waited for, then ptx_upsample_temporal (returned as a closure: the part that is timed)."""
+    if not args.phases:
+        return lambda: hi.Upsample(lo)
+    px, py = phase_of(args, i)
+    lo.set_phase_of(hi, args.upsample, px, py)
+    lo.Render()
+    lo.Denoise(iterations=args.iterations)
+    lo.synchronize()
+    return lambda: hi.UpsampleTemporal(lo, px, py)
 
 
 def upsample_pair(args, **kw):
@@ -165,8 +188,9 @@ def upsample_pair(args, **kw):
 
 def measure_upsample(args):
     from pathtracerdemo_amd import _native as N
-    bound = upsample_bound_ms(args, "guide") + upsample_bound_ms(args, "upsample")
-    out = {"what": "ptx_upsample", "scale": args.upsample, "width": args.width, "height": args.height, "scene": args.scene,
+    kind = "upsample_temporal" if args.phases else "upsample"
+    bound = upsample_bound_ms(args, "guide") + upsample_bound_ms(args, kind)
+    out = {"what": "ptx_" + kind, "scale": args.upsample, "width": args.width, "height": args.height, "scene": args.scene,
            "pipeline": args.pipeline, "calls": args.calls, "warmup": args.warmup, "bound_ms_at_8TBs": round(bound, 4)}
     if not args.no_events:
         import torch
@@ -176,8 +200,9 @@ def measure_upsample(args):
         ms = []
         for i in range(args.warmup + args.calls):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            call = upsample_call(args, lo, hi, i)
             a.record(stream)
-            hi.Upsample(lo)
+            call()
             b.record(stream)
             b.synchronize()
             if i >= args.warmup:
@@ -190,8 +215,9 @@ def measure_upsample(args):
     lo, hi = upsample_pair(args, time_launches=True)
     per_call = []
     for i in range(args.warmup + args.calls):
+        call = upsample_call(args, lo, hi, i)
         before = hi.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE]
-        hi.Upsample(lo)
+        call()
         hi.synchronize()
         if i >= args.warmup:
             per_call.append(hi.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE] - before)
@@ -221,7 +247,14 @@ def measure_displayed_frame(args):
             r.GetCamera().set_yaw(args.yaw_step * (i + 1))
             r.ResetFrameCount()
             r.Update()
-        if s:
+        if s and args.phases:
+            px, py = phase_of(args, i)
+            small.set_phase_of(full, s, px, py)  # (instead of the camera its Update() just set)
+            small.Render()
+            small.Denoise(iterations=args.iterations)
+            full.run_pass(N.PTX_PASS_GBUFFER)
+            full.UpsampleTemporal(small, px, py)
+        elif s:
             small.Render()
             small.Denoise(iterations=args.iterations)
             full.run_pass(N.PTX_PASS_GBUFFER)
@@ -235,7 +268,7 @@ def measure_displayed_frame(args):
             ms.append((time.perf_counter() - t0) * 1e3)
     for r in rs:
         r.close()
-    return {"what": "displayed frame, moving camera", "form": f"1/{s} size + G-buffer pass + ptx_upsample" if s else "full size + ptx_denoise",
+    return {"what": "displayed frame, moving camera", "form": f"1/{s} size + G-buffer pass + ptx_upsample{'_temporal, phases cycling' if args.phases else ''}" if s else "full size + ptx_denoise",
             "yaw_step": args.yaw_step, "width": args.width, "height": args.height, "scene": args.scene, "pipeline": args.pipeline,
             "iterations": args.iterations, "frames": args.calls, "warmup": args.warmup,
             "host_ms_per_frame": {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}}
@@ -246,9 +279,9 @@ def upsample_from_trace(args):
     rows = [r for r in csv.DictReader(open(args.trace)) if "dn_" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     calls = [(a, b) for a, b in zip(rows, rows[1:]) if "dn_guide" in a["Kernel_Name"] and "dn_upsample" in b["Kernel_Name"]][-args.calls:]
-    out = {"what": "ptx_upsample per kernel (rocprofv3 kernel trace)", "scale": args.upsample, "width": args.width,
+    out = {"what": f"ptx_upsample{'_temporal' if args.phases else ''} per kernel (rocprofv3 kernel trace)", "scale": args.upsample, "width": args.width,
            "height": args.height, "calls": len(calls), "kernels": []}
-    for k, kind in enumerate(("guide", "upsample")):
+    for k, kind in enumerate(("guide", "upsample_temporal" if args.phases else "upsample")):
         us = statistics.median((int(c[k]["End_Timestamp"]) - int(c[k]["Start_Timestamp"])) / 1e3 for c in calls)
         bound = upsample_bound_ms(args, kind) * 1e3
         out["kernels"].append({"kernel": calls[0][k]["Kernel_Name"].split("(")[0].replace("void ", ""), "median_us": round(us, 2),
@@ -506,6 +539,7 @@ def main():
     ap.add_argument("--yaw-step", type=float, default=0.5, help="--temporal: degrees the camera yaws before every call (0: still)")
     ap.add_argument("--bands", type=int, default=0, help="time ptx_denoise_bands on the frame as this many equal row bands")
     ap.add_argument("--upsample", type=int, default=0, help="time ptx_upsample from 1/S of --width x --height (S: 2, 3 or 4)")
+    ap.add_argument("--phases", action="store_true", help="--upsample: ptx_upsample_temporal on small frames whose phase cycles")
     ap.add_argument("--displayed-frame", action="store_true", help="host ms per displayed frame under a yawing camera")
     ap.add_argument("--no-events", action="store_true", help="only the TIME_LAUNCHES handle (the run a profiler traces)")
     ap.add_argument("--trace", help="a rocprofv3 run_kernel_trace.csv of this script: print per-kernel medians")
