@@ -66,7 +66,7 @@ extern "C" {
 #define PTX_PASS_INIT 1
 #define PTX_PASS_FINAL 2
 #define PTX_PASS_MCPT 3
-#define PTX_PASS_TRACE 4  /* ptx_trace / ptx_trace_device (stats slot only) */
+#define PTX_PASS_TRACE 4  /* ptx_trace / ptx_trace_device / ptx_trace_queries (stats slot only) */
 #define PTX_PASS_TEMPORAL 8  /* reuse: PT_1 reservoir <- previous frame's output (same pixel) */
 #define PTX_PASS_SPATIAL 9   /* reuse: pairwise-MIS resampling over neighbours -> Final's input */
 /* stats-only slots: every launch of the wavefront pipeline's kernels, by kind */
@@ -473,9 +473,25 @@ int ptx_build_info(char *out, size_t bytes);
  * rays: n x {o.x,o.y,o.z,d.x, d.y,d.z,-,-} f32 (32 B); hits: n x {t, flags|inst|mat (u32 bits),
  * prim (u32 bits), bary.x, bary.y, pos.x, pos.y, pos.z} (32 B; flags bit31 = valid).
  * eps_mode 0 = G-buffer epsilons (PT_01), 1 = secondary-pass epsilons (PT_1/PT_4/MCPT).
- * ptx_trace takes host arrays (blocking); ptx_trace_device takes device pointers (async). */
+ * ptx_trace takes host arrays (blocking); ptx_trace_device takes device pointers (async).
+ * Both run a kernel of their own (the lane-refill walk trace_queue_sm, or one thread per ray on a
+ * PTX_FLAG_SIMPLE_KERNELS handle): no frame traces through it. */
 int ptx_trace(ptx_handle *h, const float *rays, float *hits, size_t n, int eps_mode);
 int ptx_trace_device(ptx_handle *h, const void *rays_dev, void *hits_dev, size_t n, int eps_mode);
+/* Arbitrary queries through the kernel the handle's frames trace with (wave_trace: the streamed walk
+ * with the instance cull when the root / instance tables fit LDS, the global-table fallback when they
+ * do not, the counting instance on a PTX_FLAG_COUNT_WORK handle; occ_only != 0: the any-hit instance
+ * of the GI spatial rounds).  Host arrays, blocking.
+ * queries: n x {o.x,o.y,o.z,remain, d.x,d.y,d.z,kind} (32 B, the trace queue's layout); kind is a u32
+ * bit pattern: 0 closest hit (remain unused), 1 Visibility (SH/PT_1_InitPass.wgsl:774-802: the
+ * transmittance over `remain` along d, through at most 5 transmissive hits), 2 occlusion (0 when a hit
+ * has t <= remain, else 1).
+ * results: n x 8 f32 -- a closest query's is ptx_trace's hit record; a Visibility or occlusion query's
+ * word 0 is the transmittance and words 1..7 are 0.
+ * PTX_E_INVALID, before any GPU work: null arrays with n > 0, eps_mode outside 0 / 1, a kind outside
+ * 0..2, occ_only with a query that is not an occlusion query, a PTX_FLAG_SIMPLE_KERNELS or
+ * PTX_FLAG_ROW_CENSUS handle, no scene or no frame.  n = 0 is PTX_OK.  Stats slot PTX_PASS_TRACE. */
+int ptx_trace_queries(ptx_handle *h, const float *queries, float *results, size_t n, int eps_mode, int occ_only);
 /* Use an external hipStream_t (e.g. torch's current stream); NULL restores the own stream. */
 int ptx_set_stream(ptx_handle *h, void *hip_stream);
 int ptx_destroy(ptx_handle *h);

@@ -102,6 +102,7 @@ def lib(variant: str = ""):
                                          ctypes.POINTER(ctypes.c_uint32)]
         _lib.pto_trace.argtypes = [ctypes.POINTER(Inputs), P, P, ctypes.c_size_t, ctypes.c_int,
                                    ctypes.POINTER(Counters)]
+        _lib.pto_visibility.argtypes = _lib.pto_trace.argtypes
         _lib.pto_ray_triangle.argtypes = [P, P, P, P, P, ctypes.c_float]
         _lib.pto_ray_triangle.restype = ctypes.c_float
     return _lib
@@ -176,6 +177,19 @@ class Frame:
         lib(self.variant).pto_trace(ctypes.byref(inp), _ptr(rays), _ptr(hits), len(rays), eps_mode, ctypes.byref(cnt))
         self.counters["trace"] = cnt.as_dict()
         return (hits, self.counters["trace"]) if return_counters else hits
+
+    def visibility(self, queries: np.ndarray, eps_mode: int = 1, return_counters: bool = False):
+        """Transmittances (n,) f32 of (n, 8) f32 queries {o.xyz, remain, d.xyz, kind}: kind (u32 bits) 1 is
+        Visibility's loop on the ray, 2 "a hit with t <= remain blocks" (pto_visibility)."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 8)
+        out = np.zeros(len(queries), np.float32)
+        inp = Inputs(self.uniform.ctypes.data, self.scene.ctypes.data, self.geometry.ctypes.data,
+                     self.accel.ctypes.data)
+        cnt = Counters()
+        lib(self.variant).pto_visibility(ctypes.byref(inp), _ptr(queries), _ptr(out), len(queries), eps_mode,
+                                         ctypes.byref(cnt))
+        self.counters["visibility"] = cnt.as_dict()
+        return (out, self.counters["visibility"]) if return_counters else out
 
     def run(self, pass_id: int, threads: int = 0, rect=None, reservoir: np.ndarray | None = None) -> dict:
         """One pass over `rect` (x0, y0, x1, y1).  PASS_TEMPORAL updates `reservoir` from

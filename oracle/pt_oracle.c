@@ -716,12 +716,10 @@ static v3 l_emit(const ctx *c, const light_sample *XL, const surface *X) {
 }
 
 /* GetMaterialFromHit + Visibility, SH/PT_1_InitPass.wgsl:316-322,774-802 */
-static float visibility(const ctx *c, v3 start, v3 end) {
+/* the loop on a ray: from `o` along `d`, `remain` the distance left to the light */
+static float visibility_ray(const ctx *c, v3 o, v3 d_, float remain) {
     float T = 1.0f;
-    float dist = vlength(vsub(end, start));
-    v3 dir = vdivs(vsub(end, start), dist);
-    ray r = {start, dir};
-    float remain = dist;
+    ray r = {o, d_};
     for (int it = 0; it < 5; ++it) {
         hit h = trace_ray(c, r);
         if (!h.valid || h.t > remain) return T;
@@ -734,6 +732,11 @@ static float visibility(const ctx *c, v3 start, v3 end) {
         r.o = s.pos;
     }
     return 0.0f;
+}
+static float visibility(const ctx *c, v3 start, v3 end) {
+    float dist = vlength(vsub(end, start));
+    v3 dir = vdivs(vsub(end, start), dist);
+    return visibility_ray(c, start, dir, dist);
 }
 
 /* CreateEnvLight, SH/PT_1_InitPass.wgsl:717-730 */
@@ -1681,6 +1684,24 @@ void pto_trace(const pto_inputs *in, const float *rays, float *hits, size_t n, i
         if (h.valid) pos = get_surface(&c, h.s).pos;
         o[0] = h.t; o[1] = f32_of(enc); o[2] = f32_of(h.s.prim); o[3] = h.s.bu;
         o[4] = h.s.bv; o[5] = pos.x; o[6] = pos.y; o[7] = pos.z;
+    }
+}
+
+void pto_visibility(const pto_inputs *in, const float *queries, float *out, size_t n, int eps_mode, pto_counters *cnt) {
+    ctx c;
+    ctx_init(&c, in, eps_mode == 0 ? EPS_GBUFFER : EPS_INIT, cnt);
+    for (size_t i = 0; i < n; ++i) {
+        const float *q = queries + 8 * i;
+        uint32_t kind;
+        memcpy(&kind, q + 7, sizeof kind);
+        const v3 o = V3(q[0], q[1], q[2]), d = V3(q[4], q[5], q[6]);
+        if (kind == 2u) {
+            ray r = {o, d};
+            hit h = trace_ray(&c, r);
+            out[i] = (h.valid && h.t <= q[3]) ? 0.0f : 1.0f;
+        } else {
+            out[i] = visibility_ray(&c, o, d, q[3]);
+        }
     }
 }
 

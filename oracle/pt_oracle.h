@@ -138,6 +138,10 @@ int pto_run_gi_temporal_motion(int nthreads, const pto_inputs *in, int x0, int y
  * rays n x 8 f32 {o, d.x | d.y, d.z, -, -}; hits n x 8 {t, flags|inst|mat, prim, bu, bv, pos}.
  * eps_mode 0 = PT_01 epsilons, 1 = PT_1/PT_4/MCPT epsilons. */
 void pto_trace(const pto_inputs *in, const float *rays, float *hits, size_t n, int eps_mode, pto_counters *cnt);
+/* Visibility on explicit rays: queries n x 8 f32 in the trace queue's layout {o, remain | d, kind
+ * (u32 bits)}; out n f32.  kind 1: Visibility's loop (SH/PT_1_InitPass.wgsl:774-802) from o along d
+ * with `remain` left to the light; kind 2: 0 when the closest hit is valid with t <= remain, else 1. */
+void pto_visibility(const pto_inputs *in, const float *queries, float *out, size_t n, int eps_mode, pto_counters *cnt);
 
 /* Known-answer helpers (SH/PT_1_InitPass.wgsl:810-826). */
 uint32_t pto_pcg(uint32_t seed);

@@ -13,6 +13,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PTX_LIB_PATH") or os.path.join(PKG_DIR, "libptx.so")
 
 PTX_OK = 0
+PTX_E_INVALID = -1  # bad argument / state
 PTX_E_PENDING = -5  # ptx_present_poll: still in flight
 PTX_ABI_VERSION = 5
 PTX_PIPELINE_RESTIR, PTX_PIPELINE_MCPT, PTX_PIPELINE_RESTIR_REUSE, PTX_PIPELINE_RESTIR_GI = 0, 1, 2, 3
@@ -53,7 +54,8 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_halo_unpack", "ptx_comm_unique_id", "ptx_comm_init", "ptx_comm_init_all", "ptx_render_bands",
             "ptx_row_census", "ptx_comm_info", "ptx_present", "ptx_present_async", "ptx_present_poll",
             "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands",
-            "ptx_upsample", "ptx_upsample_bands", "ptx_phase_uniform", "ptx_upsample_temporal"]
+            "ptx_upsample", "ptx_upsample_bands", "ptx_phase_uniform", "ptx_upsample_temporal",
+            "ptx_trace_queries"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -135,6 +137,7 @@ def load(path: str = LIB_PATH):
     lib.ptx_set_stream.argtypes = [H, P]
     lib.ptx_trace.argtypes = [H, P, P, ctypes.c_size_t, ctypes.c_int]
     lib.ptx_trace_device.argtypes = [H, P, P, ctypes.c_size_t, ctypes.c_int]
+    lib.ptx_trace_queries.argtypes = [H, P, P, ctypes.c_size_t, ctypes.c_int, ctypes.c_int]
     lib.ptx_present.argtypes = [H, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, P]
     lib.ptx_present_async.argtypes = [H, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
     lib.ptx_present_poll.argtypes = [H, P, ctypes.c_size_t]

@@ -85,6 +85,9 @@ struct Scene {
     const uint32_t *lights;  // S + U[U_OFF_LIGHT]: STRIDE_LIGHT words per light (get_light)
     const uint32_t *cdf;     // S + U[U_OFF_CDF]: one float per light (light_cdf)
     uint32_t n_inst, n_subs;
+    // the instance cull's scene-wide bounds (inst_may_hit): the largest |world box| coordinate, pad
+    // and per-ray scale of the instances it may cull
+    float cull_box, cull_pad, cull_scale;
     uint32_t width, height, row_begin, row_end;
     unsigned long long *counters;  // nullptr unless PTX_FLAG_COUNT_WORK
     // PTX_FLAG_ROW_CENSUS (counting builds): the work counters go to per-region blocks of
@@ -405,7 +408,8 @@ __device__ __forceinline__ void complete_hit(const Scene &sc, const Ray &ray, Pa
 // lies in a root box for some t in [vx, vy]) runs within the f32 rounding of the transform -- a
 // relative 1e-7 of the coordinates -- of the world box the host maps the local union box to,
 // and the box is padded by 1e-5 of the coordinates' magnitude (>= 40x that rounding) plus
-// 2^-12 * max|o| for the ray origin's own rounding, so such a ray always passes here.  A NaN bound
+// wscale * max|o| for the ray origin's own rounding, plus the local direction's rounding times the
+// ray parameter (below: what a far origin needs), so such a ray always passes here.  A NaN bound
 // (an idle lane) never passes, as no root test would.  The counting build checks the claim on
 // every query it traces (CNT_CULL_MISS: a culled lane whose root pre-filter passed) without
 // culling; the other builds skip an instance when no lane of the wave may reach it.
@@ -419,15 +423,41 @@ constexpr int CNT_DENOISE_CLIP = 7;  // PTX_COUNTER_DENOISE_CLIP: dn_temporal's 
 // the SIMD-utilisation profile's 8 .. 8 + 2 * PROF_REGIONS - 1)
 constexpr int CNT_REPLAY = 18;
 static_assert(CNT_REPLAY >= 8 + 2 * PROF_REGIONS && CNT_REPLAY < kCounterWords, "a free counter word");
-__device__ __forceinline__ bool inst_may_hit(const Inst &I, f3 o, f3 winv, float omax, float vy) {
+__device__ __forceinline__ bool inst_may_hit(const Scene &sc, const Inst &I, f3 o, f3 winv, float omax, float vy) {
     if (!(I.wpad >= 0.0f)) return true;
-    const float p = I.wpad + I.wscale * omax;
+    // p0 covers the rounding of the local origin lo.  The local direction ld = M^-1 (o + d) - M^-1 o
+    // carries the rounding of o + d and of both transforms too -- q <= p0 / 16 in world units (the
+    // sum's 2^-24 (max|o| + 1) and 2 x 4 ulp of the transforms' magnitudes, against p0's 1e-5 of them)
+    // -- and the point lo + s ld is off by s q more: the world box a root test can pass in grows
+    // with the parameter.  A point of the ray inside that box has s (max|d_k| - q) <= |box| + p0 +
+    // max|o|, so with q min|1/d_k| <= 1/128 (p0 min|1/d_k| <= 1/8) the pad p0 + s q is at most
+    // p0 (1 + 1/64 + (|box| + max|o|) min|1/d_k| / 14).  That factor is the ray's alone with the
+    // scene's largest |box|, pad and scale (Scene::cull_box / cull_pad / cull_scale: hoisted out of
+    // the instance loop, one multiply per instance).  In a scene's own range it adds ~1e-3 to the
+    // pad; a ray from 1000 scene diagonals away, whose local direction is off by 1e-3 rad, gets the
+    // ~100 units it needs.  A direction within rounding of zero length is never culled (inf).
+    const float wmin = fminf(fminf(fabsf(winv.x), fabsf(winv.y)), fabsf(winv.z));
+    const float grow = (sc.cull_pad + sc.cull_scale * omax) * wmin <= 0.125f
+                           ? 1.015625f + (sc.cull_box + omax) * (wmin * (1.0f / 14.0f))
+                           : __builtin_inff();
+    const float p = (I.wpad + I.wscale * omax) * grow;
     const float t0x = ((I.wlo[0] - p) - o.x) * winv.x, t1x = ((I.whi[0] + p) - o.x) * winv.x;
     const float t0y = ((I.wlo[1] - p) - o.y) * winv.y, t1y = ((I.whi[1] + p) - o.y) * winv.y;
     const float t0z = ((I.wlo[2] - p) - o.z) * winv.z, t1z = ((I.whi[2] + p) - o.z) * winv.z;
     const float tmin = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z));
     const float tmax = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
     return tmin <= tmax && tmax >= 0.0f && tmin <= vy + fabsf(vy) * 0x1p-10f + 1e-3f;
+}
+// The bound a Visibility / occlusion segment is walked under.  Visibility (SH/PT_1_InitPass.wgsl:
+// 774-802) traces with TraceRay's 1e10 and then drops a hit with t > remain; walking under a bound
+// near `remain` prunes what lies behind the light.  The bound is not `remain` itself: a box is kept
+// when its f32 entry distance is <= the bound, and the entry of a box whose face a triangle lies in
+// can round a few ulp above the triangle's own t, so under `remain` a hit with t == remain (or an
+// ulp below) was pruned where the reference blocks.  With 2^-10 of slack (and 1e-3 absolute, the
+// instance cull's) every hit the reference can accept is reached unless the triangle's t and its
+// boxes' entry disagree by more than that; a closest hit past `remain` is dropped as before.
+__device__ __forceinline__ float vis_bound(float remain) {
+    return fminf(remain + (fabsf(remain) * 0x1p-10f + 1e-3f), 1e10f);
 }
 #ifndef PTX_INST_CULL
 #define PTX_INST_CULL 1
@@ -460,7 +490,9 @@ __device__ __forceinline__ bool inst_may_hit(const Inst &I, f3 o, f3 winv, float
 // ROOTQ: sub-mesh roots of an instance go through one per-lane root queue (incoherent
 // secondary rays); otherwise one root at a time for the whole wave (coherent primary rays,
 // whose lanes mostly enter the same roots).  Same per-lane order and results either way.
-// ANY (occlusion queries): stop at the first accepted hit, position not reconstructed.
+// ANY (occlusion queries): stop at the first accepted hit with t <= t_stop (the query's `remain`;
+// t_max is vis_bound(remain), so a hit between the two is kept as the bound and the walk goes on),
+// position not reconstructed.
 // Until that hit the visit order -- and the bound t_max -- are the closest-hit walk's, so
 // "some hit with t <= t_max" comes out exactly when the closest hit has t <= t_max.
 // COOP (`coop` = this wave's LDS scratch, used when the whole wave entered): the leaves the
@@ -527,7 +559,8 @@ __device__ __forceinline__ int deal_owner(CoopLds coop, uint32_t lane, uint32_t 
 template <bool COUNT, bool PROF = false, bool ROOTQ = true, bool ANY = false, bool COOP = false, bool UNI = false>
 __device__ __forceinline__ Hit trace_core_tab(const Scene &sc, const SubRoot *subs, const Inst *insts, Ray ray,
                                               PassEps eps, uint32_t *stack, uint32_t stride, float t_max = 1e10f,
-                                              CoopLds coop = CoopLds{nullptr}, bool want_pos = true) {
+                                              CoopLds coop = CoopLds{nullptr}, bool want_pos = true,
+                                              float t_stop = 3.0e38f) {
     Prof pf{};
     Hit best;
     best.valid = false;
@@ -546,7 +579,7 @@ __device__ __forceinline__ Hit trace_core_tab(const Scene &sc, const SubRoot *su
     // (with COOP an occluded lane keeps iterating, without work, so the wave stays whole)
     for (uint32_t ii = 0; ii < sc.n_inst && (COOP || !stop); ++ii) {
         const Inst &I = insts[ii];
-        const bool may = !PTX_INST_CULL || !rfin || inst_may_hit(I, ray.o, winv, omax, vy);
+        const bool may = !PTX_INST_CULL || !rfin || inst_may_hit(sc, I, ray.o, winv, omax, vy);
         if (PTX_INST_CULL && !COUNT && wballot(may) == 0ull) continue;  // (wave-uniform)
         if (PROF) pf.hit(PROF_INST);
         // TransformRayWithMat4x4(InRay, M^-1, false), SH/PT_1_InitPass.wgsl:486-496
@@ -715,7 +748,7 @@ __device__ __forceinline__ Hit trace_core_tab(const Scene &sc, const SubRoot *su
                                 best.s.inst = ii;
                                 best.s.mat = grp;
                                 best.s.prim = 0xffffffffu - (uint32_t)key;
-                                if (ANY) {  // occluded: no more work for this lane
+                                if (ANY && !(vy > t_stop)) {  // occluded: no more work for this lane
                                     stop = true;
                                     sp = -1;
                                     mask = 0u;
@@ -746,9 +779,9 @@ __device__ __forceinline__ Hit trace_core_tab(const Scene &sc, const SubRoot *su
                     best.s.inst = ii;
                     best.s.mat = grp;
                     best.s.prim = first + k;
-                    if (ANY) break;
+                    if (ANY && !(vy > t_stop)) break;
                 }
-                if (ANY && best.valid) {  // occluded: drop the rest of the walk
+                if (ANY && best.valid && !(vy > t_stop)) {  // occluded: drop the rest of the walk
                     stop = true;
                     break;
                 }
@@ -788,7 +821,8 @@ __device__ __forceinline__ Hit trace_core_tab(const Scene &sc, const SubRoot *su
 template <bool COUNT, bool PROF = false, bool ANY = false>
 __device__ __forceinline__ Hit trace_core_flat(const Scene &sc, const SubRoot *subs, const Inst *insts, Ray ray,
                                                PassEps eps, uint32_t *stack, uint32_t stride, float t_max,
-                                               CoopLds coop, bool want_pos, uint32_t *dbg = nullptr) {
+                                               CoopLds coop, bool want_pos, uint32_t *dbg = nullptr,
+                                               float t_stop = 3.0e38f) {
     // dbg (diagnostic build, tools/trace_tail.py): wave-level {refill iterations, node-loop
     // iterations, leaf phases, triangle-deal chunks, calls, max slab tests of a lane}
 #ifndef PTX_WG_TIMES
@@ -841,7 +875,7 @@ __device__ __forceinline__ Hit trace_core_flat(const Scene &sc, const SubRoot *s
                                        __builtin_amdgcn_rcpf(ray.d.z));
                     // (COUNT: every instance is walked; the cull is only checked below)
                     while (next < sc.n_inst) {
-                        may = !PTX_INST_CULL || !rfin || inst_may_hit(insts[next], ray.o, winv, omax, vy);
+                        may = !PTX_INST_CULL || !rfin || inst_may_hit(sc, insts[next], ray.o, winv, omax, vy);
                         if (may || COUNT) break;
                         ++next;
                     }
@@ -984,11 +1018,11 @@ __device__ __forceinline__ Hit trace_core_flat(const Scene &sc, const SubRoot *s
                 best.s.inst = cur;
                 best.s.mat = grp;
                 best.s.prim = first + k;
-                if (ANY) break;
+                if (ANY && !(vy > t_stop)) break;
             }
         }
         leaf = 0u;
-        if (ANY && best.valid && !done) {  // occluded: no more work for this lane
+        if (ANY && best.valid && !(vy > t_stop) && !done) {  // occluded: no more work for this lane
             done = true;
             sp = -1;
             mask = 0u;

@@ -48,6 +48,7 @@ struct ptx_handle {
     // derived MI355X layout
     DevBuf d_tris, d_nodes, d_subs, d_insts, d_mats, d_tverts;
     uint32_t n_tris = 0, n_nodes = 0, n_inst = 0, n_subs = 0, max_depth = 0, stack_depth = 0;
+    float cull_box = 0.0f, cull_pad = 0.0f, cull_scale = 0.0f;  // Scene::cull_* (build_layout)
     uint32_t layout_key[8] = {0};
     bool layout_valid = false;
     bool scene_loaded = false;
@@ -80,7 +81,8 @@ struct ptx_handle {
     // records, copied on its stream before the next frame's G-buffer may overwrite them
     bool hist_moved = false;
     DevBuf d_psurf;
-    DevBuf d_qrays, d_qhits;  // staging for ptx_trace (host arrays)
+    DevBuf d_qrays, d_qhits;  // staging for ptx_trace and ptx_trace_queries (host arrays)
+    DevBuf d_qcnt;            // ptx_trace_queries: the segment counts of its one-round queue
     // row census (PTX_FLAG_ROW_CENSUS): kCensusWords u64 per G-buffer tile row + queue slot
     DevBuf d_census;
     uint32_t census_blocks = 0;

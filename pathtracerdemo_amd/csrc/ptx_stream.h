@@ -64,7 +64,7 @@ __device__ __forceinline__ void trace_stream(const Scene &sc, const SubRoot *sub
     int sp = -1;
     uint32_t n_aabb = 0u, n_tri = 0u;
     auto begin_walk = [&]() {  // a query (or a Visibility continuation) from ray.o along ray.d
-        vy = kind != Q_CLOSEST ? fminf(remain, 1e10f) : 1e10f;
+        vy = kind != Q_CLOSEST ? vis_bound(remain) : 1e10f;
         vy_pf = vy;
         rfin = finite3(ray.o) && finite3(ray.d);
         omax = fmaxf(fmaxf(fabsf(ray.o.x), fabsf(ray.o.y)), fabsf(ray.o.z));
@@ -199,7 +199,7 @@ __device__ __forceinline__ void trace_stream(const Scene &sc, const SubRoot *sub
                     const f3 winv = mk(__builtin_amdgcn_rcpf(ray.d.x), __builtin_amdgcn_rcpf(ray.d.y),
                                        __builtin_amdgcn_rcpf(ray.d.z));
                     while (next < sc.n_inst) {
-                        if (!PTX_INST_CULL || !rfin || inst_may_hit(insts[next], ray.o, winv, omax, vy)) break;
+                        if (!PTX_INST_CULL || !rfin || inst_may_hit(sc, insts[next], ray.o, winv, omax, vy)) break;
                         ++next;
                     }
                     if (next >= sc.n_inst) {
@@ -317,11 +317,11 @@ __device__ __forceinline__ void trace_stream(const Scene &sc, const SubRoot *sub
                 binst = cur;
                 bmat = grp;
                 bprim = first + k;
-                if (OCC) break;
+                if (OCC && !(vy > remain)) break;
             }
         }
         leaf = 0u;
-        if (OCC && bvalid && !done) {  // occluded: no more work for this query
+        if (OCC && bvalid && !(vy > remain) && !done) {  // occluded (a hit inside `remain`): no more work for this query
             done = true;
             sp = -1;
             mask = 0u;

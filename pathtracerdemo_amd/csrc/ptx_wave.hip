@@ -34,9 +34,9 @@ namespace ptx {
 
 // ---------------------------------------------------------------- trace queue
 // Workgroup j traces ray segment j of `round`.  A Visibility query is traced with its
-// hit range capped at the remaining distance to the light: Visibility only looks at the
-// closest hit when its t <= remain, and the cap leaves the visit order -- hence which of
-// several equal-t triangles wins -- unchanged for every hit inside the cap.
+// hit range capped just past the remaining distance to the light (vis_bound, ptx_device.h):
+// Visibility only looks at the closest hit when its t <= remain, and the cap leaves the visit
+// order -- hence which of several equal-t triangles wins -- unchanged for every hit inside it.
 // OCC: every query of the launch is Q_OCC (the GI shift's binary visibility): an any-hit
 // walk (trace_core_tab ANY), exact for "is there a hit with t <= remain".
 #ifndef TRACE_OCC_WAVES
@@ -74,13 +74,13 @@ __device__ __forceinline__ void trace_lanes(const Scene &sc, const SubRoot *subs
                                             uint32_t seg, bool active, float4 *res, uint32_t gi, uint32_t *dbg) {
     const bool vis = kind != Q_CLOSEST;
     for (;;) {
-        const float t_max = !active ? __builtin_nanf("") : vis ? fminf(remain, 1e10f) : 1e10f;
+        const float t_max = !active ? __builtin_nanf("") : vis ? vis_bound(remain) : 1e10f;
         // a Visibility hit's position is only needed to restart through a transmissive surface:
         // it is reconstructed below for those lanes only
         Hit h = (LDS_TABLES && FLAT)
-                    ? trace_core_flat<COUNT, PROF, OCC>(sc, subs, insts, r, eps, stack, WB, t_max, coop, !vis, dbg)
+                    ? trace_core_flat<COUNT, PROF, OCC>(sc, subs, insts, r, eps, stack, WB, t_max, coop, !vis, dbg, remain)
                     : trace_core_tab<COUNT, PROF, true, OCC, TRACE_COOP, LDS_TABLES && PTX_NODE_UNI>(
-                          sc, subs, insts, r, eps, stack, WB, t_max, coop, !vis);
+                          sc, subs, insts, r, eps, stack, WB, t_max, coop, !vis, remain);
         if (active && !vis) {
             const uint32_t enc = ((h.valid ? 1u : 0u) << 31) | (h.s.inst << 16) | h.s.mat;
             res[2u * gi] = make_float4(h.t, asf(enc), asf(h.s.prim), h.s.bu);
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(WB) void trace_queue_sm(Scene sc, const float4 *ray
             vit = 0u;
             have = true;
             ii = 0xffffffffu; s = 0u; nsub = 0u; sp = -1; tcount = 0u;
-            vy = vis ? fminf(remain, 1e10f) : 1e10f;
+            vy = vis ? vis_bound(remain) : 1e10f;
             bvalid = false; n_aabb = 0u; n_tri = 0u;
         }
         if (__ballot(have) == 0ull) break;
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(WB) void trace_queue_sm(Scene sc, const float4 *ray
                                 r.o = h.pos;
                                 ++vit;
                                 ii = 0xffffffffu; s = 0u; nsub = 0u; sp = -1; tcount = 0u;
-                                vy = fminf(remain, 1e10f);
+                                vy = vis_bound(remain);
                                 bvalid = false; n_aabb = 0u; n_tri = 0u;
                             }
                         }

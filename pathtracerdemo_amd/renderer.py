@@ -373,6 +373,17 @@ class Renderer:
         self._call("ptx_trace", self._h, rays.ctypes.data, hits.ctypes.data, len(rays), eps_mode)
         return hits
 
+    def trace_queries(self, queries: np.ndarray, eps_mode: int = 1, occ_only: bool = False) -> np.ndarray:
+        """Queries through the kernel this renderer's frames trace with (ptx_trace_queries; trace() runs
+        a kernel of its own): (n, 8) f32 {o.xyz, remain, d.xyz, kind}, kind the u32 bit pattern 0 closest
+        hit, 1 Visibility, 2 occlusion; returns (n, 8) f32 -- trace()'s hit record for a closest query,
+        {transmittance, 0 x 7} for the others.  occ_only: the any-hit kernel (every query of kind 2)."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 8)
+        out = np.zeros_like(queries)
+        self._call("ptx_trace_queries", self._h, queries.ctypes.data, out.ctypes.data, len(queries), int(eps_mode),
+                   1 if occ_only else 0)
+        return out
+
     def reset_stats(self) -> None:
         self._call("ptx_reset_stats", self._h)
 

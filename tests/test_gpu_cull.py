@@ -7,33 +7,15 @@ reference would enter:
     whole frames of every pipeline, on the furnished interior and on a stress scene of chairs
     with anisotropic scales and tilted rotations;
   * the culling build renders those frames bit for bit like the oracle (no cull)."""
-import copy
-import json
 import os
 
 import numpy as np
 import pytest
 
-from helpers import uniform_for
+from helpers import stress_scene, uniform_for
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def stress_scene():
-    """C3 with 11 chairs under anisotropic scales and rotations about all three axes, some of
-    them overlapping the camera's line of sight and each other."""
-    from pathtracerdemo_amd.scene.world import compile_scene
-    d = json.load(open(os.path.join(ROOT, "scenes", "c3_furnished.json")))
-    k = 0
-    for a in d["assets"]:
-        if a.get("meshName") == "Chair" and a["id"] != "chair_instance_0":
-            k += 1
-            t = a["transform"]
-            t["scale"] = [0.02 * (1 + 0.3 * (k % 3)), 0.02 * (1 + 0.2 * (k % 4)), 0.01 + 0.004 * k]
-            t["rotation"] = [11.0 * k, 37.0 * k, -23.0 * k]
-            t["position"] = [t["position"][0] * 0.6, -90 + 15 * (k % 3), t["position"][2] * 0.5 + 40]
-    return compile_scene(d)
 
 
 @pytest.fixture(scope="module")

@@ -4,14 +4,12 @@ the furnished C3 (13 instances, scenes/c3_furnished.json) and C1 with ten window
 LDS fast path (round 1 capped it at 8 instances); C1 with 170 windows (30 KB of tables) takes
 the fallback kernels (global-memory tables, the pass-by-pass G-buffer).  Every pipeline
 matches the oracle bit for bit either way, and a furnished frame splits into bands."""
-import copy
-import json
 import os
 
 import numpy as np
 import pytest
 
-from helpers import uniform_for
+from helpers import huge_tables_scene, many_instances_scene, table_bytes, uniform_for, windows_scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,40 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def many_instances():
-    """DUMMY_SCENE_1 with ten PureWindow instances (11 instances > the 8 staged in LDS)."""
-    from pathtracerdemo_amd.scene.world import compile_scene
-    d = json.load(open(os.path.join(ROOT, "scenes", "dummy_scene_1.json")))
-    win = next(a for a in d["assets"] if a.get("meshName") == "PureWindow")
-    extra = []
-    for k in range(1, 10):
-        w = copy.deepcopy(win)
-        w["id"] = f"window_instance_{k}"
-        w["transform"]["position"] = [-3.0 + 0.6 * k, 0.1 * k, -2.0 - 0.3 * k]
-        extra.append(w)
-    d["assets"] = d["assets"][:2] + extra + d["assets"][2:]
-    cs = compile_scene(d)
-    assert cs.instance_count == 11
-    return cs
-
-
-def windows_scene(n):
-    from pathtracerdemo_amd.scene.world import compile_scene
-    d = json.load(open(os.path.join(ROOT, "scenes", "dummy_scene_1.json")))
-    win = next(a for a in d["assets"] if a.get("meshName") == "PureWindow")
-    extra = []
-    for k in range(1, n):
-        w = copy.deepcopy(win)
-        w["id"] = f"window_instance_{k}"
-        w["transform"]["position"] = [-3.0 + 0.035 * k, 0.006 * k, -2.0 - 0.02 * k]
-        extra.append(w)
-    d["assets"] = d["assets"][:2] + extra + d["assets"][2:]
-    return compile_scene(d)
-
-
-def table_bytes(cs):
-    n_subs = sum(int(cs.scene[cs.offsets["mesh_descriptor"] + 6 * int(cs.scene[33 * i + 32]) + 5])
-                 for i in range(cs.instance_count))
-    return ((32 * n_subs + 15) & ~15) + 144 * cs.instance_count
+    return many_instances_scene()
 
 
 @pytest.fixture(scope="module")
@@ -63,9 +28,7 @@ def furnished():
 
 @pytest.fixture(scope="module")
 def huge_tables():
-    cs = windows_scene(170)
-    assert table_bytes(cs) > 24576  # past kLdsTableMax: the global-table kernels
-    return cs
+    return huge_tables_scene()
 
 
 @pytest.mark.parametrize("which", ["many_instances", "furnished", "huge_tables"])
