@@ -191,17 +191,9 @@ bool has_reuse(const ptx_handle *h) {
 }
 // ReSTIR without reuse pipelines its frames too: frame N + 1's G-buffer + PT_1 beside frame N's
 // PT_4 (C1 1080p, one sequence per context at 768-pixel segments: 1536-1543 Msamples/s against
-// 1406-1414 one frame at a time; PTX_AB=PIPE_RESTIR=0: A/B).  Its timed-alone region keeps static
-// slots, as its pipelined frames do (use_dyn_batches).
+// 1406-1414 one frame at a time; PTX_AB=PIPE_RESTIR=0: A/B).
 static bool restir_pipe() {
     static const bool on = ab_knob("PIPE_RESTIR", 1) != 0;
-    return on;
-}
-// The DI reuse pipeline's whole-image frames on static trace slots with 2 front sequences per
-// context, as ReSTIR's and TEST_MCPT's, instead of dynamic batches with one (PTX_AB=REUSE_STATIC=0:
-// A/B); its segments stay seg_pixels' reuse rule (1024 px at 1080p)
-static bool reuse_static() {
-    static const bool on = ab_knob("REUSE_STATIC", 1) != 0;
     return on;
 }
 // TEST_MCPT likewise: frame N + 1's paths beside frame N's, each frame's colours mixed into the
@@ -573,9 +565,8 @@ int wave_buffers(ptx_handle *h, WaveBufs &w) {
     const size_t cap = per_px * seg_px * slots;
     // (sized by the segment size: re-checked every call, alloc_buf keeps a buffer of the right size)
     const size_t state_b = (size_t)kWaveStateSlots * npix * 16u, act_b = slots * seg_px * jpp * 4u;
-    // counts per round and slot, then the dynamic-batch counters of trace_queue: one per
-    // (tile set, launch sequence, round) -- kDynCounters words
-    const size_t ctr_b = (2u * kWaveMaxRounds * slots + kDynCounters) * 4u;
+    // counts per round and slot (WaveBufs::cnt)
+    const size_t ctr_b = 2u * kWaveMaxRounds * slots * 4u;
     auto &c = h->cur();
     const bool resize = (c.wstate.p && c.wstate.bytes != state_b) || (c.wact[0].p && c.wact[0].bytes != act_b) ||
                         (c.wact[1].p && c.wact[1].bytes != act_b) || (c.wctr.p && c.wctr.bytes != ctr_b) ||
@@ -589,7 +580,7 @@ int wave_buffers(ptx_handle *h, WaveBufs &w) {
     if (int rc = alloc_buf(h, c.wact[1], act_b)) return rc;
     const void *ctr_before = c.wctr.p;
     if (int rc = alloc_buf(h, c.wctr, ctr_b)) return rc;
-    // a new counter buffer starts from zero (the dynamic-batch heads count from it)
+    // a new counter buffer starts from zero: no slot's count is ever uninitialised memory
     if (c.wctr.p != ctr_before) HIP_CHECK(h, memset_sync(h, c.wctr.p, 0, c.wctr.bytes));
     if (h->cfg.pipeline == PTX_PIPELINE_RESTIR_REUSE) {
         // replay lists of the fused spatial combine: lengths start from zero, their consumer
@@ -632,8 +623,6 @@ int wave_buffers(ptx_handle *h, WaveBufs &w) {
     w.act_stride = (uint32_t)(seg_px * jpp);
     w.cnt = (uint32_t *)c.wctr.p;
     w.trace_waves = trace_waves_of(h);
-    static const uint32_t env_split = (uint32_t)ab_knob("TRACE_SPLIT", 0);
-    w.trace_split = env_split >= 1u && env_split <= 16u ? env_split : 1u;
     w.seg_base = 0;
     w.seg_count = w.nseg;
     static const uint32_t cl = (uint32_t)ab_knob("SEG_CLUSTER", 1);  // A/B
@@ -646,7 +635,6 @@ int wave_buffers(ptx_handle *h, WaveBufs &w) {
     w.tile1 = w.ntile1 = 0;
     w.seg_phys = 0;
     w.cnt_stride = (uint32_t)slots;
-    w.dyn = nullptr;  // set per launch sequence (launch_wave_parts)
     return PTX_OK;
 }
 
@@ -936,23 +924,11 @@ static hipError_t join_sequences(ptx_handle *h, int k) {
     return e;
 }
 
-static bool whole_band_sequences(const ptx_handle *h);
-// Dynamic trace batches (trace_queue's launch-wide batch stream) for the whole-band launch
-// sequences of a whole-image handle; a band handle (halo rows or a communicator) keeps one slot per
-// workgroup -- measured at the streamed walk on configs[3]'s 8 re-cut bands, each alone with the
-// exchange proxy: static 2.34-2.50 ms against dynamic 2.45-2.56 (the headline: dynamic 515 against
-// static 506-510 Msamples/s; tools/cl/r5_bands2.sh).  PTX_AB=TRACE_DYN=0 / 1 forces it off / on.
-static bool use_dyn_batches(const ptx_handle *h) {
-    static const int dyn_env = ab_knob("TRACE_DYN", -1);
-    const bool band = h->comm || h->halo_top || h->halo_bot;
-    // (every pipeline keeps static slots in its pipelined frames since late round 5: C1 1080p
-    // ReSTIR 1536-1543 Msamples/s against 1431-1443 with dynamic batches, 1406-1414 one frame at a
-    // time (tools/cl/r5_piperestir2.sh); TEST_MCPT 1663-1668 against 1598-1609, 1509-1515
-    // (r5_pipemcpt.sh); GI C3 at 1792-pixel segments 1104-1107 against 1082 (r5_pipemcpt3.sh);
-    // the reuse headline through REUSE_STATIC (reuse_static))
-    return dyn_env == 1 ||
-           (dyn_env != 0 && whole_band_sequences(h) && !band && h->cfg.pipeline == PTX_PIPELINE_RESTIR_REUSE &&
-            !reuse_static());
+// Launch sequence q of k takes share q of a tile set's `nseg` segments: a contiguous range, the
+// k shares cover every segment once.
+static void seg_share(WaveBufs &part, uint32_t nseg, int q, int k) {
+    part.seg_base = (uint32_t)((uint64_t)nseg * q / k);
+    part.seg_count = (uint32_t)((uint64_t)nseg * (q + 1) / k) - part.seg_base;
 }
 // A band's spatial pass + PT_4 with the halo in flight (PTX_FLAG_HALO_OVERLAP): only the start
 // kernel runs per tile set -- the interior rows' shift jobs (their neighbourhood lies inside the
@@ -972,8 +948,6 @@ static hipError_t spatial_overlap_seq(ptx_handle *h, const Scene &sc, const Wave
     int k = env_bk > 0 && frames_in_flight(h) ? env_bk : 1;
     if (h->cfg.flags & PTX_FLAG_SINGLE_STREAM) k = 1;
     k = std::max(1, std::min<int>({k, ptx_handle::kMaxSplit, (int)interior.nseg, (int)edge.nseg}));
-    const bool use_dyn = use_dyn_batches(h);
-    const size_t dyn0 = 2u * kWaveMaxRounds * (size_t)interior.cnt_stride;
     ReuseArgs A = reuse_args(h, PTX_PASS_SPATIAL);
     const bool fold = A.fold_last && interior.res[2];
     if (!fold) A.fold_last = 0u;
@@ -984,17 +958,11 @@ static hipError_t spatial_overlap_seq(ptx_handle *h, const Scene &sc, const Wave
     for (int q = 0; q < k && e == hipSuccess; ++q) {
         hipStream_t st = q ? h->cur().sub[q] : h->cur().stream;
         WaveBufs wi = interior, we = edge;
-        wi.seg_base = (uint32_t)((uint64_t)interior.nseg * q / k);
-        wi.seg_count = (uint32_t)((uint64_t)interior.nseg * (q + 1) / k) - wi.seg_base;
-        we.seg_base = (uint32_t)((uint64_t)edge.nseg * q / k);
-        we.seg_count = (uint32_t)((uint64_t)edge.nseg * (q + 1) / k) - we.seg_base;
+        seg_share(wi, interior.nseg, q, k);
+        seg_share(we, edge.nseg, q, k);
         wi.seg_phys = interior.seg_phys + E;
         we.seg_phys = interior.seg_phys + E + wi.seg_base + wi.seg_count - we.seg_base;
         E += we.seg_count;
-        wi.dyn = use_dyn ? (uint32_t *)h->cur().wctr.p + dyn0 + (size_t)q * kWaveMaxRounds * kDynRoundWords : nullptr;
-        we.dyn = use_dyn ? (uint32_t *)h->cur().wctr.p + dyn0 +
-                               (size_t)(ptx_handle::kMaxSplit + q) * kWaveMaxRounds * kDynRoundWords
-                         : nullptr;
         if (fold) wi.nres = we.nres = 3;
         WaveBufs wt = wi;  // this sequence's trace launches: both shares' slots
         wt.seg_count = wi.seg_count + we.seg_count;
@@ -1033,7 +1001,7 @@ hipError_t launch_wave_parts(ptx_handle *h, const Scene &sc, const WaveBufs &w, 
         return spatial_overlap_seq(h, sc, w, *then, then_wait);
     static const int env_k = ab_knob("WAVE_STREAMS", 0);
     // pipelined frames: each of the two contexts in flight runs its passes as ONE launch
-    // sequence (whole-band launches, dynamic trace batches); measured at 1080p C3 reuse: 1
+    // sequence (whole-band launches); measured at 1080p C3 reuse: 1
     // stream per context 338 Msamples/s, 2 streams 308, unpipelined 3 streams 320
     // (PTX_AB=PIPE_STREAMS=k: A/B)
     // (ReSTIR without reuse, TEST_MCPT and the reuse pipeline's whole-image frames: 2 per context
@@ -1046,11 +1014,7 @@ hipError_t launch_wave_parts(ptx_handle *h, const Scene &sc, const WaveBufs &w, 
     const bool band_h = h->comm || h->halo_top || h->halo_bot || (h->cfg.flags & PTX_FLAG_HALO_SKIP);
     // (GI keeps one too: its moving camera 779-784 Msamples/s against 753-759 with two, still
     // 1104-1107 against 1111-1113 -- tools/cl/r5_gicam2.sh, r5_pipemcpt3.sh)
-    const int pipe_k = env_pk > 0 ? env_pk
-                       : band_h || h->cfg.pipeline == PTX_PIPELINE_RESTIR_GI ||
-                                 (h->cfg.pipeline == PTX_PIPELINE_RESTIR_REUSE && !reuse_static())
-                           ? 1
-                           : 2;
+    const int pipe_k = env_pk > 0 ? env_pk : band_h || h->cfg.pipeline == PTX_PIPELINE_RESTIR_GI ? 1 : 2;
     int k = frames_in_flight(h) ? pipe_k : env_k > 0 ? env_k : 3;
     // a pipelined frame's spatial pass + PT_4 (the serial back half every frame waits for) as
     // two launch sequences: one half's trace rounds overlap the other's logic kernels.  Same
@@ -1106,17 +1070,7 @@ hipError_t launch_wave_parts(ptx_handle *h, const Scene &sc, const WaveBufs &w, 
             const WaveBufs &ws = set ? *then : w;
             if (set && then_wait && (e = hipStreamWaitEvent(st, then_wait, 0)) != hipSuccess) return e;
             WaveBufs part = ws;
-            // dynamic trace batches: with the pipelined frames' whole-band launch sequences
-            // (+5.6 % there); with three concurrent sequences per frame the other sequences
-            // already fill a launch's tail and the per-workgroup prefix costs more than it
-            // saves (1080p, static vs dynamic: ReSTIR 1240 vs 1081, GI 675 vs 625, TEST_MCPT
-            // 1264 vs 1229 Msamples/s).  PTX_AB=TRACE_DYN=0 / 1 forces it off / on.
-            const bool use_dyn = use_dyn_batches(h);
-            part.dyn = !use_dyn ? nullptr
-                               : (uint32_t *)h->cur().wctr.p + 2u * kWaveMaxRounds * ws.cnt_stride +
-                                     (uint32_t)((set * ptx_handle::kMaxSplit + q) * kWaveMaxRounds) * kDynRoundWords;
-            part.seg_base = (uint32_t)((uint64_t)ws.nseg * q / k);
-            part.seg_count = (uint32_t)((uint64_t)ws.nseg * (q + 1) / k) - part.seg_base;
+            seg_share(part, ws.nseg, q, k);
             if (!part.seg_count) continue;
             for (int i = 0; i < npasses; ++i) {
                 if (passes[i] == PTX_PASS_GBUFFER) {
@@ -1183,15 +1137,10 @@ static hipError_t launch_back_chain(ptx_handle *h, const Scene &sc, const WaveBu
         if (!c.ev_hand[q] && (e = hipEventCreateWithFlags(&c.ev_hand[q], hipEventDisableTiming)) != hipSuccess) return e;
     }
     if ((e = fork_sequences(h, k)) != hipSuccess) return e;
-    const bool use_dyn = use_dyn_batches(h);
     WaveBufs part[ptx_handle::kMaxSplit];
     for (int q = 0; q < k; ++q) {
         part[q] = w;
-        part[q].dyn = !use_dyn ? nullptr
-                               : (uint32_t *)c.wctr.p + 2u * kWaveMaxRounds * w.cnt_stride +
-                                     (uint32_t)(q * kWaveMaxRounds) * kDynRoundWords;
-        part[q].seg_base = (uint32_t)((uint64_t)w.nseg * q / k);
-        part[q].seg_count = (uint32_t)((uint64_t)w.nseg * (q + 1) / k) - part[q].seg_base;
+        seg_share(part[q], w.nseg, q, k);
     }
     for (int q = 0; q < k && with_temporal; ++q) {
         hipStream_t st = q ? c.sub[q] : c.stream;
@@ -1282,17 +1231,6 @@ int motion_prepare(ptx_handle *h, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------- frame pipelining
-// Frames whose passes run as whole-band launch sequences: pipelined frames, or the same
-// handle timed launch by launch (PTX_FLAG_TIME_LAUNCHES + SINGLE_STREAM, bench.py's roofline
-// region), so both run the same trace kernel mode
-static bool whole_band_sequences(const ptx_handle *h) {
-    const uint32_t fl = h->cfg.flags;
-    const bool timed_alone = (fl & PTX_FLAG_TIME_LAUNCHES) && (fl & PTX_FLAG_SINGLE_STREAM);
-    return frames_in_flight(h) ||
-           (timed_alone && (h->cfg.pipeline == PTX_PIPELINE_RESTIR_REUSE || h->cfg.pipeline == PTX_PIPELINE_RESTIR_GI) &&
-            !h->comm && !h->halo_top && !h->halo_bot &&
-            (size_t)h->band_h * h->cfg.width <= ((size_t)4u << 20));
-}
 bool pipelined(const ptx_handle *h) {
     static const bool off = ab_knob("PIPELINE_FRAMES", 1) == 0;  // A/B
     // band handles (a rank's band of a split frame: communicator, halo rows or HALO_SKIP) pipeline
@@ -2580,8 +2518,8 @@ int ptx_trace_device(ptx_handle *h, const void *rays_dev, void *hits_dev, size_t
     resolve_event(t, h);
     Scene sc = make_scene(h);
     HIP_CHECK(h, hipEventRecord(t.start, h->cur().stream));
-    // one thread per ray with the SIMPLE_KERNELS flag; otherwise the lane-refill kernel the
-    // wavefront passes trace with
+    // one thread per ray with the SIMPLE_KERNELS flag; otherwise the lane-refill closest-hit
+    // kernel (trace_queue_sm; the wavefront passes trace with trace_queue)
     const bool simple = (h->cfg.flags & PTX_FLAG_SIMPLE_KERNELS) != 0;
     hipError_t e = (simple ? launch_trace_rays : launch_trace_rays_sm)(
         sc, (const float4 *)rays_dev, (float4 *)hits_dev, (uint32_t)n, eps_mode, h->stack_depth, h->cur().stream);
@@ -2646,7 +2584,6 @@ int ptx_trace_queries(ptx_handle *h, const float *queries, float *results, size_
     w.nres = 2;
     w.cnt = (uint32_t *)h->d_qcnt.p;
     w.trace_waves = trace_waves_of(h);
-    w.trace_split = 1;
     TimedLaunch &t = h->ring[h->ring_pos];
     h->ring_pos = (h->ring_pos + 1) % kEventRing;
     resolve_event(t, h);

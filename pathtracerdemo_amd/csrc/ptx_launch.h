@@ -123,12 +123,6 @@ constexpr uint32_t kStateCs2 = 7u, kStateCs3 = 8u, kStateTsel = 9u;
 constexpr uint32_t kWaveSegPixels = 768u;  // padded pixels per segment (12 8x8 tiles); 768 > 512 > 1024 > 256
 constexpr int kWaveRoundsInit = 3, kWaveRoundsFinal = 3, kWaveRoundsMcpt = 4;
 constexpr int kWaveMaxRounds = 5;
-// dynamic trace batches: per (tile set, launch sequence, round) kDynHeads dequeue heads, one
-// per XCD, each on its own 128-byte line (kDynStride words): one device-scope head saturates
-// at ~88 dequeues/us (MI355X_MICROARCH.md, dequeue), far below a trace launch's demand
-constexpr uint32_t kDynHeads = 8u, kDynStride = 32u;
-constexpr uint32_t kDynRoundWords = kDynHeads * kDynStride;
-constexpr uint32_t kDynCounters = 2u * 4u * kWaveMaxRounds * kDynRoundWords;
 struct WaveBufs {
     float4 *state;       // kWaveStateSlots * npix, SoA
     uint32_t npix;       // pixels of the band
@@ -146,8 +140,6 @@ struct WaveBufs {
     uint32_t act_stride; // list entries per segment (seg_px; seg_px * jobs per pixel for reuse)
     uint32_t *cnt;       // 2 * kWaveMaxRounds * nseg counts
     uint32_t trace_waves;  // trace_queue occupancy target (waves per SIMD; 4 or 5, per pipeline)
-    uint32_t trace_split;  // workgroups per ray segment in trace_queue (batches of 256 rays dealt
-                           // round-robin over them): a segment's rays are not one serial chain
     // Tile set of the launch: virtual tile v (what the segments spread over) is band tile
     // v < ntile0 ? tile0 + v : tile1 + (v - ntile0), for v < ntile0 + ntile1 (8x8 tiles in
     // raster order).  Default: the whole band.  A band's spatial pass runs its interior rows
@@ -157,17 +149,10 @@ struct WaveBufs {
     // storage, count words at cnt[(2r or 2r+1) * cnt_stride + slot]).  Two tile sets in flight
     // at once use disjoint physical slots.
     uint32_t seg_phys, cnt_stride;
-    // Dynamic trace batches (trace_queue): this launch sequence's kWaveMaxRounds groups of
-    // kDynHeads dequeue heads (round r at dyn + r * kDynRoundWords; the logic round that emits
-    // trace round r zeroes them in seg_begin); nullptr = one slot per trace workgroup.
-    uint32_t *dyn;
     // DI reuse pipeline: primary-hit surface records (2 uint4 per pixel, first band row; halo
     // rows at negative / >= npix indices), written by winit_start; nullptr otherwise
     uint4 *surf;
 };
-// dynamic trace batches: one workgroup per slot, at most kDynMaxGroups (the chip holds ~1024 trace
-// workgroups; later ones find the list drained and leave)
-constexpr uint32_t kDynMaxGroups = 1024u, kDynMaxSlots = 4096u;
 // occ_only: every query of the round is Q_OCC (any-hit kernel instance)
 hipError_t wave_trace(const Scene &sc, const WaveBufs &w, int round, int eps_mode, uint32_t stack_depth,
                       hipStream_t s, bool occ_only = false);

@@ -11,7 +11,7 @@
 namespace ptx {
 
 // ---------------------------------------------------------------- streamed lanes
-// The production walk (flattened instances, LDS tables, dynamic batches) with LANE REFILL: a
+// The production walk (flattened instances, LDS tables) with LANE REFILL: a
 // lane whose query is over takes the next query of the wave's batch stream at once, instead of
 // idling until the wave's slowest query of a fixed 64-query batch ends.  The walk is
 // trace_core_flat's -- refill (instance + root pre-filter), node loop, cooperative leaf phase,
@@ -22,29 +22,22 @@ namespace ptx {
 // lanes' new queries.  Lanes whose query is over are finalised (result written, or the
 // Visibility walk continued from the transmissive hit) and given new queries once at least
 // kStreamRefill of them wait, or when no lane is still walking (the result write and the ray
-// load then serve many lanes at once).  The stream (DYN): the launch's 64-query batches
-// (WaveBufs::dyn chunk heads, as trace_queue), taken by the wave as its lanes need them; or
-// (static slots) the workgroup's segment `sj` (`sn` queries), its 64-query batches taken by the
-// workgroup's waves through an LDS counter.
+// load then serve many lanes at once).  The stream: the workgroup's segment `sj` (`sn` queries),
+// its 64-query batches taken by the workgroup's waves, as their lanes need them, through the LDS
+// counter `l_next`.
 #ifndef PTX_STREAM_REFILL
 #define PTX_STREAM_REFILL 32
 #endif
 #ifndef PTX_TRACE_STREAM
 #define PTX_TRACE_STREAM 1
 #endif
-template <bool PROF, bool OCC, bool DYN>
+template <bool PROF, bool OCC>
 __device__ __forceinline__ void trace_stream(const Scene &sc, const SubRoot *subs, const Inst *insts, PassEps eps,
-                                             uint32_t *stack, CoopLds coop, const WaveBufs &w, uint32_t round,
-                                             const uint32_t *pref, uint32_t *heads, float4 *res_all,
-                                             uint32_t *l_next = nullptr, uint32_t sj = 0u, uint32_t sn = 0u) {
+                                             uint32_t *stack, CoopLds coop, const WaveBufs &w, float4 *res_all,
+                                             uint32_t *l_next, uint32_t sj, uint32_t sn) {
     constexpr uint32_t stride = WB;
     const uint32_t lane = __lane_id();
     // ---- the batch stream (wave-uniform)
-    const uint32_t total = DYN ? pref[w.seg_count] : 0u;
-    uint32_t x = blockIdx.x % kDynHeads, visited = 0u;
-    uint32_t c0 = (uint32_t)((uint64_t)total * x / kDynHeads), c1 = (uint32_t)((uint64_t)total * (x + 1u) / kDynHeads);
-    uint32_t bnext = 0u;
-    if (DYN && lane == 0u) bnext = atomicAdd(heads + x * kDynStride, 1u);
     bool src_done = false;
     uint32_t qbase = 0u, qleft = 0u;  // the current batch's untaken queries: ray slots qbase ..
     // ---- this lane's query
@@ -128,7 +121,7 @@ __device__ __forceinline__ void trace_stream(const Scene &sc, const SubRoot *sub
             // new queries for the free lanes, in lane order from the stream
             unsigned long long want = wballot(!has);
             while (want != 0ull && !src_done) {  // wave-uniform
-                if (!DYN && qleft == 0u) {  // the workgroup's next batch of its segment
+                if (qleft == 0u) {  // the workgroup's next batch of its segment
                     uint32_t b = 0u;
                     if (lane == 0u) b = __hip_atomic_fetch_add(l_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
@@ -138,35 +131,6 @@ __device__ __forceinline__ void trace_stream(const Scene &sc, const SubRoot *sub
                     }
                     qbase = sj * w.ray_stride + b * 64u;
                     qleft = min(64u, sn - b * 64u);
-                }
-                if (DYN && qleft == 0u) {
-                    for (;;) {  // the next batch of this wave's chunk, or of the next chunk
-                        const uint32_t bi = c0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)bnext);
-                        if (bi < c1) {
-                            if (lane == 0u) bnext = atomicAdd(heads + x * kDynStride, 1u);  // fetched ahead
-                            uint32_t lo_i = 0u, hi_i = w.seg_count;  // last slot with pref <= bi
-                            while (hi_i - lo_i > 1u) {
-                                const uint32_t mid = (lo_i + hi_i) >> 1;
-                                if (pref[mid] <= bi) lo_i = mid;
-                                else hi_i = mid;
-                            }
-                            const uint32_t j = w.seg_phys + w.seg_base + lo_i;
-                            const uint32_t n = w.cnt[(2u * round + 1u) * w.cnt_stride + j];
-                            const uint32_t i0 = (bi - pref[lo_i]) * 64u;
-                            qbase = j * w.ray_stride + i0;
-                            qleft = min(64u, n - i0);
-                            break;
-                        }
-                        if (++visited == kDynHeads) {
-                            src_done = true;
-                            break;
-                        }
-                        x = (x + 1u) % kDynHeads;
-                        c0 = (uint32_t)((uint64_t)total * x / kDynHeads);
-                        c1 = (uint32_t)((uint64_t)total * (x + 1u) / kDynHeads);
-                        if (lane == 0u) bnext = atomicAdd(heads + x * kDynStride, 1u);
-                    }
-                    if (src_done) break;
                 }
                 const uint32_t m = (uint32_t)__popcll(want), take = min(m, qleft);
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(want >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)want, 0u));

@@ -71,14 +71,14 @@ constexpr uint32_t kFlatMinInstances = 1u;
 template <bool COUNT, bool PROF, bool OCC, bool LDS_TABLES, bool FLAT>
 __device__ __forceinline__ void trace_lanes(const Scene &sc, const SubRoot *subs, const Inst *insts, PassEps eps,
                                             uint32_t *stack, CoopLds coop, Ray r, uint32_t kind, float T, float remain,
-                                            uint32_t seg, bool active, float4 *res, uint32_t gi, uint32_t *dbg) {
+                                            uint32_t seg, bool active, float4 *res, uint32_t gi) {
     const bool vis = kind != Q_CLOSEST;
     for (;;) {
         const float t_max = !active ? __builtin_nanf("") : vis ? vis_bound(remain) : 1e10f;
         // a Visibility hit's position is only needed to restart through a transmissive surface:
         // it is reconstructed below for those lanes only
         Hit h = (LDS_TABLES && FLAT)
-                    ? trace_core_flat<COUNT, PROF, OCC>(sc, subs, insts, r, eps, stack, WB, t_max, coop, !vis, dbg, remain)
+                    ? trace_core_flat<COUNT, PROF, OCC>(sc, subs, insts, r, eps, stack, WB, t_max, coop, !vis, remain)
                     : trace_core_tab<COUNT, PROF, true, OCC, TRACE_COOP, LDS_TABLES && PTX_NODE_UNI>(
                           sc, subs, insts, r, eps, stack, WB, t_max, coop, !vis, remain);
         if (active && !vis) {
@@ -116,7 +116,7 @@ __device__ __forceinline__ void trace_lanes(const Scene &sc, const SubRoot *subs
 template <bool COUNT, bool PROF, bool OCC, bool LDS_TABLES = false, bool FLAT = false>
 __device__ __forceinline__ void trace_batch(const Scene &sc, const SubRoot *subs, const Inst *insts, PassEps eps,
                                             uint32_t *stack, CoopLds coop, float4 *res_all, const float4 *rays_all,
-                                            uint32_t gbase, uint32_t i, bool active, uint32_t *dbg = nullptr) {
+                                            uint32_t gbase, uint32_t i, bool active) {
     const uint32_t gi = gbase + i;
     float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
     if (active) {
@@ -124,183 +124,62 @@ __device__ __forceinline__ void trace_batch(const Scene &sc, const SubRoot *subs
         b = rays_all[2u * gi + 1u];
     }
     trace_lanes<COUNT, PROF, OCC, LDS_TABLES, FLAT>(sc, subs, insts, eps, stack, coop, Ray{mk(a.x, a.y, a.z), mk(b.x, b.y, b.z)},
-                                                    asu(b.w), 1.0f, a.w, 0u, active, res_all, gi, dbg);
+                                                    asu(b.w), 1.0f, a.w, 0u, active, res_all, gi);
 }
 }  // namespace ptx
 #include "ptx_stream.h"
 namespace ptx {
 
-// Dynamic batches (WaveBufs::dyn): the launch's rays -- every slot of the launch's segment
-// range -- are one list of 64-query batches (a slot's batch k = its queries 64k .. 64k+63,
-// consecutive entries of one tile, coherent), and every wave takes the next batch from a
-// per-(part, round) counter until the list is exhausted.  A launch then ends when the
-// last batch ends, not when the heaviest segment does: with a fixed slot per workgroup
-// the spatial pass's largest trace launch ran its median workgroup 1.14 ms and its slowest
-// 1.90 ms (tools/wave_timeline.py).  Each query's result goes to its own slot, so the
-// assignment of batches to waves changes nothing in the output.  The workgroup's first
-// (seg_count + 1) dynamic-LDS words hold the exclusive prefix of the slots' batch counts.
-__device__ __forceinline__ uint32_t dyn_prefix_words(const WaveBufs &w) { return (w.seg_count + 4u) & ~3u; }
-__device__ __forceinline__ void dyn_prefix(const WaveBufs &w, uint32_t round, uint32_t *pref) {
-    __shared__ uint32_t l_wsum[WB / 64];
-    const uint32_t n = w.seg_count, per = (n + WB - 1u) / WB, t0 = threadIdx.x * per;
-    const uint32_t *cnt = w.cnt + (2u * round + 1u) * w.cnt_stride + w.seg_phys + w.seg_base;
-    uint32_t loc = 0u;
-    for (uint32_t k = 0; k < per && t0 + k < n; ++k) loc += (cnt[t0 + k] + 63u) >> 6;
-    uint32_t total;
-    uint32_t ex = wave_scan(loc, total);
-    if (__lane_id() == 63u) l_wsum[threadIdx.x >> 6] = ex + loc;
-    __syncthreads();
-    for (uint32_t q = 0; q < (threadIdx.x >> 6); ++q) ex += l_wsum[q];
-    for (uint32_t k = 0; k < per && t0 + k < n; ++k) {
-        pref[t0 + k] = ex;
-        ex += (cnt[t0 + k] + 63u) >> 6;
-    }
-    if (threadIdx.x == WB - 1u) pref[n] = ex;
-    __syncthreads();
-}
-
-// The dynamic trace batches (WaveBufs::dyn) and split segments (WaveBufs::trace_split) are A/B
-// modes of the measurement build since late round 5 (every production frame traces static slots,
-// one workgroup per segment: use_dyn_batches): the shipped kernel is compiled without those
-// branches (their batch walks spilled 28 B per lane into the streamed static path).
-#ifndef PTX_TRACE_AB_PATHS
-#ifdef PTX_AB_BUILD
-#define PTX_TRACE_AB_PATHS 1
-#else
-#define PTX_TRACE_AB_PATHS 0
-#endif
-#endif
-constexpr bool kAbBuild = PTX_TRACE_AB_PATHS != 0;
 template <bool COUNT, int WAVES, bool PROF = false, bool LDS_TABLES = true, bool OCC = false, bool FLAT = false>
 __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(WAVES, 8)))
 void trace_queue(Scene sc, WaveBufs w, uint32_t round, PassEps eps) {
     PTX_WAVE_TIMER(sc, KID_TRACE | (w.seg_base ? 0x80u : 0u));
-    // dynamic LDS: [scene tables (LDS_TABLES)] [batch prefix (dynamic batches)] [stacks]
+    // dynamic LDS: [scene tables (LDS_TABLES)] [stacks]
     extern __shared__ __attribute__((aligned(16))) uint32_t wstack[];
-    const bool dyn = kAbBuild && !COUNT && w.dyn != nullptr;
     const uint32_t tw = LDS_TABLES ? tables_lds_bytes(sc) / 4u : 0u;
-    uint32_t *pref = wstack + tw;
-    uint32_t *stack = wstack + tw + (dyn ? dyn_prefix_words(w) : 0u) + threadIdx.x;
+    uint32_t *stack = wstack + tw + threadIdx.x;
     __shared__ unsigned long long c_key[WB];
     __shared__ uint32_t c_mark[WB];
     const CoopLds coop{c_key + (threadIdx.x & ~63u), c_mark + (threadIdx.x & ~63u)};
-    if (dyn) {
-        dyn_prefix(w, round, pref);
-        const uint32_t total = pref[w.seg_count];
-        if (blockIdx.x * (WB / 64u) >= total) return;  // (workgroup-uniform) more waves than batches
-        const LdsTables T = LDS_TABLES ? stage_tables(sc, wstack) : LdsTables{sc.subs, sc.insts};
-        const SubRoot *subs = T.subs;
-        const Inst *insts = T.insts;
-        // the batch list in kDynHeads contiguous chunks, chunk x dequeued through head x by the
-        // waves of XCD x (workgroups are dealt to the XCDs round-robin: block b on XCD b % 8);
-        // a wave whose chunk is drained moves on to the next one
-        uint32_t *heads = w.dyn + round * kDynRoundWords;
-        const uint32_t lane = __lane_id();
-        float4 *res_all = res_buf(w, round);
-        if constexpr (PTX_TRACE_STREAM && LDS_TABLES && FLAT && !COUNT) {  // lane refill (trace_stream)
-            trace_stream<PROF, OCC, true>(sc, subs, insts, eps, stack, coop, w, round, pref, heads, res_all);
-            return;
-        }
-        uint32_t x = blockIdx.x % kDynHeads, visited = 0u;
-        uint32_t c0 = (uint32_t)((uint64_t)total * x / kDynHeads), c1 = (uint32_t)((uint64_t)total * (x + 1u) / kDynHeads);
-        // each dequeue takes G consecutive batches (WaveBufs::trace_split in this mode): one
-        // atomic per G * 64 queries, traced back to back by the same wave
-        const uint32_t G = w.trace_split;
-        uint32_t bnext = 0u;
-        if (lane == 0u) bnext = atomicAdd(heads + x * kDynStride, 1u);
-        // one trace_batch per dequeued batch, every Visibility restart in place
-        uint32_t bi = c0 + G * (uint32_t)__builtin_amdgcn_readfirstlane((int)bnext);
-        for (;;) {  // wave-uniform
-            if (bi >= c1) {  // this chunk is drained: the next head
-                if (++visited == kDynHeads) break;
-                x = (x + 1u) % kDynHeads;
-                c0 = (uint32_t)((uint64_t)total * x / kDynHeads);
-                c1 = (uint32_t)((uint64_t)total * (x + 1u) / kDynHeads);
-                if (lane == 0u) bnext = atomicAdd(heads + x * kDynStride, 1u);
-                bi = c0 + G * (uint32_t)__builtin_amdgcn_readfirstlane((int)bnext);
-                continue;
-            }
-            if (lane == 0u) bnext = atomicAdd(heads + x * kDynStride, 1u);  // the next dequeue, fetched ahead
-            const uint32_t bend = min(bi + G, c1);
-            uint32_t lo = 0u;
-            for (; bi < bend; ++bi) {
-                uint32_t hi = w.seg_count;  // last slot with pref <= bi (batches ascend: search from lo)
-                while (hi - lo > 1u) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (pref[mid] <= bi) lo = mid;
-                    else hi = mid;
-                }
-                const uint32_t j = w.seg_phys + w.seg_base + lo;
-                const uint32_t n = w.cnt[(2u * round + 1u) * w.cnt_stride + j];
-                const uint32_t i = (bi - pref[lo]) * 64u + lane;
-#ifdef PTX_WG_TIMES
-                const unsigned long long tb0 = __builtin_amdgcn_s_memrealtime();
-                uint32_t dbg[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-#else
-                uint32_t *dbg = nullptr;
-#endif
-                trace_batch<COUNT, PROF, OCC, LDS_TABLES, FLAT>(sc, subs, insts, eps, stack, coop,
-                                                                 res_all + 2u * (size_t)j * w.ray_stride,
-                                                                 w.rays + 2u * (size_t)j * w.ray_stride, 0u, i, i < n, dbg);
-#ifdef PTX_WG_TIMES
-                batch_record(sc.wgt, tb0, bi, round, dbg);
-#endif
-            }
-            bi = c0 + G * (uint32_t)__builtin_amdgcn_readfirstlane((int)bnext);
-        }
-        return;
-    }
-    // Static: workgroup -> (segment, share): the trace_split workgroups of a segment take its
-    // 256-ray batches round-robin; results go to the rays' own slots, so the split is exact.
-    // A segment's shares are consecutive blocks, so they spread over XCDs (blocks b and b+8
-    // share one: MI355X_MICROARCH.md, workgroup dispatch) -- measured faster than keeping
-    // them on one XCD.  For K | 8 the share index rotates with b / 8, else share 0 (the
-    // heaviest) would always land on the same XCDs.
-    const uint32_t K = w.trace_split, b = blockIdx.x;
-    const uint32_t share = (b % K + ((8u % K) == 0u ? (b >> 3) : 0u)) % K, local = b / K;
-    const uint32_t j = w.seg_phys + w.seg_base + local;  // physical queue slot
+    // workgroup b traces segment seg_base + b; results go to the rays' own slots
+    const uint32_t j = w.seg_phys + w.seg_base + blockIdx.x;  // physical queue slot
     const uint32_t n = w.cnt[(2u * round + 1u) * w.cnt_stride + j];
-    if (share * WB >= n) return;  // (workgroup-uniform) nothing for this share
+    if (n == 0u) return;  // (workgroup-uniform) nothing in this segment
     __shared__ uint32_t l_next;   // (trace_stream's batch counter)
     if (threadIdx.x == 0u) l_next = 0u;  // (ordered by stage_tables' barrier)
     const LdsTables T = LDS_TABLES ? stage_tables(sc, wstack) : LdsTables{sc.subs, sc.insts};
     const SubRoot *subs = T.subs;
     const Inst *insts = T.insts;
     if constexpr (PTX_TRACE_STREAM && LDS_TABLES && FLAT && !COUNT) {  // lane refill over the segment
-        if (!kAbBuild || K == 1u) {
-            trace_stream<PROF, OCC, false>(sc, subs, insts, eps, stack, coop, w, round, nullptr, nullptr,
-                                           res_buf(w, round), &l_next, j, n);
-            return;
-        }
+        trace_stream<PROF, OCC>(sc, subs, insts, eps, stack, coop, w, res_buf(w, round), &l_next, j, n);
+        return;
     }
     if (COUNT && sc.census)  // row census: this slot's queries count into its own block
         sc.counters = sc.census + (size_t)kCensusWords * ((sc.row_end - sc.row_begin + 7u) / 8u + j);
-    for (uint32_t i0 = share * WB; i0 < n; i0 += K * WB) {  // workgroup-uniform
+    for (uint32_t i0 = 0u; i0 < n; i0 += WB) {  // workgroup-uniform
         const uint32_t i = i0 + threadIdx.x;
         trace_batch<COUNT, PROF, OCC, LDS_TABLES, FLAT>(sc, subs, insts, eps, stack, coop, res_buf(w, round), w.rays,
                                                          j * w.ray_stride, i, i < n);
     }
 }
 
-// Lane-refill form of the same queries.  The whole traversal -- instance loop, sub-root
-// loop, BLAS stack walk, leaf triangle loop and the Visibility continuation -- is one
+// ptx_trace's closest-hit queries, lane-refill form.  The whole traversal -- instance loop,
+// sub-root loop, BLAS stack walk and leaf triangle loop -- is one
 // flat per-lane state machine: every iteration a lane does ONE unit of work (a node-pair
 // test, a triangle test, or a root/instance step), and a lane whose ray is done takes
 // the segment's next ray at once instead of idling until the wave's slowest ray ends.
 // Per ray the visit order (and so the hit, ties included, and the work counters) is the
 // reference's exactly: only the interleaving across lanes changes.
-// Workgroup j handles segment j: `cnt` given -> cnt[j] rays at j * stride (queue layout
-// {o, remain}, {d, kind}); `cnt` null -> rays [j * stride, min((j+1) * stride, n_total))
-// in the public ptx_trace layout {o.xyz, d.x}, {d.yz, -, -} (closest hit only).
+// Workgroup j handles rays [j * stride, min((j+1) * stride, n_total)) in the public ptx_trace
+// layout {o.xyz, d.x}, {d.yz, -, -}.  (On the wavefront queues it measured -28 % against
+// trace_queue: DESIGN §4.1b.)
 template <bool COUNT>
 __global__ __launch_bounds__(WB) void trace_queue_sm(Scene sc, const float4 *rays_all, float4 *res_all,
-                                                     const uint32_t *cnt, uint32_t stride, uint32_t n_total,
-                                                     PassEps eps) {
+                                                     uint32_t stride, uint32_t n_total, PassEps eps) {
     extern __shared__ __attribute__((aligned(16))) uint32_t wstack[];
     uint32_t *stack = wstack + threadIdx.x;
     const uint32_t j = blockIdx.x;
-    const bool pub = cnt == nullptr;
-    const uint32_t n = pub ? min(stride, n_total - j * stride) : cnt[j];
+    const uint32_t n = min(stride, n_total - j * stride);
     const float4 *rays = rays_all + 2u * (size_t)j * stride;
     float4 *res = res_all + 2u * (size_t)j * stride;
     const float vx = 1e-4f;
@@ -309,10 +188,6 @@ __global__ __launch_bounds__(WB) void trace_queue_sm(Scene sc, const float4 *ray
     uint32_t next = threadIdx.x, cur = 0u;
     bool have = false;
     Ray r{};                       // world ray of the current trace
-    bool vis = false;              // Visibility / occlusion query (else closest hit)
-    bool occ = false;              // occlusion query: every hit inside `remain` blocks
-    float T = 1.0f, remain = 0.0f; // Visibility product / remaining distance
-    uint32_t vit = 0u;             // Visibility segment (0..4)
     uint32_t ii = 0u, s = 0u, nsub = 0u, grp = 0u, sub_base = 0u, tri_base = 0u;
     f3 lo{}, ld{}, inv{};          // ray in the current instance's space
     int sp = -1;
@@ -327,15 +202,10 @@ __global__ __launch_bounds__(WB) void trace_queue_sm(Scene sc, const float4 *ray
             cur = next;
             next += WB;
             const float4 a = rays[2u * cur], b = rays[2u * cur + 1u];
-            r = pub ? Ray{mk(a.x, a.y, a.z), mk(a.w, b.x, b.y)} : Ray{mk(a.x, a.y, a.z), mk(b.x, b.y, b.z)};
-            vis = !pub && asu(b.w) != Q_CLOSEST;
-            occ = !pub && asu(b.w) == Q_OCC;
-            T = 1.0f;
-            remain = a.w;
-            vit = 0u;
+            r = Ray{mk(a.x, a.y, a.z), mk(a.w, b.x, b.y)};
             have = true;
             ii = 0xffffffffu; s = 0u; nsub = 0u; sp = -1; tcount = 0u;
-            vy = vis ? vis_bound(remain) : 1e10f;
+            vy = 1e10f;
             bvalid = false; n_aabb = 0u; n_tri = 0u;
         }
         if (__ballot(have) == 0ull) break;
@@ -388,37 +258,11 @@ __global__ __launch_bounds__(WB) void trace_queue_sm(Scene sc, const float4 *ray
                 h.t = bvalid ? vy : 0.0f;
                 h.s = Compact{0u, bvalid ? binst : 0u, bvalid ? bmat : 0u, bvalid ? bprim : 0u, 0.0f, 0.0f};
                 h.pos = mk(0.0f, 0.0f, 0.0f);
-                if (!vis) {
-                    if (bvalid) complete_hit(sc, r, eps, h);
-                    const uint32_t enc = ((h.valid ? 1u : 0u) << 31) | (h.s.inst << 16) | h.s.mat;
-                    res[2u * cur] = make_float4(h.t, asf(enc), asf(h.s.prim), h.s.bu);
-                    res[2u * cur + 1u] = make_float4(h.s.bv, h.pos.x, h.pos.y, h.pos.z);
-                    have = false;
-                } else {  // Visibility step (SH/PT_1_InitPass.wgsl:774-802)
-                    float out = -1.0f;
-                    if (!h.valid || h.t > remain) out = T;
-                    else {
-                        const float tr = occ ? 0.0f : get_transmission(sc, h.s.inst, h.s.mat);
-                        if (tr == 0.0f) out = 0.0f;
-                        else {
-                            T *= tr;
-                            remain -= h.t;
-                            if (vit == 4u) out = 0.0f;  // gives up after 5 segments
-                            else {
-                                complete_hit(sc, r, eps, h);
-                                r.o = h.pos;
-                                ++vit;
-                                ii = 0xffffffffu; s = 0u; nsub = 0u; sp = -1; tcount = 0u;
-                                vy = vis_bound(remain);
-                                bvalid = false; n_aabb = 0u; n_tri = 0u;
-                            }
-                        }
-                    }
-                    if (out >= 0.0f) {  // only res.x: .yzw and res[2i+1] carry the payload
-                        res[2u * cur].x = out;
-                        have = false;
-                    }
-                }
+                if (bvalid) complete_hit(sc, r, eps, h);
+                const uint32_t enc = ((h.valid ? 1u : 0u) << 31) | (h.s.inst << 16) | h.s.mat;
+                res[2u * cur] = make_float4(h.t, asf(enc), asf(h.s.prim), h.s.bu);
+                res[2u * cur + 1u] = make_float4(h.s.bv, h.pos.x, h.pos.y, h.pos.z);
+                have = false;
                 continue;
             }
         }
@@ -1269,32 +1113,14 @@ __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(LOGIC_WAVES,
 }
 
 // =========================================================================== host side
-// trace_queue's grid: trace_split workgroups per segment
-static inline bool trace_dyn(const WaveBufs &w) { return kAbBuild && w.dyn != nullptr && w.seg_count <= kDynMaxSlots; }
-static inline uint32_t trace_grid(const WaveBufs &w) {
-    // (PTX_AB=DYN_GROUPS=n: A/B -- the cap dates from the 4-wave trace; at 5 waves per SIMD the chip
-    // holds 1280 trace workgroups)
-    static const uint32_t groups = (uint32_t)ab_knob("DYN_GROUPS", (int)kDynMaxGroups);
-    return trace_dyn(w) ? std::min(w.seg_count, groups) : w.seg_count * w.trace_split;
-}
+// trace_queue's grid: one workgroup per segment of the launch
+static inline uint32_t trace_grid(const WaveBufs &w) { return w.seg_count; }
 
-hipError_t wave_trace(const Scene &sc, const WaveBufs &w_in, int round, int eps_mode, uint32_t depth, hipStream_t s,
+hipError_t wave_trace(const Scene &sc, const WaveBufs &w, int round, int eps_mode, uint32_t depth, hipStream_t s,
                       bool occ_only) {
     const PassEps eps = eps_mode == 0 ? PassEps{1e-8f, 1e-6f} : PassEps{1e-4f, 1e-8f};
-    WaveBufs w = w_in;
-    // counting builds keep the per-slot census (the SIMD-utilisation build profiles the production
-    // walk, streamed lanes included, when it applies)
-    static const bool prof = ab_knob("TRACE_PROF", 0) != 0;
-    const bool prof_stream = PTX_TRACE_STREAM && prof && !occ_only && tables_fit_lds(sc) && PTX_FLAT_INST &&
-                             sc.n_inst >= (uint32_t)ab_knob("FLAT_MIN_INST", (int)kFlatMinInstances);
-    if ((sc.counters && !prof_stream) || !trace_dyn(w)) w.dyn = nullptr;
-    if (w.dyn) {  // batches per dequeue (A/B: PTX_AB=TRACE_DYN_G=g)
-        static const uint32_t g = (uint32_t)ab_knob("TRACE_DYN_G", 0);
-        w.trace_split = g >= 1u && g <= 16u ? g : 1u;
-    }
-    // dynamic LDS: scene tables (the LDS-table variants) + batch prefix (dynamic batches) + stacks
-    const size_t lds = (tables_fit_lds(sc) ? tables_lds_bytes(sc) : 0u) +
-                       (w.dyn ? 4u * (size_t)((w.seg_count + 4u) & ~3u) : 0u) + stack_lds_bytes(depth);
+    // dynamic LDS: scene tables (the LDS-table variants) + stacks
+    const size_t lds = (tables_fit_lds(sc) ? tables_lds_bytes(sc) : 0u) + stack_lds_bytes(depth);
     static const uint32_t flat_min = (uint32_t)ab_knob("FLAT_MIN_INST", (int)kFlatMinInstances);  // A/B
     const bool flat = PTX_FLAT_INST && sc.n_inst >= flat_min;
     if (occ_only && tables_fit_lds(sc)) {  // occlusion rounds (GI spatial)
@@ -1309,21 +1135,7 @@ hipError_t wave_trace(const Scene &sc, const WaveBufs &w_in, int round, int eps_
                                (uint32_t)round, eps);
         return hipGetLastError();
     }
-    // (PTX_AB=TRACE_REFILL: the lane-refill kernel of ptx_trace on the queues -- A/B builds)
-    static const bool refill = ab_knob("TRACE_REFILL", 0) != 0;
-    if (refill) {
-        const uint32_t pb = w.seg_phys + w.seg_base;
-        const uint32_t *cnt = w.cnt + (2u * round + 1u) * w.cnt_stride + pb;
-        float4 *res = w.res[w.nres == 3u ? round % 3 : round & 1] + 2u * (size_t)pb * w.ray_stride;
-        if (sc.counters)
-            hipLaunchKernelGGL(trace_queue_sm<true>, dim3(w.seg_count), dim3(WB), lds, s, sc,
-                               w.rays + 2u * (size_t)pb * w.ray_stride, res, cnt,
-                               w.ray_stride, 0u, eps);
-        else
-            hipLaunchKernelGGL(trace_queue_sm<false>, dim3(w.seg_count), dim3(WB), lds, s, sc,
-                               w.rays + 2u * (size_t)pb * w.ray_stride, res, cnt,
-                               w.ray_stride, 0u, eps);
-    } else if (sc.counters && ab_knob("TRACE_PROF", 0)) {  // SIMD-utilisation diagnostics
+    if (sc.counters && ab_knob("TRACE_PROF", 0)) {  // SIMD-utilisation diagnostics
         if (flat && tables_fit_lds(sc))  // (the production walk: flattened instances, LDS tables, and
             // COUNT off so that the instance cull applies as in production -- the PROF regions
             // still count into sc.counters; the work counters stay zero)
@@ -1362,7 +1174,7 @@ hipError_t wave_trace(const Scene &sc, const WaveBufs &w_in, int round, int eps_
     return hipGetLastError();
 }
 
-// ptx_trace / ptx_trace_device queries (public ray layout) through the same kernel.
+// ptx_trace / ptx_trace_device queries (public ray layout): trace_queue_sm, one workgroup per 1024 rays.
 hipError_t launch_trace_rays_sm(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,
                                 uint32_t depth, hipStream_t s) {
     if (n == 0) return hipSuccess;
@@ -1370,11 +1182,11 @@ hipError_t launch_trace_rays_sm(const Scene &sc, const float4 *rays, float4 *hit
     const uint32_t per_wg = 4u * WB;
     const dim3 grid((n + per_wg - 1u) / per_wg);
     if (sc.counters)
-        hipLaunchKernelGGL(trace_queue_sm<true>, grid, dim3(WB), stack_lds_bytes(depth), s, sc, rays, hits, nullptr,
-                           per_wg, n, eps);
+        hipLaunchKernelGGL(trace_queue_sm<true>, grid, dim3(WB), stack_lds_bytes(depth), s, sc, rays, hits, per_wg, n,
+                           eps);
     else
-        hipLaunchKernelGGL(trace_queue_sm<false>, grid, dim3(WB), stack_lds_bytes(depth), s, sc, rays, hits, nullptr,
-                           per_wg, n, eps);
+        hipLaunchKernelGGL(trace_queue_sm<false>, grid, dim3(WB), stack_lds_bytes(depth), s, sc, rays, hits, per_wg, n,
+                           eps);
     return hipGetLastError();
 }
 

@@ -1,8 +1,8 @@
 #!/usr/bin/env bash
 # Per-kernel A/B: rocprofv3 --kernel-trace --stats of a short single-sequence bench per library
 # (PTX_AB=PIPELINE_FRAMES=0: kernels do not share the chip with a second frame), then the
-# average duration of every kernel side by side (static trace slots, the production mode since late
-# round 5; EXTRA_AB=TRACE_DYN=1 for the dynamic batches).  usage: LIBS="libptx_a.so libptx.so" bash tools/ab_kernels.sh
+# average duration of every kernel side by side (EXTRA_AB adds switches, e.g. EXTRA_AB=TRACE_OCC=4
+# for the trace kernel at 4 waves per SIMD).  usage: LIBS="libptx_a.so libptx.so" bash tools/ab_kernels.sh
 set -u
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 P=$R/pathtracerdemo_amd

@@ -9,8 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 # region (PTX_FLAG_SINGLE_STREAM); the two-stream production overlap is measured by the
 # bench's headline value, not by per-kernel averages
 # and one frame in flight (frame pipelining overlaps consecutive frames' kernels); EXTRA_AB
-# adds switches (e.g. TRACE_DYN=1: the dynamic trace batches, the reuse pipeline's default
-# before late round 5)
+# adds switches (e.g. TRACE_OCC=4: the trace kernel at 4 waves per SIMD)
 export PTX_AB="WAVE_STREAMS=1,PIPELINE_FRAMES=0${EXTRA_AB:+,$EXTRA_AB}"
 # (the shipped libptx.so compiles these switches to their defaults since round 5: the profile
 # runs the measurement build of the same sources, make -C pathtracerdemo_amd/csrc ab)

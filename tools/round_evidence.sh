@@ -7,8 +7,8 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$R"
 ROUND=${ROUND:-r1}
 for WL in ${WORKLOADS:-reuse restir mcpt}; do
-  # (every whole-image pipeline runs static trace slots since late round 5, as the profile's
-  # one-frame-in-flight region does: no TRACE_DYN override)
+  # (the profile's one-frame-in-flight region traces as the production frames do: one workgroup
+  # per segment, the trace launch's only mode)
   TAG=${ROUND}_$WL BENCH_ARGS="--workload $WL" bash tools/profile.sh || { echo "profile $WL failed"; exit 1; }
   # the bench line's log: under $OUT (default build/evidence, which git ignores)
   LOG="${OUT:-build/evidence}/bench_${ROUND}_$WL.log"
