@@ -541,13 +541,6 @@ static uint32_t seg_pixels(const ptx_handle *h) {
 // shift jobs per pixel the DI reuse passes may hold at once: the spatial pass's 2M, the motion
 // temporal pass's kMotionJobs
 static size_t reuse_jobs_per_px(const ptx_handle *h) { return std::max<size_t>(2u * h->reuse_neighbors, kMotionJobs); }
-// trace_queue's occupancy target for the handle's band (WaveBufs::trace_waves).  Measured (DESIGN.md
-// §4.1b, with the flat node loop): 4 waves per SIMD (no spill) for every pipeline at 1080p (GI 720 vs
-// 714 Msamples/s at 5), 5 for bands of more than 4 Mpx (a 3840x2160 frame on one GPU: 414.6 vs 413.9
-// Msamples/s, trace roofline 0.611 vs 0.597)
-static uint32_t trace_waves_of(const ptx_handle *h) {
-    return (size_t)h->band_h * h->cfg.width > ((size_t)4u << 20) ? 5u : 4u;
-}
 // Wavefront buffers, sized for the largest round: PT_1 emits <= 2 rays per pixel, PT_4
 // <= 1, TEST_MCPT <= LightCount + 1 (all shadow rays of a vertex + the next path ray).
 int wave_buffers(ptx_handle *h, WaveBufs &w) {
@@ -622,7 +615,6 @@ int wave_buffers(ptx_handle *h, WaveBufs &w) {
     // streams (e.g. one half's spatial pass beside the other half's PT_4)
     w.act_stride = (uint32_t)(seg_px * jpp);
     w.cnt = (uint32_t *)c.wctr.p;
-    w.trace_waves = trace_waves_of(h);
     w.seg_base = 0;
     w.seg_count = w.nseg;
     static const uint32_t cl = (uint32_t)ab_knob("SEG_CLUSTER", 1);  // A/B
@@ -2583,7 +2575,6 @@ int ptx_trace_queries(ptx_handle *h, const float *queries, float *results, size_
     w.res[0] = w.res[1] = (float4 *)h->d_qhits.p;  // (round 0 writes res[0])
     w.nres = 2;
     w.cnt = (uint32_t *)h->d_qcnt.p;
-    w.trace_waves = trace_waves_of(h);
     TimedLaunch &t = h->ring[h->ring_pos];
     h->ring_pos = (h->ring_pos + 1) % kEventRing;
     resolve_event(t, h);

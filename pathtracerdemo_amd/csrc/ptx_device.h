@@ -234,6 +234,14 @@ struct Prof {
     }
 };
 
+// a walk's SIMD-utilisation profile into the counters
+__device__ __forceinline__ void prof_flush(const Scene &sc, const Prof &pf) {
+    for (int r = 0; r < PROF_REGIONS; ++r) {
+        if (pf.wave[r]) atomicAdd(&sc.counters[8 + 2 * r], (unsigned long long)pf.wave[r]);
+        if (pf.lane[r]) atomicAdd(&sc.counters[9 + 2 * r], (unsigned long long)pf.lane[r]);
+    }
+}
+
 // A lane mask of a boolean: the ballot builtin on the i1 itself.  (HIP's __ballot takes an
 // int, so a bool predicate went through a VGPR -- v_cndmask + v_cmp -- before the mask; in the
 // traversal's per-iteration loop tests that is two VALU instructions each.)
@@ -442,23 +450,11 @@ __device__ __forceinline__ float vis_bound(float remain) {
 #ifndef PTX_INST_CULL
 #define PTX_INST_CULL 1
 #endif
-#ifndef PTX_EARLY_LEAF_K  // trace_core_flat's early leaf phase (0 = off)
+#ifndef PTX_EARLY_LEAF_K  // the walks' early leaf phase (0 = off)
 #define PTX_EARLY_LEAF_K 16
 #endif
 #ifndef PTX_EARLY_LEAF_L
 #define PTX_EARLY_LEAF_L 4
-#endif
-#ifndef PTX_EARLY_LEAF_TAB  // the same in trace_core_tab (scenes of < 3 instances, G-buffer, PT_4)
-#define PTX_EARLY_LEAF_TAB 1
-#endif
-#ifndef PTX_EARLY_LEAF_TAB_K
-#define PTX_EARLY_LEAF_TAB_K PTX_EARLY_LEAF_K
-#endif
-#ifndef PTX_EARLY_LEAF_TAB_L
-#define PTX_EARLY_LEAF_TAB_L PTX_EARLY_LEAF_L
-#endif
-#ifndef PTX_EARLY_REFILL_K  // trace_core_flat's early exit from the refill loop (0 = off; K = 4 / 8 / 16 measured -0.5 to -1 %)
-#define PTX_EARLY_REFILL_K 0
 #endif
 
 // TraceRay (SH/PT_1_InitPass.wgsl:605-715; PT_01:509-621): closest hit over every
@@ -534,9 +530,49 @@ __device__ __forceinline__ int deal_owner(CoopLds coop, uint32_t lane, uint32_t 
     if (lane == 0u && before != 0ull) m = max(m, 64u - (uint32_t)__builtin_clzll(before));
     return (int)wave_incl_max(m) - 1;
 }
-// UNI: `subs` is the workgroup's LDS copy of the root table (like `stack`): pops and root takes
-// share one code path (fewer exec-mask branches per node-loop iteration; same per-lane sequence).
-template <bool COUNT, bool PROF = false, bool ROOTQ = true, bool ANY = false, bool COOP = false, bool UNI = false>
+// The cooperative leaf deal (COOP above), called by every lane of a whole wave: the triangles of
+// the leaves the lanes hold (`leaf`, 0 = none; triangle base `tri_base`, local ray lo / ld, bound
+// vy) are tested 64 at a time, each by one lane with the owning lane's ray, bound and base.
+// Returns whether some lane computed a NaN t (wave-uniform); if none did, `key` is the lane's
+// minimum over (t bits, ~primitive) of the accepted triangles of its leaf, ~0 when there is none.
+template <bool PROF>
+__device__ __forceinline__ bool coop_leaf_deal(const Scene &sc, CoopLds coop, PassEps eps, uint32_t leaf,
+                                               uint32_t tri_base, f3 lo, f3 ld, float vy, Prof &pf,
+                                               unsigned long long &key) {
+    const uint32_t lane = __lane_id();
+    const uint32_t cnt = leaf ? (leaf >> 24) & 0x7Fu : 0u, lfirst = leaf & LEAF_FIRST_MASK;
+    uint32_t total;
+    const uint32_t excl = wave_excl_sum(cnt, total);
+    __hip_atomic_store(&coop.key[lane], ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);  // (compiler order; one wave's LDS ops run in order)
+    bool nan_seen = false;
+    for (uint32_t c0 = 0; c0 < total; c0 += 64u) {
+        const uint32_t u = c0 + lane;
+        const int owner = deal_owner(coop, lane, cnt, excl, c0);
+        // triangle u of the deal: the owner's leaf triangle lfirst + (u - excl), in its instance
+        const uint32_t tri = u + __shfl(lfirst - excl, owner);
+        const uint32_t tb = __shfl(tri_base, owner);
+        const f3 olo = mk(__shfl(lo.x, owner), __shfl(lo.y, owner), __shfl(lo.z, owner));
+        const f3 old = mk(__shfl(ld.x, owner), __shfl(ld.y, owner), __shfl(ld.z, owner));
+        const float ovy = __shfl(vy, owner);
+        if (u < total) {
+            if (PROF) pf.hit(PROF_TRI);
+            const float4 *tp = sc.tris + 3u * (tb + tri);
+            const float t = ray_tri(olo, old, tp[0], tp[1], tp[2], eps.det_eps);
+            if (t != t) nan_seen = true;
+            else if (!(ovy < t))
+                atomicMin(&coop.key[owner],
+                          ((unsigned long long)__float_as_uint(t) << 32) | (unsigned long long)(0xffffffffu - tri));
+        }
+    }
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    key = __hip_atomic_load(&coop.key[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    return wballot(nan_seen) != 0ull;
+}
+// The walk one instance at a time for the whole wave: the one-thread-per-pixel kernels, the
+// G-buffer (ROOTQ = false), and trace_queue where the flat walk below does not apply -- tables too
+// large for LDS, or a counting instance (COUNT: every instance is walked, the cull only checked).
+template <bool COUNT, bool PROF = false, bool ROOTQ = true, bool ANY = false, bool COOP = false>
 __device__ __forceinline__ Hit trace_core_tab(const Scene &sc, const SubRoot *subs, const Inst *insts, Ray ray,
                                               PassEps eps, uint32_t *stack, uint32_t stride, float t_max = 1e10f,
                                               CoopLds coop = CoopLds{nullptr}, bool want_pos = true,
@@ -611,36 +647,16 @@ __device__ __forceinline__ Hit trace_core_tab(const Scene &sc, const SubRoot *su
                     const bool want = leaf == 0u && (sp >= 0 || mask != 0u);
                     const unsigned long long wm = wballot(want);
                     if (wm == 0ull) break;
-                    // early leaf phase (as trace_core_flat; only where the cooperative phase runs)
-                    if constexpr (PTX_EARLY_LEAF_K > 0 && PTX_EARLY_LEAF_TAB && COOP) {
-                        if (wave_coop && __builtin_popcountll(wm) <= PTX_EARLY_LEAF_TAB_K &&
-                            __builtin_popcountll(wballot(leaf != 0u)) >= PTX_EARLY_LEAF_TAB_L)
+                    // early leaf phase (FlatWalk::nodes'; only where the cooperative phase runs)
+                    if constexpr (PTX_EARLY_LEAF_K > 0 && COOP) {
+                        if (wave_coop && __builtin_popcountll(wm) <= PTX_EARLY_LEAF_K &&
+                            __builtin_popcountll(wballot(leaf != 0u)) >= PTX_EARLY_LEAF_L)
                             break;
                     }
                     if (PROF && want) pf.hit(PROF_NODE);
                     uint32_t ref = 0u;
                     bool node = false;
-                    if (UNI) {
-                        // One path for a pop and a root take (`subs` and the stack both in LDS):
-                        // the next reference is read from the stack top, or -- with an empty stack
-                        // -- from the next queued root's record, through one selected LDS address.
-                        // A root is re-tested only when a hit has moved the bound since the
-                        // pre-filter (else the pre-filter's result is the reference's test).
-                        // (predicated: lanes without work read a valid slot and keep their state)
-                        const bool from_root = sp < 0;
-                        const uint32_t k = (from_root && mask != 0u) ? (uint32_t)__builtin_ctz(mask) : 0u;
-                        const uint32_t *src = from_root ? &roots[s0 + k].ref : &stack[(uint32_t)(from_root ? 0 : sp) * stride];
-                        ref = *src;
-                        const bool tk_root = want && from_root;
-                        bool take = want;
-                        if (tk_root && !(ROOTQ && vy == vy_pf)) take = box_root(lo, inv, roots[s0 + k], vx, vy);
-                        mask = tk_root ? (mask & (mask - 1u)) : mask;
-                        sp = (want && !from_root) ? sp - 1 : sp;
-                        grp = (tk_root && take) ? s0 + k : grp;
-                        const bool is_leaf = (ref & LEAF_BIT) != 0u;
-                        leaf = (take && is_leaf) ? ref : leaf;
-                        node = take && !is_leaf;
-                    } else if (leaf == 0u && sp < 0 && mask != 0u) {
+                    if (leaf == 0u && sp < 0 && mask != 0u) {
                         const uint32_t k = (uint32_t)__builtin_ctz(mask);
                         mask &= mask - 1u;
                         const SubRoot &R = roots[s0 + k];
@@ -676,52 +692,10 @@ __device__ __forceinline__ Hit trace_core_tab(const Scene &sc, const SubRoot *su
                 if (wave_coop && __ballot(1) == ~0ull) {  // a wave-uniform leaf phase
                     if (wballot(leaf != 0u) == 0ull) break;
                     if (PROF) pf.hit(PROF_LEAF);
-                    const uint32_t lane = __lane_id();
-                    const uint32_t cnt = leaf ? (leaf >> 24) & 0x7Fu : 0u, lfirst = leaf & LEAF_FIRST_MASK;
-                    uint32_t total;
-                    const uint32_t excl = wave_excl_sum(cnt, total);
-                    __hip_atomic_store(&coop.key[lane], ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    __atomic_signal_fence(__ATOMIC_SEQ_CST);  // (compiler order; one wave's LDS ops run in order)
-                    bool nan_seen = false;
-                    for (uint32_t c0 = 0; c0 < total; c0 += 64u) {
-                        const uint32_t u = c0 + lane;
-                        // owner of triangle u = the last lane with a nonempty leaf whose
-                        // exclusive count is <= u: each such lane whose leaf starts inside this
-                        // chunk marks its start position (lane + 1; starts are distinct and
-                        // ascend with the lane), position 0 also takes the last owner that
-                        // started before the chunk, and a prefix maximum over the positions
-                        // carries every mark forward
-                        __hip_atomic_store(&coop.mark[lane], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-                        if (cnt != 0u && excl >= c0 && excl - c0 < 64u)
-                            __hip_atomic_store(&coop.mark[excl - c0], lane + 1u, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-                        uint32_t m = __hip_atomic_load(&coop.mark[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        const unsigned long long before = wballot(cnt != 0u && excl < c0);
-                        if (lane == 0u && before != 0ull) m = max(m, 64u - (uint32_t)__builtin_clzll(before));
-                        const int owner = (int)wave_incl_max(m) - 1;
-                        // triangle u of the deal is the owner's leaf triangle lfirst + (u - excl)
-                        const uint32_t tri = u + __shfl(lfirst - excl, owner);
-                        const f3 olo = mk(__shfl(lo.x, owner), __shfl(lo.y, owner), __shfl(lo.z, owner));
-                        const f3 old = mk(__shfl(ld.x, owner), __shfl(ld.y, owner), __shfl(ld.z, owner));
-                        const float ovy = __shfl(vy, owner);
-                        if (u < total) {
-                            if (PROF) pf.hit(PROF_TRI);
-                            const float4 *tp = tris + 3u * tri;
-                            const float t = ray_tri(olo, old, tp[0], tp[1], tp[2], eps.det_eps);
-                            if (t != t) nan_seen = true;
-                            else if (!(ovy < t))
-                                atomicMin(&coop.key[owner], ((unsigned long long)__float_as_uint(t) << 32) |
-                                                                (unsigned long long)(0xffffffffu - tri));
-                        }
-                    }
-                    __atomic_signal_fence(__ATOMIC_SEQ_CST);
-                    if (wballot(nan_seen) == 0ull) {
+                    unsigned long long key;
+                    if (!coop_leaf_deal<PROF>(sc, coop, eps, leaf, I.tri_base, lo, ld, vy, pf, key)) {
                         if (leaf) {
-                            const unsigned long long key =
-                                __hip_atomic_load(&coop.key[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                            n_tri += cnt;
+                            n_tri += (leaf >> 24) & 0x7Fu;
                             if (key != ~0ull) {
                                 vy = __uint_as_float((uint32_t)(key >> 32));
                                 best.valid = true;
@@ -770,12 +744,7 @@ __device__ __forceinline__ Hit trace_core_tab(const Scene &sc, const SubRoot *su
         }
     }
     const bool counted = t_max == t_max;  // a NaN bound: an idle lane keeping its wave whole
-    if (PROF && counted) {
-        for (int r = 0; r < PROF_REGIONS; ++r) {
-            if (pf.wave[r]) atomicAdd(&sc.counters[8 + 2 * r], (unsigned long long)pf.wave[r]);
-            if (pf.lane[r]) atomicAdd(&sc.counters[9 + 2 * r], (unsigned long long)pf.lane[r]);
-        }
-    }
+    if (PROF && counted) prof_flush(sc, pf);
     if (COUNT && counted) {
         atomicAdd(&sc.counters[CNT_RAYS], 1ull);
         atomicAdd(&sc.counters[CNT_INST], (unsigned long long)sc.n_inst);
@@ -789,99 +758,114 @@ __device__ __forceinline__ Hit trace_core_tab(const Scene &sc, const SubRoot *su
     }
     return best;
 }
-// The same walk with the instance loop flattened into the lanes (trace_queue's form: whole-wave
-// calls, root and instance tables in LDS).  Each lane keeps its own place in the instance list:
-// a lane whose roots and stack of one instance are exhausted moves on to the next instance its
-// ray may reach (inst_may_hit) at the next refill -- after the current leaf phase -- instead of
-// idling until every lane of the wave has finished that instance; lanes in different instances
-// share the node loop and the cooperative leaf phases (the owner's triangle base travels with
-// its ray).  Per lane the order of instances, roots, pops, node tests, pushes and triangle
-// tests is the reference's (SH/PT_1_InitPass.wgsl:605-715), so hits, ties and work counts are
-// unchanged; a leaf phase in which a lane computed a NaN t runs its leaves sequentially.
-template <bool COUNT, bool PROF = false, bool ANY = false>
-__device__ __forceinline__ Hit trace_core_flat(const Scene &sc, const SubRoot *subs, const Inst *insts, Ray ray,
-                                               PassEps eps, uint32_t *stack, uint32_t stride, float t_max,
-                                               CoopLds coop, bool want_pos, float t_stop = 3.0e38f) {
-    Prof pf{};
-    Hit best;
-    best.valid = false;
-    best.t = 0.0f;
-    best.s = Compact{0u, 0u, 0u, 0u, 0.0f, 0.0f};
-    best.pos = mk(0.0f, 0.0f, 0.0f);
-    const float vx = 1e-4f;
-    float vy = t_max;
-    uint32_t n_aabb = 0, n_tri = 0;
-    const bool counted = t_max == t_max;  // a NaN bound: an idle lane keeping its wave whole
-    const bool rfin = finite3(ray.o) && finite3(ray.d);
-    const float omax = fmaxf(fmaxf(fabsf(ray.o.x), fabsf(ray.o.y)), fabsf(ray.o.z));
-    uint32_t next = 0u;                       // the next instance to consider
-    uint32_t cur = 0u, s0 = 0u, nsub = 0u;    // the instance walked, its root chunk, its root count
+// The same walk with the instance loop flattened into the lanes (whole-wave calls, root and
+// instance tables in LDS): what trace_queue and wfinal_* trace with when the tables fit.  Each lane
+// keeps its own place in the instance list: a lane whose roots and stack of one instance are
+// exhausted moves on to the next instance its ray may reach (inst_may_hit) at the next refill --
+// after the current leaf phase -- instead of idling until every lane of the wave has finished that
+// instance; lanes in different instances share the node loop and the cooperative leaf phases (the
+// owner's triangle base travels with its ray).  Per lane the order of instances, roots, pops, node
+// tests, pushes and triangle tests is the reference's (SH/PT_1_InitPass.wgsl:605-715), so hits,
+// ties and work counts are unchanged; a leaf phase in which a lane computed a NaN t runs its leaves
+// sequentially.
+// FlatWalk is one lane's state of that walk, and its three phases the steps a driver loops over:
+// trace_core_flat (a batch: 64 queries begin and end together) and trace_stream (ptx_stream.h: a
+// lane whose query is over takes a new one).  Every lane of the wave calls every step.  A lane
+// without a query is `done` with an empty stack, root mask and leaf -- as begin() with a NaN bound
+// and the end of any walk leave it -- so no step's predicate asks whether the lane has one.
+// Each step works on a copy `w` of the state and stores it back at its end: the compiler optimises
+// a step before it inlines it, and there the state behind `this` is memory, which shapes the loops
+// around loads and stores (measured: 20 B/lane of scratch in trace_queue and 4 more VGPRs, against
+// none with the copies, which are registers from the start).
+struct FlatWalk {
+    static constexpr float vx = 1e-4f;
+    float vy = 0.0f, vy_pf = 0.0f;           // the bound (the best t so far), and the root pre-filter's
+    float omax = 0.0f;                       // instance cull inputs (inst_may_hit): max |o|, and
+    bool rfin = true;                        //   a ray with a non-finite component is never culled
+    bool done = true;                        // every instance walked (or occluded, or no query)
+    bool bvalid = false;                     // the best hit: instance, sub-mesh, primitive
+    uint32_t binst = 0u, bmat = 0u, bprim = 0u;
+    uint32_t next = 0u;                      // the next instance to consider
+    uint32_t cur = 0u, s0 = 0u, nsub = 0u;   // the instance walked, its root chunk, its root count
     uint32_t sub_base = 0u, tri_base = 0u;
-    bool done = !counted;                     // (no box passes a NaN bound: nothing to walk)
-    f3 lo = mk(0.0f, 0.0f, 0.0f), ld = lo, inv = lo;
-    uint32_t mask = 0u, grp = 0u, leaf = 0u;
+    f3 lo{0.0f, 0.0f, 0.0f}, ld{0.0f, 0.0f, 0.0f}, inv{0.0f, 0.0f, 0.0f};  // the ray in that instance
+    uint32_t mask = 0u, grp = 0u, leaf = 0u; // queued roots of the chunk, the sub-mesh walked, the leaf held
     int sp = -1;
-    float vy_pf = vy;
-    for (;;) {
-        // refill: a lane with no leaf, no stack and no queued root takes its instance's next
-        // chunk of 32 roots or its next instance (transform + root pre-filter)
-        for (uint32_t refills = 0u;; ++refills) {
-            const bool need = !done && leaf == 0u && sp < 0 && mask == 0u;
-            const unsigned long long nm = wballot(need);
-            if (nm == 0ull) break;
-            // early exit (PTX_EARLY_REFILL_K > 0): after one refill, when at most K lanes still
-            // look for a root that passes, the lanes that have one walk it now and those K go on
-            // at the next refill.  Per lane nothing moves; only the interleaving across lanes.
-            if constexpr (PTX_EARLY_REFILL_K > 0) {
-                if (refills > 0u && __builtin_popcountll(nm) <= PTX_EARLY_REFILL_K &&
-                    wballot(leaf != 0u || sp >= 0 || mask != 0u) != 0ull)
-                    break;
-            }
+    uint32_t n_aabb = 0u, n_tri = 0u;        // work counts (slab tests incl. every root once, triangle tests)
+
+    // A query along `ray` under the bound t_max (NaN: no query, the lane only keeps its wave whole)
+    __device__ __forceinline__ void begin(const Ray &ray, float t_max) {
+        vy = vy_pf = t_max;
+        rfin = finite3(ray.o) && finite3(ray.d);
+        omax = fmaxf(fmaxf(fabsf(ray.o.x), fabsf(ray.o.y)), fabsf(ray.o.z));
+        bvalid = false;
+        binst = bmat = bprim = 0u;
+        next = cur = s0 = nsub = sub_base = tri_base = 0u;
+        mask = grp = leaf = 0u;
+        sp = -1;
+        done = !(t_max == t_max);  // (no box passes a NaN bound: nothing to walk)
+        n_aabb = n_tri = 0u;
+    }
+    // refill: a lane with no leaf, no stack and no queued root takes its instance's next chunk
+    // of 32 roots or its next instance (transform + root pre-filter)
+    template <bool PROF>
+    __device__ __forceinline__ void refill(const Scene &sc, const SubRoot *subs, const Inst *insts, const Ray &ray,
+                                           Prof &pf) {
+        FlatWalk w = *this;
+        for (;;) {
+            const bool need = !w.done && w.leaf == 0u && w.sp < 0 && w.mask == 0u;
+            if (wballot(need) == 0ull) break;
             if (need) {
-                bool may = true;
-                if (s0 + 32u < nsub) {
-                    s0 += 32u;
+                if (w.s0 + 32u < w.nsub) {
+                    w.s0 += 32u;
                 } else {
                     const f3 winv = mk(__builtin_amdgcn_rcpf(ray.d.x), __builtin_amdgcn_rcpf(ray.d.y),
                                        __builtin_amdgcn_rcpf(ray.d.z));
-                    // (COUNT: every instance is walked; the cull is only checked below)
-                    while (next < sc.n_inst) {
-                        may = !PTX_INST_CULL || !rfin || inst_may_hit(sc, insts[next], ray.o, winv, omax, vy);
-                        if (may || COUNT) break;
-                        ++next;
+                    while (w.next < sc.n_inst) {
+                        if (!PTX_INST_CULL || !w.rfin || inst_may_hit(sc, insts[w.next], ray.o, winv, w.omax, w.vy)) break;
+                        ++w.next;
                     }
-                    if (next >= sc.n_inst) {
-                        done = true;
+                    if (w.next >= sc.n_inst) {
+                        w.done = true;
                     } else {
-                        cur = next++;
-                        const Inst &I = insts[cur];
+                        w.cur = w.next++;
+                        const Inst &I = insts[w.cur];
                         if (PROF) pf.hit(PROF_INST);
                         // TransformRayWithMat4x4(InRay, M^-1, false), SH/PT_1_InitPass.wgsl:486-496
-                        lo = xform_point(I.minv, ray.o);
+                        w.lo = xform_point(I.minv, ray.o);
                         const f3 le = xform_point(I.minv, ray.o + ray.d);
-                        ld = le - lo;
-                        inv = mk(1.0f / ld.x, 1.0f / ld.y, 1.0f / ld.z);
-                        sub_base = I.sub_base;
-                        nsub = I.nsub;
-                        tri_base = I.tri_base;
-                        s0 = 0u;
-                        n_aabb += nsub;  // the reference tests every sub-mesh root once
+                        w.ld = le - w.lo;
+                        w.inv = mk(1.0f / w.ld.x, 1.0f / w.ld.y, 1.0f / w.ld.z);
+                        w.sub_base = I.sub_base;
+                        w.nsub = I.nsub;
+                        w.tri_base = I.tri_base;
+                        w.s0 = 0u;
+                        w.n_aabb += w.nsub;  // the reference tests every sub-mesh root once
                     }
                 }
-                if (!done && nsub != 0u) {
+                if (!w.done && w.nsub != 0u) {
                     // pre-filter: every root of the chunk against the best t at this point (the
                     // reference tests root s with the best t after roots < s, never larger; the
-                    // exact test is repeated when a root is taken, below)
-                    const uint32_t nc = nsub - s0 < 32u ? nsub - s0 : 32u;
-                    mask |= root_mask<PROF>(subs + (sub_base + s0), nc, lo, inv, vx, vy, pf);
-                    vy_pf = vy;
-                    if (COUNT && PTX_INST_CULL && !may && mask != 0u) atomicAdd(&sc.counters[CNT_CULL_MISS], 1ull);
+                    // exact test is repeated when a root is taken, in nodes())
+                    const uint32_t nc = w.nsub - w.s0 < 32u ? w.nsub - w.s0 : 32u;
+                    w.mask |= root_mask<PROF>(subs + (w.sub_base + w.s0), nc, w.lo, w.inv, vx, w.vy, pf);
+                    w.vy_pf = w.vy;
                 }
             }
         }
-        // node loop: pops and root takes through one LDS read (as trace_core_tab UNI)
+        *this = w;
+    }
+    // node loop: pops and root takes through one LDS read (`subs` and the stack both in LDS): the
+    // next reference comes from the stack top or -- with an empty stack -- from the next queued
+    // root's record, through one selected address.  A root is re-tested only when a hit has moved
+    // the bound since the pre-filter (else the pre-filter's result is the reference's test).
+    // (predicated: lanes without work read a valid slot and keep their state)
+    template <bool PROF>
+    __device__ __forceinline__ void nodes(const Scene &sc, const SubRoot *subs, uint32_t *stack, uint32_t stride,
+                                          Prof &pf) {
+        FlatWalk w = *this;
         for (;;) {
-            const bool want = leaf == 0u && (sp >= 0 || mask != 0u);
+            const bool want = w.leaf == 0u && (w.sp >= 0 || w.mask != 0u);
             const unsigned long long wm = wballot(want);
             if (wm == 0ull) break;
             // early leaf phase (PTX_EARLY_LEAF_K > 0): once at most K lanes still descend and
@@ -890,140 +874,139 @@ __device__ __forceinline__ Hit trace_core_flat(const Scene &sc, const SubRoot *s
             // is tested before its next pop either way); only the interleaving across lanes.
             if constexpr (PTX_EARLY_LEAF_K > 0) {
                 if (__builtin_popcountll(wm) <= PTX_EARLY_LEAF_K &&
-                    __builtin_popcountll(wballot(leaf != 0u)) >= PTX_EARLY_LEAF_L)
+                    __builtin_popcountll(wballot(w.leaf != 0u)) >= PTX_EARLY_LEAF_L)
                     break;
             }
             if (PROF && want) pf.hit(PROF_NODE);
-            const bool from_root = sp < 0;
-            const uint32_t k = (from_root && mask != 0u) ? (uint32_t)__builtin_ctz(mask) : 0u;
-            const SubRoot *R = subs + (sub_base + s0 + k);
-            const uint32_t *src = from_root ? &R->ref : &stack[(uint32_t)(from_root ? 0 : sp) * stride];
+            const bool from_root = w.sp < 0;
+            const uint32_t k = (from_root && w.mask != 0u) ? (uint32_t)__builtin_ctz(w.mask) : 0u;
+            const SubRoot *R = subs + (w.sub_base + w.s0 + k);
+            const uint32_t *src = from_root ? &R->ref : &stack[(uint32_t)(from_root ? 0 : w.sp) * stride];
             const uint32_t ref = *src;
             const bool tk_root = want && from_root;
             bool take = want;
-            if (tk_root && !(vy == vy_pf)) take = box_root(lo, inv, *R, vx, vy);
-            mask = tk_root ? (mask & (mask - 1u)) : mask;
-            sp = (want && !from_root) ? sp - 1 : sp;
-            grp = (tk_root && take) ? s0 + k : grp;
+            if (tk_root && !(w.vy == w.vy_pf)) take = box_root(w.lo, w.inv, *R, vx, w.vy);
+            w.mask = tk_root ? (w.mask & (w.mask - 1u)) : w.mask;
+            w.sp = (want && !from_root) ? w.sp - 1 : w.sp;
+            w.grp = (tk_root && take) ? w.s0 + k : w.grp;
             const bool is_leaf = (ref & LEAF_BIT) != 0u;
-            leaf = (take && is_leaf) ? ref : leaf;
+            w.leaf = (take && is_leaf) ? ref : w.leaf;
             if (!(take && !is_leaf)) continue;
             const float4 *np = reinterpret_cast<const float4 *>(sc.nodes + ref);
             float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
             uint32_t lref = __float_as_uint(q3.x), rref = __float_as_uint(q3.y);
             float tl, tr;
             bool hl, hr;
-            box_pair(lo, inv, q0, q1, q2, vx, vy, hl, hr, tl, tr);
-            n_aabb += 2;
+            box_pair(w.lo, w.inv, q0, q1, q2, vx, w.vy, hl, hr, tl, tr);
+            w.n_aabb += 2;
             const bool both = hl && hr;
             const uint32_t near = tl < tr ? lref : rref, far = tl < tr ? rref : lref;
-            stack[(uint32_t)(sp + 1) * stride] = both ? far : (hl ? lref : rref);
-            stack[(uint32_t)(sp + 2) * stride] = near;
-            sp += both ? 2 : ((hl || hr) ? 1 : 0);
+            stack[(uint32_t)(w.sp + 1) * stride] = both ? far : (hl ? lref : rref);
+            stack[(uint32_t)(w.sp + 2) * stride] = near;
+            w.sp += both ? 2 : ((hl || hr) ? 1 : 0);
         }
-        const unsigned long long holders = wballot(leaf != 0u);
-        if (holders == 0ull) {
-            if (wballot(!done) == 0ull) break;  // every lane has walked every instance
-            continue;
-        }
-        // cooperative leaf phase (trace_core_tab COOP), the owner's triangle base included
+        *this = w;
+    }
+    // cooperative leaf phase (coop_leaf_deal).  Returns whether any lane held a leaf.  ANY: a hit
+    // with t <= t_stop ends the lane's walk.
+    template <bool PROF, bool ANY>
+    __device__ __forceinline__ bool leaves(const Scene &sc, CoopLds coop, PassEps eps, float t_stop, Prof &pf) {
+        if (wballot(leaf != 0u) == 0ull) return false;
+        FlatWalk w = *this;
         if (PROF) pf.hit(PROF_LEAF);
-        const uint32_t lane = __lane_id();
-        const uint32_t cnt = leaf ? (leaf >> 24) & 0x7Fu : 0u, lfirst = leaf & LEAF_FIRST_MASK;
-        uint32_t total;
-        const uint32_t excl = wave_excl_sum(cnt, total);
-        __hip_atomic_store(&coop.key[lane], ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        bool nan_seen = false;
-        for (uint32_t c0 = 0; c0 < total; c0 += 64u) {
-            const uint32_t u = c0 + lane;
-            const int owner = deal_owner(coop, lane, cnt, excl, c0);
-            // triangle u of the deal: the owner's leaf triangle lfirst + (u - excl), in its instance
-            const uint32_t tri = u + __shfl(lfirst - excl, owner);
-            const uint32_t tb = __shfl(tri_base, owner);
-            const f3 olo = mk(__shfl(lo.x, owner), __shfl(lo.y, owner), __shfl(lo.z, owner));
-            const f3 old = mk(__shfl(ld.x, owner), __shfl(ld.y, owner), __shfl(ld.z, owner));
-            const float ovy = __shfl(vy, owner);
-            if (u < total) {
-                if (PROF) pf.hit(PROF_TRI);
-                const float4 *tp = sc.tris + 3u * (tb + tri);
-                const float t = ray_tri(olo, old, tp[0], tp[1], tp[2], eps.det_eps);
-                if (t != t) nan_seen = true;
-                else if (!(ovy < t))
-                    atomicMin(&coop.key[owner],
-                              ((unsigned long long)__float_as_uint(t) << 32) | (unsigned long long)(0xffffffffu - tri));
-            }
-        }
-        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        if (wballot(nan_seen) == 0ull) {
-            if (leaf) {
-                const unsigned long long key = __hip_atomic_load(&coop.key[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                n_tri += cnt;
+        unsigned long long key;
+        if (!coop_leaf_deal<PROF>(sc, coop, eps, w.leaf, w.tri_base, w.lo, w.ld, w.vy, pf, key)) {
+            if (w.leaf) {
+                w.n_tri += (w.leaf >> 24) & 0x7Fu;
                 if (key != ~0ull) {
-                    vy = __uint_as_float((uint32_t)(key >> 32));
-                    best.valid = true;
-                    best.s.inst = cur;
-                    best.s.mat = grp;
-                    best.s.prim = 0xffffffffu - (uint32_t)key;
+                    w.vy = __uint_as_float((uint32_t)(key >> 32));
+                    w.bvalid = true;
+                    w.binst = w.cur;
+                    w.bmat = w.grp;
+                    w.bprim = 0xffffffffu - (uint32_t)key;
                 }
             }
-        } else if (leaf) {  // a NaN t somewhere in the wave: this phase's leaves one by one
-            const uint32_t first = leaf & LEAF_FIRST_MASK, count = (leaf >> 24) & 0x7Fu;
-            const float4 *tp = sc.tris + 3u * (tri_base + first);
+        } else if (w.leaf) {  // a NaN t somewhere in the wave: this phase's leaves one by one
+            const uint32_t first = w.leaf & LEAF_FIRST_MASK, count = (w.leaf >> 24) & 0x7Fu;
+            const float4 *tp = sc.tris + 3u * (w.tri_base + first);
             for (uint32_t k = 0; k < count; ++k) {
                 if (PROF) pf.hit(PROF_TRI);
-                const float t = ray_tri(lo, ld, tp[3u * k + 0u], tp[3u * k + 1u], tp[3u * k + 2u], eps.det_eps);
-                ++n_tri;
-                if (vy < t) continue;
-                vy = t;
-                best.valid = true;
-                best.s.inst = cur;
-                best.s.mat = grp;
-                best.s.prim = first + k;
-                if (ANY && !(vy > t_stop)) break;
+                const float t = ray_tri(w.lo, w.ld, tp[3u * k + 0u], tp[3u * k + 1u], tp[3u * k + 2u], eps.det_eps);
+                ++w.n_tri;
+                if (w.vy < t) continue;
+                w.vy = t;
+                w.bvalid = true;
+                w.binst = w.cur;
+                w.bmat = w.grp;
+                w.bprim = first + k;
+                if (ANY && !(w.vy > t_stop)) break;
             }
         }
-        leaf = 0u;
-        if (ANY && best.valid && !(vy > t_stop) && !done) {  // occluded: no more work for this lane
-            done = true;
-            sp = -1;
-            mask = 0u;
+        w.leaf = 0u;
+        if (ANY && w.bvalid && !(w.vy > t_stop) && !w.done) {  // occluded: no more work for this lane
+            w.done = true;
+            w.sp = -1;
+            w.mask = 0u;
         }
+        *this = w;
+        return true;
     }
+    // the hit record so far: instance / sub-mesh / primitive and t; barycentrics and position
+    // are complete_hit's
+    __device__ __forceinline__ Hit hit() const {
+        Hit h;
+        h.valid = bvalid;
+        h.t = bvalid ? vy : 0.0f;
+        h.s = Compact{0u, binst, bmat, bprim, 0.0f, 0.0f};
+        h.pos = mk(0.0f, 0.0f, 0.0f);
+        return h;
+    }
+    // PROF: the culled walk's executed tests of one query, into the work counters
+    __device__ __forceinline__ void count(const Scene &sc) const {
+        atomicAdd(&sc.counters[CNT_RAYS], 1ull);
+        atomicAdd(&sc.counters[CNT_INST], (unsigned long long)sc.n_inst);
+        atomicAdd(&sc.counters[CNT_AABB], (unsigned long long)n_aabb);
+        atomicAdd(&sc.counters[CNT_TRI], (unsigned long long)n_tri);
+        if (bvalid) atomicAdd(&sc.counters[CNT_HITS], 1ull);
+    }
+};
+// One batch: every lane of the wave walks its ray (t_max NaN: none) until all are done.  The hit
+// comes back without barycentrics and position (complete_hit).
+template <bool PROF = false, bool ANY = false>
+__device__ __forceinline__ Hit trace_core_flat(const Scene &sc, const SubRoot *subs, const Inst *insts, Ray ray,
+                                               PassEps eps, uint32_t *stack, uint32_t stride, float t_max,
+                                               CoopLds coop, float t_stop = 3.0e38f) {
+    Prof pf{};
+    FlatWalk wk;
+    wk.begin(ray, t_max);
+    for (;;) {
+        wk.refill<PROF>(sc, subs, insts, ray, pf);
+        wk.nodes<PROF>(sc, subs, stack, stride, pf);
+        // no leaf anywhere and no lane with an instance left: every lane has walked every instance
+        if (!wk.leaves<PROF, ANY>(sc, coop, eps, t_stop, pf) && wballot(!wk.done) == 0ull) break;
+    }
+    const bool counted = t_max == t_max;
     if (PROF && counted) {
-        for (int r = 0; r < PROF_REGIONS; ++r) {
-            if (pf.wave[r]) atomicAdd(&sc.counters[8 + 2 * r], (unsigned long long)pf.wave[r]);
-            if (pf.lane[r]) atomicAdd(&sc.counters[9 + 2 * r], (unsigned long long)pf.lane[r]);
-        }
+        prof_flush(sc, pf);
+        wk.count(sc);
     }
 #ifdef PTX_WG_TIMES
-    if (sc.wgt && counted && n_aabb >= kStragglerAabb) {
+    if (sc.wgt && counted && wk.n_aabb >= kStragglerAabb) {
         const unsigned long long i = atomicAdd(sc.wgt, 2ull);
         if (i + 1u < (1ull << 20)) {
             unsigned long long *r = sc.wgt + 4u + 4u * i;
             r[0] = pk2(ray.o.x, ray.o.y);
             r[1] = pk2(ray.o.z, ray.d.x);
-            r[2] = ((unsigned long long)KID_STRAGGLER << 32) | n_aabb;
-            r[3] = (unsigned long long)n_tri | ((unsigned long long)__float_as_uint(t_max) << 32);
+            r[2] = ((unsigned long long)KID_STRAGGLER << 32) | wk.n_aabb;
+            r[3] = (unsigned long long)wk.n_tri | ((unsigned long long)__float_as_uint(t_max) << 32);
             r[4] = pk2(ray.d.y, ray.d.z);
-            r[5] = (unsigned long long)__float_as_uint(best.valid ? vy : -1.0f) | ((unsigned long long)best.s.inst << 32);
-            r[6] = ((unsigned long long)KID_STRAGGLER2 << 32) | best.s.prim;
-            r[7] = best.s.mat;
+            r[5] = (unsigned long long)__float_as_uint(wk.bvalid ? wk.vy : -1.0f) | ((unsigned long long)wk.binst << 32);
+            r[6] = ((unsigned long long)KID_STRAGGLER2 << 32) | wk.bprim;
+            r[7] = wk.bmat;
         }
     }
 #endif
-    if ((COUNT || PROF) && counted) {  // (PROF alone: the culled walk's executed tests)
-        atomicAdd(&sc.counters[CNT_RAYS], 1ull);
-        atomicAdd(&sc.counters[CNT_INST], (unsigned long long)sc.n_inst);
-        atomicAdd(&sc.counters[CNT_AABB], (unsigned long long)n_aabb);
-        atomicAdd(&sc.counters[CNT_TRI], (unsigned long long)n_tri);
-        if (best.valid) atomicAdd(&sc.counters[CNT_HITS], 1ull);
-    }
-    if (best.valid) {
-        best.t = vy;
-        if (!ANY && want_pos) complete_hit(sc, ray, eps, best, insts);
-    }
-    return best;
+    return wk.hit();
 }
 
 // Sub-root and instance tables staged in LDS when they fit: every ray tests every root of

@@ -17,15 +17,19 @@
 // serialises at ~4 ns per wave-level append, which cost more than the shading itself).
 //
 // Kernels (256-thread workgroups, one per segment):
-//   trace_queue  -- lean closest-hit / Visibility queries over a ray segment (≈70
-//                   VGPRs); the Visibility loop (<=5 traces through transmissive hits,
-//                   SH/PT_1_InitPass.wgsl:774-802) runs inside it, pruned at the light.
+//   trace_queue  -- closest-hit / Visibility / occlusion queries over a ray segment: the
+//                   flattened walk (FlatWalk, ptx_device.h) streamed over the segment's
+//                   queries (trace_stream, ptx_stream.h) at 5 waves per SIMD; the Visibility
+//                   loop (<=5 traces through transmissive hits, SH/PT_1_InitPass.wgsl:774-802)
+//                   runs inside it, pruned at the light (end_query, ptx_wave_common.h).
+//   wfinal_one / wfinal_replay -- PT_4 in one launch, its few replays walked inline with the
+//                   same walk, a batch at a time (trace_core_flat).
 //   *_start      -- per pixel: first vertex, emits the first round of rays.
 //   *_step       -- per active pixel: consumes its results, advances to the next vertex,
 //                   emits the next round.  Pixel state lives in HBM (SoA float4 slots).
 // Rounds: init <= 3 traces (vertices 1..3), final <= 3 (two regenerated BSDF rays + the
 // light visibility), MCPT <= 4 (primary + 3 bounces with all lights' shadow rays).
-#include "ptx_wave_common.h"
+#include "ptx_stream.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -38,82 +42,39 @@ namespace ptx {
 // Visibility only looks at the closest hit when its t <= remain, and the cap leaves the visit
 // order -- hence which of several equal-t triangles wins -- unchanged for every hit inside it.
 // OCC: every query of the launch is Q_OCC (the GI shift's binary visibility): an any-hit
-// walk (trace_core_tab ANY), exact for "is there a hit with t <= remain".
+// walk (ANY), exact for "is there a hit with t <= remain".
+// Which walk: tables in LDS and not counting -> the flat walk (FlatWalk, ptx_device.h), streamed
+// over the segment (trace_stream); otherwise -- tables too large for LDS, or a counting instance,
+// which walks every instance -- trace_core_tab, batch by batch.
 #ifndef TRACE_OCC_WAVES
 #define TRACE_OCC_WAVES 5  // occupancy of the occlusion-query instance (GI spatial rounds)
 #endif
-#ifndef TRACE_COOP
-#define TRACE_COOP true
-#endif
-// One wave's batch of up to 64 queries (lane i of `rays` / `res`; `active` = lane has one).
-// Every lane of the wave calls the traversal every time -- lanes without a query (past the
-// segment's end, or whose Visibility walk is over) with a NaN bound, which no box overlaps --
-// so the whole wave takes part in the cooperative leaf phases.
-#ifndef PTX_NODE_UNI
-#define PTX_NODE_UNI 1  // one pop / root-take path in the node loop when the tables sit in LDS
-#endif
-#ifndef PTX_FLAT_INST
-#define PTX_FLAT_INST 1  // the instance loop flattened into the lanes (trace_core_flat) for scenes
-#endif                   // of >= kFlatMinInstances instances (host side, wave_trace)
-// Measured same box (1080p): furnished C3 (13 instances) +9.7 %, GI on C3 (3) +3.2 %, reuse on
-// C3 +0.6 %, TEST_MCPT on C1 (2 instances) -3.2 % (round 3, batch walk).  With the streamed lanes
-// (trace_stream, flat walk only) C1 gains too -- TEST_MCPT 1448 -> 1512, ReSTIR 1388 -> 1417
-// Msamples/s (round 5) -- so every scene takes the flat walk.
-constexpr uint32_t kFlatMinInstances = 1u;
-#ifndef PTX_LDS_TRANS
-#define PTX_LDS_TRANS 1  // the restart test's transmission from the LDS root table (A/B: 0 = Scene::mats)
-#endif
-// The queries of one wave: lane state {ray, kind, transmittance T, remaining distance, segment}
-// for query slot gi (its result at res[2 gi]).  Visibility (SH/PT_1_InitPass.wgsl:774-802) walks
-// through transmissive hits: one trace site, looped, so the traversal code is emitted once.
+// The queries of one wave's batch: lane state {ray, kind, transmittance T, remaining distance,
+// segment} for query slot gi (its result at res[2 gi]; `active` = the lane has one).  Every lane of
+// the wave calls the traversal every time -- lanes without a query (past the segment's end, or
+// whose Visibility walk is over) with a NaN bound, which no box overlaps -- so the whole wave takes
+// part in the cooperative leaf phases.  Visibility walks on through transmissive hits (end_query):
+// one trace site, looped, so the traversal code is emitted once.
 // (A form that parked a wave's few restarting lanes in a per-wave pool and walked them later as
 // one batch measured -7.5 % on the headline, 442 vs 477 Msamples/s: round 4)
-template <bool COUNT, bool PROF, bool OCC, bool LDS_TABLES, bool FLAT>
+template <bool COUNT, bool PROF, bool OCC, bool LDS_TABLES>
 __device__ __forceinline__ void trace_lanes(const Scene &sc, const SubRoot *subs, const Inst *insts, PassEps eps,
                                             uint32_t *stack, CoopLds coop, Ray r, uint32_t kind, float T, float remain,
                                             uint32_t seg, bool active, float4 *res, uint32_t gi) {
-    const bool vis = kind != Q_CLOSEST;
     for (;;) {
-        const float t_max = !active ? __builtin_nanf("") : vis ? vis_bound(remain) : 1e10f;
-        // a Visibility hit's position is only needed to restart through a transmissive surface:
-        // it is reconstructed below for those lanes only
-        Hit h = (LDS_TABLES && FLAT)
-                    ? trace_core_flat<COUNT, PROF, OCC>(sc, subs, insts, r, eps, stack, WB, t_max, coop, !vis, remain)
-                    : trace_core_tab<COUNT, PROF, true, OCC, TRACE_COOP, LDS_TABLES && PTX_NODE_UNI>(
-                          sc, subs, insts, r, eps, stack, WB, t_max, coop, !vis, remain);
-        if (active && !vis) {
-            const uint32_t enc = ((h.valid ? 1u : 0u) << 31) | (h.s.inst << 16) | h.s.mat;
-            res[2u * gi] = make_float4(h.t, asf(enc), asf(h.s.prim), h.s.bu);
-            res[2u * gi + 1u] = make_float4(h.s.bv, h.pos.x, h.pos.y, h.pos.z);
-            active = false;
-        } else if (active) {
-            float out = -1.0f;
-            if (!h.valid || h.t > remain) out = T;
-            else {
-                const float tr = kind == Q_OCC              ? 0.0f
-                                 : PTX_LDS_TRANS ? subs_transmission(subs, insts, h.s.inst, h.s.mat)
-                                                 : get_transmission(sc, h.s.inst, h.s.mat);
-                if (tr == 0.0f) out = 0.0f;
-                else {
-                    T *= tr;
-                    remain -= h.t;
-                    complete_hit(sc, r, eps, h, insts);
-                    r.o = h.pos;
-                    if (seg == 4u) out = 0.0f;  // Visibility gives up after 5 segments
-                    ++seg;
-                }
-            }
-            if (out >= 0.0f) {  // only res.x is written: .yzw and res[2i+1] carry the payload
-                res[2u * gi].x = out;
-                active = false;
-            }
-        }
+        const float t_max = !active ? __builtin_nanf("") : kind != Q_CLOSEST ? vis_bound(remain) : 1e10f;
+        // (the hit's position is end_query's business: a Visibility walk needs it only to restart)
+        const Hit h = (LDS_TABLES && !COUNT)
+                          ? trace_core_flat<PROF, OCC>(sc, subs, insts, r, eps, stack, WB, t_max, coop, remain)
+                          : trace_core_tab<COUNT, PROF, true, OCC, true>(sc, subs, insts, r, eps, stack, WB, t_max, coop,
+                                                                         false, remain);
+        if (active && end_query(sc, subs, insts, eps, h, r, kind, T, remain, seg, res, gi)) active = false;
         if (wballot(active) == 0ull) break;
     }
 }
 // Lane i of the wave traces query i of a batch (`rays` / `res` = the segment's, slot
 // gbase + i of the launch's buffers rays_all / res_all).
-template <bool COUNT, bool PROF, bool OCC, bool LDS_TABLES = false, bool FLAT = false>
+template <bool COUNT, bool PROF, bool OCC, bool LDS_TABLES>
 __device__ __forceinline__ void trace_batch(const Scene &sc, const SubRoot *subs, const Inst *insts, PassEps eps,
                                             uint32_t *stack, CoopLds coop, float4 *res_all, const float4 *rays_all,
                                             uint32_t gbase, uint32_t i, bool active) {
@@ -123,14 +84,11 @@ __device__ __forceinline__ void trace_batch(const Scene &sc, const SubRoot *subs
         a = rays_all[2u * gi];
         b = rays_all[2u * gi + 1u];
     }
-    trace_lanes<COUNT, PROF, OCC, LDS_TABLES, FLAT>(sc, subs, insts, eps, stack, coop, Ray{mk(a.x, a.y, a.z), mk(b.x, b.y, b.z)},
-                                                    asu(b.w), 1.0f, a.w, 0u, active, res_all, gi);
+    trace_lanes<COUNT, PROF, OCC, LDS_TABLES>(sc, subs, insts, eps, stack, coop, Ray{mk(a.x, a.y, a.z), mk(b.x, b.y, b.z)},
+                                              asu(b.w), 1.0f, a.w, 0u, active, res_all, gi);
 }
-}  // namespace ptx
-#include "ptx_stream.h"
-namespace ptx {
 
-template <bool COUNT, int WAVES, bool PROF = false, bool LDS_TABLES = true, bool OCC = false, bool FLAT = false>
+template <bool COUNT, int WAVES, bool PROF = false, bool LDS_TABLES = true, bool OCC = false>
 __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(WAVES, 8)))
 void trace_queue(Scene sc, WaveBufs w, uint32_t round, PassEps eps) {
     PTX_WAVE_TIMER(sc, KID_TRACE | (w.seg_base ? 0x80u : 0u));
@@ -150,7 +108,7 @@ void trace_queue(Scene sc, WaveBufs w, uint32_t round, PassEps eps) {
     const LdsTables T = LDS_TABLES ? stage_tables(sc, wstack) : LdsTables{sc.subs, sc.insts};
     const SubRoot *subs = T.subs;
     const Inst *insts = T.insts;
-    if constexpr (PTX_TRACE_STREAM && LDS_TABLES && FLAT && !COUNT) {  // lane refill over the segment
+    if constexpr (PTX_TRACE_STREAM && LDS_TABLES && !COUNT) {  // lane refill over the segment
         trace_stream<PROF, OCC>(sc, subs, insts, eps, stack, coop, w, res_buf(w, round), &l_next, j, n);
         return;
     }
@@ -158,8 +116,8 @@ void trace_queue(Scene sc, WaveBufs w, uint32_t round, PassEps eps) {
         sc.counters = sc.census + (size_t)kCensusWords * ((sc.row_end - sc.row_begin + 7u) / 8u + j);
     for (uint32_t i0 = 0u; i0 < n; i0 += WB) {  // workgroup-uniform
         const uint32_t i = i0 + threadIdx.x;
-        trace_batch<COUNT, PROF, OCC, LDS_TABLES, FLAT>(sc, subs, insts, eps, stack, coop, res_buf(w, round), w.rays,
-                                                         j * w.ray_stride, i, i < n);
+        trace_batch<COUNT, PROF, OCC, LDS_TABLES>(sc, subs, insts, eps, stack, coop, res_buf(w, round), w.rays,
+                                                   j * w.ray_stride, i, i < n);
     }
 }
 
@@ -789,7 +747,6 @@ __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(LOGIC_WAVES,
 
 // wfinal_one's replay of a wave's live pixels (`active`, state `s`, reservoir `resv`): each emits
 // its ray into its own queue slot, the whole wave walks it, the step consumes it.
-template <bool FLAT>
 __device__ __forceinline__ void wfinal_walk(const Scene &sc, const LdsTables &T, const PassEps &eps, uint32_t *stack,
                                             const CoopLds &coop, float4 *rays, float4 *res, uint32_t slot,
                                             const uint4 *resv, float4 *accum, uint32_t pix, bool active, WFinal &s) {
@@ -817,7 +774,7 @@ __device__ __forceinline__ void wfinal_walk(const Scene &sc, const LdsTables &T,
             }
         }
         // the traversal kernel's walk, every lane of the wave (idle ones with a NaN bound)
-        trace_batch<false, false, false, true, FLAT>(sc, T.subs, T.insts, eps, stack, coop, res, rays, 0u, slot, active);
+        trace_batch<false, false, false, true>(sc, T.subs, T.insts, eps, stack, coop, res, rays, 0u, slot, active);
         if (active) {  // wfinal_step
             if (s.phase == 0u) {
                 const Hit h = get_hit(res, slot);
@@ -845,7 +802,6 @@ __device__ __forceinline__ void wfinal_walk(const Scene &sc, const LdsTables &T,
 // ray into their own queue slot, the whole wave walks it (trace_batch, every lane, the
 // traversal kernel's code), and the step consumes it -- the same rays, results and arithmetic as
 // wfinal_emit / trace_queue / wfinal_step, so the frame is bit-identical.
-template <bool FLAT>
 __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(2, 8)))
 void wfinal_one(Scene sc, WaveBufs w, const uint4 *gbuf, const uint4 *reservoir, float4 *accum, PassEps eps) {
     PTX_WAVE_TIMER(sc, KID_FINAL_START | (w.seg_base ? 0x80u : 0u));
@@ -889,7 +845,7 @@ void wfinal_one(Scene sc, WaveBufs w, const uint4 *gbuf, const uint4 *reservoir,
                 }
             }
         }
-        wfinal_walk<FLAT>(sc, T, eps, stack, coop, rays, res, slot, reservoir + 8u * (size_t)pix, accum, pix, active, s);
+        wfinal_walk(sc, T, eps, stack, coop, rays, res, slot, reservoir + 8u * (size_t)pix, accum, pix, active, s);
     }
 }
 
@@ -898,7 +854,6 @@ void wfinal_one(Scene sc, WaveBufs w, const uint4 *gbuf, const uint4 *reservoir,
 // pixels with wfinal_one's code (the same rays, results and arithmetic per pixel; the list's
 // order decides nothing), and zeroes the count it consumed.  An empty list -- practically every
 // segment of every natural frame -- costs its workgroup one load.
-template <bool FLAT>
 __global__ __launch_bounds__(WB) __attribute__((amdgpu_waves_per_eu(2, 8)))
 void wfinal_replay(Scene sc, WaveBufs w, const uint4 *gbuf, const uint4 *reservoir, float4 *accum,
                    const uint32_t *replay, uint32_t *replay_cnt, PassEps eps) {
@@ -932,7 +887,7 @@ void wfinal_replay(Scene sc, WaveBufs w, const uint4 *gbuf, const uint4 *reservo
             s.f = mk(1.0f, 1.0f, 1.0f);
             s.i = 1u;
         }
-        wfinal_walk<FLAT>(sc, T, eps, stack, coop, rays, res, slot, reservoir + 8u * (size_t)pix, accum, pix, active, s);
+        wfinal_walk(sc, T, eps, stack, coop, rays, res, slot, reservoir + 8u * (size_t)pix, accum, pix, active, s);
     }
 }
 
@@ -1121,25 +1076,20 @@ hipError_t wave_trace(const Scene &sc, const WaveBufs &w, int round, int eps_mod
     const PassEps eps = eps_mode == 0 ? PassEps{1e-8f, 1e-6f} : PassEps{1e-4f, 1e-8f};
     // dynamic LDS: scene tables (the LDS-table variants) + stacks
     const size_t lds = (tables_fit_lds(sc) ? tables_lds_bytes(sc) : 0u) + stack_lds_bytes(depth);
-    static const uint32_t flat_min = (uint32_t)ab_knob("FLAT_MIN_INST", (int)kFlatMinInstances);  // A/B
-    const bool flat = PTX_FLAT_INST && sc.n_inst >= flat_min;
     if (occ_only && tables_fit_lds(sc)) {  // occlusion rounds (GI spatial)
         if (sc.counters)
             hipLaunchKernelGGL((trace_queue<true, 6, false, true, true>), dim3(trace_grid(w)), dim3(WB), lds, s, sc, w,
                                (uint32_t)round, eps);
-        else if (flat)
-            hipLaunchKernelGGL((trace_queue<false, TRACE_OCC_WAVES, false, true, true, true>), dim3(trace_grid(w)), dim3(WB), lds,
-                               s, sc, w, (uint32_t)round, eps);
         else
             hipLaunchKernelGGL((trace_queue<false, TRACE_OCC_WAVES, false, true, true>), dim3(trace_grid(w)), dim3(WB), lds, s, sc, w,
                                (uint32_t)round, eps);
         return hipGetLastError();
     }
     if (sc.counters && ab_knob("TRACE_PROF", 0)) {  // SIMD-utilisation diagnostics
-        if (flat && tables_fit_lds(sc))  // (the production walk: flattened instances, LDS tables, and
+        if (tables_fit_lds(sc))  // (the production walk: flattened instances, LDS tables, and
             // COUNT off so that the instance cull applies as in production -- the PROF regions
-            // still count into sc.counters; the work counters stay zero)
-            hipLaunchKernelGGL((trace_queue<false, 6, true, true, false, true>), dim3(trace_grid(w)), dim3(WB), lds, s, sc, w,
+            // still count into sc.counters, and the work counters hold the culled walk's tests)
+            hipLaunchKernelGGL((trace_queue<false, 6, true, true>), dim3(trace_grid(w)), dim3(WB), lds, s, sc, w,
                                (uint32_t)round, eps);
         else
             hipLaunchKernelGGL((trace_queue<true, 6, true, false>), dim3(trace_grid(w)), dim3(WB), lds, s, sc, w,
@@ -1148,27 +1098,22 @@ hipError_t wave_trace(const Scene &sc, const WaveBufs &w, int round, int eps_mod
     else if (sc.counters)
         hipLaunchKernelGGL((trace_queue<true, 6, false, false>), dim3(trace_grid(w)), dim3(WB), lds, s, sc, w, (uint32_t)round, eps);
     else {
-        // Occupancy target per pipeline (WaveBufs::trace_waves), LDS-staged tables; A/B
-        // switches PTX_AB=TRACE_OCC=n / TRACE_NOLDS.  Measured at 1080p with 768-pixel segments:
-        // 4 waves/SIMD (no spill) is fastest for the per-instance walk (with the flat node loop:
-        // reuse 369-373 vs 339-340, ReSTIR 1301 vs 1235, TEST_MCPT 1359 vs 1261 at 5); 5 for
-        // bands above 4 Mpx; 6+ spills in the node loop.  The flattened walk (>= 3 instances)
-        // runs at 5 (96 VGPRs; its 40 B/lane of spills sit at the batch boundaries, none in the
-        // walk): reuse 462.6 vs 446.6, GI 769.6 vs 757.7, furnished C3 301.6 vs 282.2 (same box,
-        // round 3) -- the launch alone is ~3 % slower, the pipelined frame faster: 96-VGPR
-        // waves leave the other frame's logic waves room on the SIMD.
-        static const int env_occ = ab_knob("TRACE_OCC", 0);
-        const int occ = env_occ ? env_occ : (w.trace_waves == 4u && !flat) ? 4 : 5;
+        // The flat walk runs at 5 waves per SIMD (92 VGPRs, no scratch): reuse 462.6 vs 446.6 at 4,
+        // GI 769.6 vs 757.7, furnished C3 301.6 vs 282.2 (same box, round 3) -- the launch alone
+        // is ~3 % slower, the pipelined frame faster: such waves leave the other frame's logic
+        // waves room on the SIMD; 6+ spills in the node loop.  The measurement build selects the
+        // same walk at other targets (PTX_AB=TRACE_OCC=4 / 6 / 7 / 8) and the global tables for a
+        // scene whose tables fit (TRACE_NOLDS).
         static const bool no_lds = ab_knob("TRACE_NOLDS", 0) != 0;
         const bool tables_fit = tables_fit_lds(sc) && !no_lds;
-        auto k = !tables_fit ? trace_queue<false, 5, false, false>
+        auto k = tables_fit ? trace_queue<false, 5> : trace_queue<false, 5, false, false>;
 #ifdef PTX_AB_BUILD
-                 : occ >= 8  ? trace_queue<false, 8>
-                 : occ == 7  ? (flat ? trace_queue<false, 7, false, true, false, true> : trace_queue<false, 7>)
-                 : occ == 6  ? (flat ? trace_queue<false, 6, false, true, false, true> : trace_queue<false, 6>)
+        static const int occ = ab_knob("TRACE_OCC", 0);
+        if (tables_fit && occ >= 8) k = trace_queue<false, 8>;
+        else if (tables_fit && occ == 7) k = trace_queue<false, 7>;
+        else if (tables_fit && occ == 6) k = trace_queue<false, 6>;
+        else if (tables_fit && occ == 4) k = trace_queue<false, 4>;
 #endif
-                 : occ == 5  ? (flat ? trace_queue<false, 5, false, true, false, true> : trace_queue<false, 5>)
-                             : (flat ? trace_queue<false, 4, false, true, false, true> : trace_queue<false, 4>);
         hipLaunchKernelGGL(k, dim3(trace_grid(w)), dim3(WB), lds, s, sc, w, (uint32_t)round, eps);
     }
     return hipGetLastError();
@@ -1232,11 +1177,7 @@ hipError_t wave_final_one(const Scene &sc, const WaveBufs &w, const uint4 *gbuf,
                           uint32_t depth, hipStream_t s) {
     const PassEps eps{1e-4f, 1e-8f};  // (wave_trace's eps_mode 1, every wavefront pass)
     const size_t lds = tables_lds_bytes(sc) + stack_lds_bytes(depth);
-    static const uint32_t flat_min = (uint32_t)ab_knob("FLAT_MIN_INST", (int)kFlatMinInstances);
-    if (PTX_FLAT_INST && sc.n_inst >= flat_min)
-        hipLaunchKernelGGL(wfinal_one<true>, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir, accum, eps);
-    else
-        hipLaunchKernelGGL(wfinal_one<false>, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir, accum, eps);
+    hipLaunchKernelGGL(wfinal_one, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir, accum, eps);
     return hipGetLastError();
 }
 
@@ -1244,13 +1185,8 @@ hipError_t wave_final_replay(const Scene &sc, const WaveBufs &w, const uint4 *gb
                              const uint32_t *replay, uint32_t *replay_cnt, uint32_t depth, hipStream_t s) {
     const PassEps eps{1e-4f, 1e-8f};  // (wave_final_one's)
     const size_t lds = tables_lds_bytes(sc) + stack_lds_bytes(depth);
-    static const uint32_t flat_min = (uint32_t)ab_knob("FLAT_MIN_INST", (int)kFlatMinInstances);
-    if (PTX_FLAT_INST && sc.n_inst >= flat_min)
-        hipLaunchKernelGGL(wfinal_replay<true>, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir, accum, replay,
-                           replay_cnt, eps);
-    else
-        hipLaunchKernelGGL(wfinal_replay<false>, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir, accum, replay,
-                           replay_cnt, eps);
+    hipLaunchKernelGGL(wfinal_replay, dim3(w.seg_count), dim3(WB), lds, s, sc, w, gbuf, reservoir, accum, replay, replay_cnt,
+                       eps);
     return hipGetLastError();
 }
 

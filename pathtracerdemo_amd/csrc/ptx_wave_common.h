@@ -147,6 +147,45 @@ __device__ __forceinline__ Hit get_hit(const float4 *res, uint32_t idx) {
     h.pos = mk(b.y, b.z, b.w);
     return h;
 }
+#ifndef PTX_LDS_TRANS
+#define PTX_LDS_TRANS 1  // the restart test's transmission from the LDS root table (A/B: 0 = Scene::mats)
+#endif
+// The end of one walk of query slot gi (kind, transmittance T, remaining distance, segment): `h` is
+// the walk's hit without barycentrics and position.  A closest query writes its hit record.
+// Visibility (SH/PT_1_InitPass.wgsl:774-802) writes T at a miss or a hit past `remain`, 0 at an opaque
+// hit (any hit for Q_OCC) -- only res.x: .yzw and res[2 gi + 1] carry the payload -- and otherwise goes
+// on through the transmissive hit: T *= its transmission, `ray` restarts at the hit position, and the
+// fifth segment gives up with 0.  Returns whether the query is over; false: walk `ray` again.
+__device__ __forceinline__ bool end_query(const Scene &sc, const SubRoot *subs, const Inst *insts, PassEps eps, Hit h,
+                                          Ray &ray, uint32_t kind, float &T, float &remain, uint32_t &seg, float4 *res,
+                                          uint32_t gi) {
+    if (kind == Q_CLOSEST) {
+        if (h.valid) complete_hit(sc, ray, eps, h, insts);
+        const uint32_t enc = ((h.valid ? 1u : 0u) << 31) | (h.s.inst << 16) | h.s.mat;
+        res[2u * gi] = make_float4(h.t, asf(enc), asf(h.s.prim), h.s.bu);
+        res[2u * gi + 1u] = make_float4(h.s.bv, h.pos.x, h.pos.y, h.pos.z);
+        return true;
+    }
+    float out = -1.0f;
+    if (!h.valid || h.t > remain) out = T;
+    else {
+        const float tr = kind == Q_OCC    ? 0.0f
+                         : PTX_LDS_TRANS ? subs_transmission(subs, insts, h.s.inst, h.s.mat)
+                                         : get_transmission(sc, h.s.inst, h.s.mat);
+        if (tr == 0.0f) out = 0.0f;
+        else {
+            T *= tr;
+            remain -= h.t;
+            complete_hit(sc, ray, eps, h, insts);
+            ray.o = h.pos;
+            if (seg == 4u) out = 0.0f;  // Visibility gives up after 5 segments
+            ++seg;
+        }
+    }
+    if (out < 0.0f) return false;
+    res[2u * gi].x = out;
+    return true;
+}
 __device__ __forceinline__ f3 x0_of(const Scene &sc, uint32_t x, uint32_t y) {  // Get_X0, PT_1:732-738
     const float *vpinv = reinterpret_cast<const float *>(sc.U + U_VPINV);
     float u = ((float)x + 0.5f) / (float)sc.U[U_W];

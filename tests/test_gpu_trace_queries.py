@@ -16,12 +16,12 @@ import numpy as np
 import pytest
 
 import trace_rays as TR
-from helpers import huge_tables_scene, many_instances_scene, stress_scene, uniform_for
+from helpers import huge_tables_scene, many_instances_scene, root_chunks_scene, stress_scene, uniform_for
 
 pytestmark = pytest.mark.gpu
 
 W = H = 32
-SCENES = ("c1", "c3", "stress", "many", "huge")
+SCENES = ("c1", "c3", "stress", "many", "huge", "chunks")
 KEYS = ("rays", "instance_xforms", "aabb_tests", "tri_tests", "hits")
 
 
@@ -58,9 +58,9 @@ class SceneData:
 
 
 @pytest.fixture(scope="module")
-def world(scene1, scene3, oracle_mod):
+def world(scene1, scene3, oracle_mod, tmp_path_factory):
     makers = {"c1": lambda: scene1, "c3": lambda: scene3, "stress": stress_scene, "many": many_instances_scene,
-              "huge": huge_tables_scene}
+              "huge": huge_tables_scene, "chunks": lambda: root_chunks_scene(tmp_path_factory.mktemp("chunks"))}
     cache = {}
 
     def get(name):
@@ -134,6 +134,17 @@ def test_closest_families_bit_exact(world, handle, name, pipeline, eps):
         assert_words(got, sc.hits(fam, eps), f"{name} {pipeline} eps {eps} {fam}")
         some_hit |= bool(TR.hit_fields(got)[0].any())
     assert some_hit
+
+
+def test_root_chunk_scene_reaches_every_chunk(world):
+    """The `chunks` scene (helpers.root_chunks_scene: instances of 70, 33 and 70 sub-meshes) is there for
+    the walk's root chunks of 32: over the seven finite families the oracle's hits must land in second
+    and third chunks and in every instance, or the scene's cases above would pin nothing."""
+    sc = world("chunks")
+    valid, inst, sub = (np.concatenate(c) for c in zip(*(TR.hit_fields(sc.hits(f, 1))[:3] for f in TR.FAMILIES)))
+    assert len(valid) == 1792
+    assert (valid & (sub >= 32)).sum() >= 100 and (valid & (sub >= 64)).sum() >= 20
+    assert all((valid & (inst == i)).any() for i in range(3))
 
 
 # ------------------------------------------------------------------ 2: queue-size edges
@@ -216,17 +227,18 @@ def chain_ends(sc, q, eps):
 
 
 @pytest.mark.parametrize("eps", [0, 1])
-@pytest.mark.parametrize("name", ["many", "stress", "huge"])
+@pytest.mark.parametrize("name", ["many", "stress", "huge", "chunks"])
 def test_visibility_and_occlusion(world, handle, name, eps):
     sc = world(name)
     q = mixed_queries(sc, eps)
-    if name != "stress":
+    windows = name in ("many", "huge")
+    if windows:
         wq = window_queries(sc)
         q = np.concatenate([q, wq])
     ref = oracle_results(sc, q, eps)
     kind = q.view(np.uint32)[:, 7]
     assert (ref[kind != TR.Q_CLOSEST, 0] == 0).sum() >= 64 and (ref[kind != TR.Q_CLOSEST, 0] == 1).sum() >= 64
-    if name != "stress":  # (the panes: Visibility walks on through them, an occlusion query stops)
+    if windows:  # (the panes: Visibility walks on through them, an occlusion query stops)
         walked = sc.fr.visibility(wq, eps, return_counters=True)[1]["rays"]
         assert walked >= 2 * len(wq), "the window chains walk several segments each"
     if name == "many":
@@ -244,10 +256,7 @@ def test_visibility_and_occlusion(world, handle, name, eps):
 
 
 # ------------------------------------------------------------------ 5: the counting instance
-def test_counting_handle_closest(world, handle):
-    """count_work=True: the same words, the oracle's traversal work, and an instance cull that would
-    not have lost a root on the families that strain it."""
-    sc, r = world("stress"), handle("stress", count_work=True)
+def counting_closest(sc, r):
     for fam in TR.FAMILIES:
         ref, c_or = sc.fr.trace(sc.rays(fam), 1, return_counters=True)
         r.reset_stats()
@@ -259,7 +268,17 @@ def test_counting_handle_closest(world, handle):
             assert c["cull_misses"] == 0, f"{fam}: {c['cull_misses']} queries would have lost an instance to the cull"
 
 
-@pytest.mark.parametrize("name", ["many", "stress"])
+def test_counting_handle_closest(world, handle):
+    """count_work=True: the same words, the oracle's traversal work, and an instance cull that would
+    not have lost a root on the families that strain it."""
+    counting_closest(world("stress"), handle("stress", count_work=True))
+
+
+def test_counting_handle_closest_root_chunks(world, handle):
+    counting_closest(world("chunks"), handle("chunks", count_work=True))
+
+
+@pytest.mark.parametrize("name", ["many", "stress", "chunks"])
 def test_counting_handle_visibility(world, handle, name):
     """Visibility work.  The kernels walk a Visibility segment under a bound just past `remain`
     (vis_bound, ptx_device.h; at most 1e10) where TraceRay's is 1e10: the smaller bound only prunes

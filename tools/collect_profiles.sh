@@ -31,7 +31,7 @@ for WL in ${WORKLOADS:-reuse restir mcpt gi}; do
   grep '^{' "$line" | tail -n 1 > "$dst/bench_line.json"
   [ -n "$simd" ] && [ -f "$simd" ] && cp "$simd" "$dst/simd_util.txt"
   # the timed roofline symbol only (GI: the closest-hit instance, not the any-hit one); the
-  # flattened walk at 5 waves per SIMD runs every scene since round 5 (kFlatMinInstances = 1)
+  # flattened walk at 5 waves per SIMD, which every scene whose tables fit the LDS takes
   KN="trace_queue<false, 5, false, true, false"
   KEY="$WL:${SCENE[$WL]}:trace_queue:1920x1080"
   if [ -d "$dst/pmc_TCC_REQ_sum" ]; then
