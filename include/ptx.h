@@ -99,6 +99,10 @@ extern "C" {
  * itself (a spatial pass directly followed by PTX_PASS_FINAL in one ptx_render / ptx_run_passes
  * sequence), so PT_4 replayed their paths; zeroed by ptx_reset_stats */
 #define PTX_COUNTER_REPLAY 18
+/* PTX_BUF_COUNTERS word 19, every build: pixels of ptx_upsample_temporal_bands with a history candidate
+ * inside the image but outside the rows the band's state covers (not taken; see
+ * ptx_upsample_temporal_bands); zeroed by ptx_reset_stats */
+#define PTX_COUNTER_UPSAMPLE_CLIP 19
 #define PTX_BUF_RESERVOIR_HIST 4 /* band_h * W * 32 u32: spatial output = Final's input and the
                                     next frame's temporal history (reuse pipeline)           */
 #define PTX_BUF_DIRECT 5     /* band_h * W * 4 f32: direct light of the GI init pass (GI pipeline) */
@@ -109,9 +113,9 @@ extern "C" {
 #define PTX_BUF_DENOISE_HISTORY 8 /* band_h * W * 4 f32 {C.rgb, n}: the temporally integrated colour and the history
                                      length (0..255; 0 = no primary hit) of the last temporal ptx_denoise
                                      (read-only; exists after the first temporal call) */
-#define PTX_BUF_UPSAMPLE_HISTORY 9 /* H * W * 4 f32 {H.rgb, n}: the colour ptx_upsample_temporal integrated and the number
-                                      of own samples in it (0..255) after its last call on this (full-size) handle
-                                      (read-only; exists after the first call) */
+#define PTX_BUF_UPSAMPLE_HISTORY 9 /* band_h * W * 4 f32 {H.rgb, n}: the colour ptx_upsample_temporal (or its band form)
+                                      integrated and the number of own samples in it (0..255) after its last call on
+                                      this (full-size) handle (read-only; exists after the first call) */
 
 #define PTX_FLAG_COUNT_WORK 1u     /* count rays / AABB / triangle tests on device (slower)   */
 #define PTX_FLAG_SIMPLE_KERNELS 2u   /* A/B: one thread per pixel, no ray exchange            */
@@ -441,7 +445,7 @@ int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n,
  * ptx_denoise_bands on hi drop the history (the next call is a first call); ptx_set_frame never does.
  * After the call hi is no source of a ptx_upsample until it has been denoised or upsampled itself.
  *   PTX_E_INVALID with the reason in hi's ptx_last_error, before any GPU work: everything ptx_upsample
- * refuses (band handles: this call has no band form), a phase not below s, a lo whose camera is not that
+ * refuses (band handles: ptx_upsample_temporal_bands), a phase not below s, a lo whose camera is not that
  * phase's (the unshifted camera at s = 2 and s = 4 included), an alpha_min that is not 0 or finite and
  * in (0, 1], an alpha_fill that is not negative-and-finite (the default) or in [0, 1], a non-zero
  * reserved word.
@@ -459,6 +463,54 @@ typedef struct ptx_upsample_temporal_params {
     uint32_t reserved[3]; /* zero */
 } ptx_upsample_temporal_params; /* 32 bytes */
 int ptx_upsample_temporal(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_temporal_params *p /* NULL = defaults, phase (0, 0) */);
+/* ptx_upsample_temporal for a frame split into row bands (Temporal upsampling, bands):
+ * n pairs in band order, lo[i] a band of the small frame after ptx_denoise_bands, hi[i] the band of
+ * the full-size frame with s times its rows.  The forms are ptx_upsample_bands': n pairs of one
+ * process whose lo bands continue one another and cover the frame; n = 1 with two whole-image handles
+ * (exactly ptx_upsample_temporal(hi[0], lo[0], p) with reserved[0] zeroed); or n = 1 with a lo[0] whose
+ * communicator has world > 1: the rank's pair of a frame every rank makes the call for.  Either every
+ * lo owns a communicator or none does (peer copies; several pairs may share a GPU).
+ *   In this call reserved[0] of the parameters is history_rows T: 0 = 32, else 1..128; reserved[1..2]
+ * are zero.  Per pair ptx_upsample_bands' preconditions hold and ptx_upsample_temporal's camera rule:
+ * lo[i]'s words 4..22 are ptx_phase_uniform's of hi[i]'s uniform for (s, px, py), bit for bit.
+ *   The definition is the whole-image call's with every position the frame's; band offsets enter
+ * addresses only.  The small side: full-size row y reads small rows floor((y - py) / s) - 1 .. + 2, so 2
+ * rows of each neighbouring lo band suffice for every phase (their guide records are the ones lo[i]'s
+ * last ptx_denoise_bands left in its window); a pixel's own sample is a row of lo[i] itself.
+ *   The history: a band's state covers rows [Y0 - min(T, Y0), Y1 + min(T, H - Y1)) of the frame: its
+ * own rows as its previous call wrote them, the others its neighbours' own edge rows of their
+ * previous call, brought by this call's exchange.  A candidate tap inside the image but outside the
+ * covered rows is not taken, exactly as if it failed the n' >= 0 test, and a pixel with such a
+ * candidate adds 1 to PTX_COUNTER_UPSAMPLE_CLIP on its band (the same-pixel rule, a pixel without
+ * a primary hit and cw <= 0 never clip).  With the counter 0 on every band the split equals the
+ * whole-image pair bit for bit, in PTX_BUF_DENOISED and PTX_BUF_UPSAMPLE_HISTORY; in general a band's
+ * result is the whole-image definition with the previous state's taps outside its covered rows removed.
+ *   One exchange per call, before the kernels, three messages per side: lo[i]'s first / last 2 rows of
+ * PTX_BUF_DENOISED (16 B per pixel) and, where the frame has a neighbour, the first / last T rows of
+ * the set hi[i] reads, guide records (32 B) and {H, n} (16 B), over lo's communicators (counted in
+ * lo's halo_bytes_sent) or by peer copies.  They are posted in every call; a band without a state (a
+ * first call, or after a drop) sends rows with n below 0, where every tap fails.  Each band takes its
+ * mode (no history / same camera / reproject) from its own state: a band whose state was dropped
+ * alone starts without history and its neighbours find no taps in its rows.
+ *   Everything that drops the whole-image state drops a band's (ptx_upload_scene,
+ * ptx_reset_accumulation, ptx_upsample, ptx_upsample_bands, ptx_denoise, ptx_denoise_bands on hi[i]);
+ * ptx_set_frame never does.  After the call hi[i] is no source of a ptx_upsample.  Buffers of hi[i]:
+ * PTX_BUF_DENOISED and PTX_BUF_UPSAMPLE_HISTORY hold its band_h rows; the two sets carry up to 128
+ * rows above and below the band's (or what the frame has), and with the 2 x 2 small halo rows they
+ * are allocated by the first call and counted in device_bytes.  Nothing of lo changes its bits; of hi
+ * only these buffers do.
+ *   PTX_E_INVALID with the reason in hi[0]'s ptx_last_error, before any GPU work and before anything
+ * is posted: everything ptx_upsample_bands refuses, everything ptx_upsample_temporal refuses about its
+ * parameters, phase and camera, history_rows above 128, with more than one band a full-size band of
+ * fewer than T rows, a mix of lo bands with and without communicators.  ptx_upsample_temporal itself
+ * keeps refusing band handles and non-zero reserved words.
+ *   Ordering: hi[i]'s stream waits for the tail of lo[i]'s last denoise and for its neighbours' rows;
+ * every stream lo[i] can next run on waits until hi[i]'s kernels have read it and, with peer copies,
+ * until the neighbouring pairs have copied its rows; with peer copies hi[i]'s kernels, which write
+ * the set its neighbours copied from in the previous call, wait for their copies.
+ * Launches per band (hi[i]'s PTX_STAT_DENOISE): 2 (guide records, dn_upsample_temporal_win). */
+int ptx_upsample_temporal_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n,
+                                const ptx_upsample_temporal_params *p /* NULL = defaults, phase (0, 0) */);
 /* What ptx_present and ptx_present_async read: PTX_BUF_ACCUM (the default) or PTX_BUF_DENOISED
  * (fails before the first ptx_denoise, ptx_upsample or ptx_upsample_temporal). */
 int ptx_present_source(ptx_handle *h, int which);

@@ -34,6 +34,7 @@ PTX_BUF_UPSAMPLE_HISTORY = 9  # {H.rgb, n} of the last ptx_upsample_temporal on 
 PTX_COUNTER_MOTION_CLIP = 6 # word of PTX_BUF_COUNTERS: pixels a band could not reproject (ptx.h)
 PTX_COUNTER_DENOISE_CLIP = 7  # word of PTX_BUF_COUNTERS: pixels with a history candidate past a band's denoiser state
 PTX_COUNTER_REPLAY = 18  # word of PTX_BUF_COUNTERS: pixels PT_4 replayed behind a shading spatial combine
+PTX_COUNTER_UPSAMPLE_CLIP = 19  # word of PTX_BUF_COUNTERS: pixels with a history candidate past a band's upsampler state
 PTX_FLAG_COUNT_WORK = 1
 PTX_FLAG_SIMPLE_KERNELS = 2
 PTX_FLAGS_RETIRED = 12  # the removed persistent-lane / tiled A/B variants: ptx_create rejects them
@@ -55,7 +56,7 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_row_census", "ptx_comm_info", "ptx_present", "ptx_present_async", "ptx_present_poll",
             "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands",
             "ptx_upsample", "ptx_upsample_bands", "ptx_phase_uniform", "ptx_upsample_temporal",
-            "ptx_trace_queries"]
+            "ptx_trace_queries", "ptx_upsample_temporal_bands"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -148,6 +149,8 @@ def load(path: str = LIB_PATH):
     lib.ptx_upsample_bands.argtypes = [ctypes.POINTER(H), ctypes.POINTER(H), ctypes.c_int, ctypes.POINTER(PtxUpsampleParams)]
     lib.ptx_phase_uniform.argtypes = [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]
     lib.ptx_upsample_temporal.argtypes = [H, H, ctypes.POINTER(PtxUpsampleTemporalParams)]
+    lib.ptx_upsample_temporal_bands.argtypes = [ctypes.POINTER(H), ctypes.POINTER(H), ctypes.c_int,
+                                                ctypes.POINTER(PtxUpsampleTemporalParams)]
     lib.ptx_present_source.argtypes = [H, ctypes.c_int]
     lib.ptx_run_passes.argtypes = [H, P, ctypes.c_int]
     lib.ptx_halo_rows.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),

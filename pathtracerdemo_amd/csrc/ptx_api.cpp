@@ -1520,7 +1520,11 @@ static bool buffer_view(ptx_handle *h, int which, DevBuf &v) {
         v.p = h->d_dn_hist[h->dn_set].p ? (char *)h->d_dn_hist[h->dn_set].p + (size_t)h->dn_cap_top * h->cfg.width * 16u : nullptr;
         v.bytes = px * 16u;
         return v.p != nullptr;
-    case PTX_BUF_UPSAMPLE_HISTORY: v.p = h->d_ut_hist[h->ut_set].p; v.bytes = px * 16u; return v.p != nullptr;
+    // (the temporal upsampler's sets of a band carry ut_cap_top halo rows above the band's)
+    case PTX_BUF_UPSAMPLE_HISTORY:
+        v.p = h->d_ut_hist[h->ut_set].p ? (char *)h->d_ut_hist[h->ut_set].p + (size_t)ut_cap_top(h) * h->cfg.width * 16u : nullptr;
+        v.bytes = px * 16u;
+        return v.p != nullptr;
     default: return false;
     }
 }
@@ -1809,6 +1813,105 @@ int upsample_alloc(ptx_handle *hi, uint32_t halo_rows, uint32_t w) {
     if (halo_rows)  // the neighbours' rows of the small image: 2 above, 2 below
         if (int rc = alloc_buf(hi, hi->d_up_halo, (size_t)4u * w * 16u)) return rc;
     return PTX_OK;
+}
+
+// ---------------------------------------------------------------- temporal upsampler (ptx_upsample_temporal, ptx_upsample_temporal_bands)
+int upsample_temporal_params(ptx_handle *err, const ptx_upsample_temporal_params *p, UtCall &c, const char *what, bool bands) {
+    c = UtCall{};
+    if (!p) return PTX_OK;
+    for (int k = bands ? 1 : 0; k < 3; ++k)
+        if (p->reserved[k]) return fail(err, PTX_E_INVALID, "%s: a reserved word is not zero", what);
+    if (!std::isfinite(p->sigma_plane) || p->sigma_plane < 0.0f)
+        return fail(err, PTX_E_INVALID, "%s: sigma_plane %g (finite, >= 0)", what, p->sigma_plane);
+    if (p->sigma_plane != 0.0f) c.sigma_plane = p->sigma_plane;
+    if (!std::isfinite(p->alpha_min) || p->alpha_min < 0.0f || p->alpha_min > 1.0f)
+        return fail(err, PTX_E_INVALID, "%s: alpha_min %g (0 = default, else finite and in (0, 1])", what, p->alpha_min);
+    if (p->alpha_min != 0.0f) c.alpha_min = p->alpha_min;
+    if (!std::isfinite(p->alpha_fill) || p->alpha_fill > 1.0f)
+        return fail(err, PTX_E_INVALID, "%s: alpha_fill %g (negative = default, else finite and in [0, 1])", what, p->alpha_fill);
+    if (p->alpha_fill >= 0.0f) c.alpha_fill = p->alpha_fill + 0.0f;  // (a -0 counts as 0)
+    c.px = p->px;
+    c.py = p->py;
+    if (bands) {
+        if (p->reserved[0] > kUtRowsMax)
+            return fail(err, PTX_E_INVALID, "%s: history_rows %u (0 = %u, else 1..%u)", what, p->reserved[0], kUtRowsDefault, kUtRowsMax);
+        if (p->reserved[0]) c.rows = p->reserved[0];
+    }
+    return PTX_OK;
+}
+
+int upsample_temporal_camera(ptx_handle *err, ptx_handle *hi, ptx_handle *lo, uint32_t s, const UtCall &c, const char *what) {
+    if (c.px >= s || c.py >= s) return fail(err, PTX_E_INVALID, "%s: phase (%u, %u) of a %u x %u block", what, c.px, c.py, s, s);
+    uint32_t want[PTX_UNIFORM_WORDS];
+    if (ptx_phase_uniform(hi->uniform, s, c.px, c.py, want) != PTX_OK)
+        return fail(err, PTX_E_INVALID, "%s: no phase uniform of the full-size handle's frame", what);
+    if (std::memcmp(want + 4, lo->uniform + 4, 19 * sizeof(uint32_t)) != 0)
+        return fail(err, PTX_E_INVALID, "%s: the small handle's camera (uniform words 4..22) is not ptx_phase_uniform's of the "
+                                        "full-size handle's for phase (%u, %u)", what, c.px, c.py);
+    return PTX_OK;
+}
+
+int upsample_temporal_alloc(ptx_handle *err, ptx_handle *hi, uint32_t halo_rows, uint32_t w) {
+    if (!hi->d_dn_guide.p) {  // (the layout a band's first ptx_denoise_bands would give the output: denoise_alloc)
+        hi->dn_cap_top = std::min(dn_reach(6u), hi->cfg.row_begin);
+        hi->dn_cap_bot = std::min(dn_reach(6u), hi->cfg.height - hi->cfg.row_end);
+    }
+    const size_t W = hi->cfg.width;
+    const size_t opx = (size_t)(hi->dn_cap_top + hi->band_h + hi->dn_cap_bot) * W;
+    const size_t spx = (size_t)(ut_cap_top(hi) + hi->band_h + ut_cap_bot(hi)) * W;
+    int rc = alloc_buf(hi, hi->d_denoised, opx * 16u);
+    for (int k = 0; k < 2 && !rc; ++k) {
+        rc = alloc_buf(hi, hi->d_ut_guide[k], spx * 32u);
+        if (!rc) rc = alloc_buf(hi, hi->d_ut_hist[k], spx * 16u);
+    }
+    if (!rc && halo_rows) rc = alloc_buf(hi, hi->d_up_halo, (size_t)4u * w * 16u);  // the neighbours' small rows: 2 above, 2 below
+    if (rc && err != hi) fail(err, rc, "%s", hi->err.c_str());  // (alloc_buf's message, where the call's refusals go)
+    return rc;
+}
+
+hipError_t upsample_temporal_launch(ptx_handle *hi, ptx_handle *lo, uint32_t s, const UtCall &c, uint32_t top, uint32_t bot,
+                                    uint32_t ht, uint32_t hb) {
+    const uint32_t W = hi->cfg.width, H = hi->cfg.height, w = lo->cfg.width;
+    const bool band = top || bot || hi->band_h != H;  // (a whole image without halo rows: ptx_upsample_temporal's launch)
+    const hipStream_t st = hi->cur().stream;
+    const int rd = hi->ut_set, wr = hi->ut_set ^ 1;
+    const uint32_t mode = !hi->ut_valid ? 0u : std::memcmp(hi->ut_camera, hi->uniform + 4, sizeof hi->ut_camera) == 0 ? 1u : 2u;
+    hi->ut_valid = false;  // (until both launches are enqueued)
+    const Scene sc = make_scene(hi);
+    // the state's sets start ut_cap_top rows above the band, the output dn_cap_top rows; lo's window `top` rows above its band
+    const size_t own = (size_t)ut_cap_top(hi) * W, cov = (size_t)(ut_cap_top(hi) - ht) * W;
+    float4 *guide = (float4 *)hi->d_ut_guide[wr].p + 2u * own;
+    float4 *hist = (float4 *)hi->d_ut_hist[wr].p + own;
+    float4 *out = (float4 *)hi->d_denoised.p + (size_t)hi->dn_cap_top * W;
+    const float4 *lguide = (const float4 *)(lo->dn_guide_swapped ? lo->d_dn_guide_prev.p : lo->d_dn_guide.p) +
+                           2u * (size_t)(lo->dn_cap_top - top) * w;
+    const float4 *lcolor = (const float4 *)lo->d_denoised.p + (size_t)lo->dn_cap_top * w;
+    const float4 *pguide = (const float4 *)hi->d_ut_guide[rd].p, *phist = (const float4 *)hi->d_ut_hist[rd].p;
+    hipError_t e = denoise_timed(hi, st, hipSuccess, [&] { return launch_denoise_guide(sc, gbuf_band(hi), guide, c.sigma_plane, st); });
+    e = denoise_timed(hi, st, e, [&] {
+        if (!band)
+            return launch_denoise_upsample_temporal(s, W, H, c.px, c.py, c.alpha_min, c.alpha_fill, mode, hi->ut_vp, guide, lguide,
+                                                    lcolor, pguide, phist, hist, out, st);
+        UtWin win;
+        win.up = UpWin{lo->cfg.row_begin - top, top + lo->band_h + bot, top, top + lo->band_h, hi->cfg.row_begin, hi->cfg.row_end};
+        win.hy0 = hi->cfg.row_begin - ht;
+        win.hrows = ht + hi->band_h + hb;
+        win.clip = (unsigned long long *)hi->d_counters.p + CNT_UPSAMPLE_CLIP;
+        return launch_denoise_upsample_temporal_win(s, W, H, c.px, c.py, c.alpha_min, c.alpha_fill, mode, hi->ut_vp, win, guide, lguide,
+                                                    lcolor, (const float4 *)hi->d_up_halo.p, pguide + 2u * cov, phist + cov, hist,
+                                                    out, st);
+    });
+    if (e == hipSuccess) {  // this call is the next one's previous call
+        hi->ut_set = wr;
+        std::memcpy(hi->ut_camera, hi->uniform + 4, sizeof hi->ut_camera);
+        float vpinv[16];
+        std::memcpy(vpinv, hi->ut_camera, sizeof vpinv);
+        mat4_inverse(vpinv, hi->ut_vp);
+        hi->ut_valid = true;
+        hi->dn_guide_stale = true;  // (PTX_BUF_DENOISED's guide records are in the state, not in d_dn_guide)
+        hi->dn_stream = st;
+    }
+    return e;
 }
 
 }  // namespace ptx
@@ -2412,23 +2515,8 @@ int ptx_upsample_temporal(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_tem
     const char *what = "ptx_upsample_temporal";
     // ---- refusals, all before any GPU work
     if (hi == lo) return fail(hi, PTX_E_INVALID, "%s: one handle on both sides", what);
-    float sigma_plane = 0.02f, alpha_min = 0.02f, alpha_fill = 0.05f;
-    uint32_t px = 0u, py = 0u;
-    if (p) {
-        for (uint32_t r : p->reserved)
-            if (r) return fail(hi, PTX_E_INVALID, "%s: a reserved word is not zero", what);
-        if (!std::isfinite(p->sigma_plane) || p->sigma_plane < 0.0f)
-            return fail(hi, PTX_E_INVALID, "%s: sigma_plane %g (finite, >= 0)", what, p->sigma_plane);
-        if (p->sigma_plane != 0.0f) sigma_plane = p->sigma_plane;
-        if (!std::isfinite(p->alpha_min) || p->alpha_min < 0.0f || p->alpha_min > 1.0f)
-            return fail(hi, PTX_E_INVALID, "%s: alpha_min %g (0 = default, else finite and in (0, 1])", what, p->alpha_min);
-        if (p->alpha_min != 0.0f) alpha_min = p->alpha_min;
-        if (!std::isfinite(p->alpha_fill) || p->alpha_fill > 1.0f)
-            return fail(hi, PTX_E_INVALID, "%s: alpha_fill %g (negative = default, else finite and in [0, 1])", what, p->alpha_fill);
-        if (p->alpha_fill >= 0.0f) alpha_fill = p->alpha_fill + 0.0f;  // (a -0 counts as 0)
-        px = p->px;
-        py = p->py;
-    }
+    UtCall c;
+    if (int rc = upsample_temporal_params(hi, p, c, what, false)) return rc;
     for (ptx_handle *h : {hi, lo})
         if (h->cfg.row_begin != 0 || h->band_h != h->cfg.height)
             return fail(hi, PTX_E_INVALID, "%s: the %s handle is a band (rows %u..%u): bands are not supported by this call", what,
@@ -2436,52 +2524,16 @@ int ptx_upsample_temporal(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_tem
     // what a pair must share, but for the camera: lo's is hi's seen through the phase
     uint32_t s = 0;
     if (int rc = upsample_pair_check(hi, hi, lo, s, what, false)) return rc;
-    const uint32_t W = hi->cfg.width, H = hi->cfg.height, w = lo->cfg.width;
-    if (px >= s || py >= s) return fail(hi, PTX_E_INVALID, "%s: phase (%u, %u) of a %u x %u block", what, px, py, s, s);
-    uint32_t want[PTX_UNIFORM_WORDS];
-    if (ptx_phase_uniform(hi->uniform, s, px, py, want) != PTX_OK)
-        return fail(hi, PTX_E_INVALID, "%s: no phase uniform of the full-size handle's frame", what);
-    if (std::memcmp(want + 4, lo->uniform + 4, 19 * sizeof(uint32_t)) != 0)
-        return fail(hi, PTX_E_INVALID, "%s: the small handle's camera (uniform words 4..22) is not ptx_phase_uniform's of the "
-                                       "full-size handle's for phase (%u, %u)", what, px, py);
+    if (int rc = upsample_temporal_camera(hi, hi, lo, s, c, what)) return rc;
     // ---- buffers (first call): the output and two sets of {guide records, history}
     HIP_CHECK(hi, hipSetDevice(hi->device));
-    const size_t npx = (size_t)W * H;
-    if (int rc = alloc_buf(hi, hi->d_denoised, npx * 16u)) return rc;
-    for (int k = 0; k < 2; ++k) {
-        if (int rc = alloc_buf(hi, hi->d_ut_guide[k], npx * 32u)) return rc;
-        if (int rc = alloc_buf(hi, hi->d_ut_hist[k], npx * 16u)) return rc;
-    }
+    if (int rc = upsample_temporal_alloc(hi, hi, 0u, lo->cfg.width)) return rc;
     // ---- behind the small handle's denoise, the two launches, and the small handle's streams behind
     // them.  On the current frame's stream, where ptx_denoise enqueues: the state a call on another
     // frame context's stream left is read after a frame that waited for ev_prev, recorded behind that call.
     if (int rc = upsample_source(hi, lo)) return rc;
-    const hipStream_t st = hi->cur().stream;
-    HIP_CHECK(hi, hipStreamWaitEvent(st, lo->ev_up_src, 0));
-    const int rd = hi->ut_set, wr = hi->ut_set ^ 1;
-    const uint32_t mode = !hi->ut_valid ? 0u : std::memcmp(hi->ut_camera, hi->uniform + 4, sizeof hi->ut_camera) == 0 ? 1u : 2u;
-    hi->ut_valid = false;  // (until both launches are enqueued)
-    const Scene sc = make_scene(hi);
-    float4 *guide = (float4 *)hi->d_ut_guide[wr].p;
-    const float4 *lguide = (const float4 *)(lo->dn_guide_swapped ? lo->d_dn_guide_prev.p : lo->d_dn_guide.p) +
-                           2u * (size_t)lo->dn_cap_top * w;
-    const float4 *lcolor = (const float4 *)lo->d_denoised.p + (size_t)lo->dn_cap_top * w;
-    hipError_t e = denoise_timed(hi, st, hipSuccess, [&] { return launch_denoise_guide(sc, gbuf_band(hi), guide, sigma_plane, st); });
-    e = denoise_timed(hi, st, e, [&] {
-        return launch_denoise_upsample_temporal(s, W, H, px, py, alpha_min, alpha_fill, mode, hi->ut_vp, guide, lguide, lcolor,
-                                                (const float4 *)hi->d_ut_guide[rd].p, (const float4 *)hi->d_ut_hist[rd].p,
-                                                (float4 *)hi->d_ut_hist[wr].p, (float4 *)hi->d_denoised.p, st);
-    });
-    if (e == hipSuccess) {  // this call is the next one's previous call
-        hi->ut_set = wr;
-        std::memcpy(hi->ut_camera, hi->uniform + 4, sizeof hi->ut_camera);
-        float vpinv[16];
-        std::memcpy(vpinv, hi->ut_camera, sizeof vpinv);
-        mat4_inverse(vpinv, hi->ut_vp);
-        hi->ut_valid = true;
-        hi->dn_guide_stale = true;  // (PTX_BUF_DENOISED's guide records are in the state, not in d_dn_guide)
-        hi->dn_stream = st;
-    }
+    HIP_CHECK(hi, hipStreamWaitEvent(hi->cur().stream, lo->ev_up_src, 0));
+    const hipError_t e = upsample_temporal_launch(hi, lo, s, c, 0u, 0u, 0u, 0u);
     if (int rc = upsample_done(hi, hi)) return rc;
     if (int rc = upsample_release(hi, lo, hi)) return rc;
     if (e != hipSuccess) return fail(hi, PTX_E_HIP, "%s launch: %s", what, hipGetErrorString(e));
@@ -2643,6 +2695,8 @@ int ptx_destroy(ptx_handle *h) {
     if (h->ev_dn_copied) (void)hipEventDestroy(h->ev_dn_copied);
     if (h->ev_up_src) (void)hipEventDestroy(h->ev_up_src);
     if (h->ev_up_done) (void)hipEventDestroy(h->ev_up_done);
+    if (h->ev_ut_ready) (void)hipEventDestroy(h->ev_ut_ready);
+    if (h->ev_ut_copied) (void)hipEventDestroy(h->ev_ut_copied);
     delete h;
     return PTX_OK;
 }

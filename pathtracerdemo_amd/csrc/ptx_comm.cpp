@@ -17,7 +17,8 @@
 //   * motion_halo: history rows, before a moved camera's temporal pass;
 //   * dn_halo (ptx_denoise_bands): texels, colour or temporal state, moments --
 //     the rows the filter reaches;
-//   * up_halo (ptx_upsample_bands): 2 rows of the neighbours' small denoised image.
+//   * up_halo (ptx_upsample_bands): 2 rows of the neighbours' small denoised image;
+//     ptx_upsample_temporal_bands adds the neighbours' history_rows rows of the previous state.
 // It moves them one of two ways:
 //   * over communicators -- across processes (one rank per GPU: a lone band of the call) or
 //     inside one (ptx_*_bands on handles that own them): grouped ncclSend / ncclRecv straight
@@ -31,7 +32,8 @@
 //   motion halo   ev_prev (its previous frame complete)        the neighbours' ev_mhalo (before its spatial pass)
 //   denoiser      ev_dn_ready (its frame; its dn_temporal)     the neighbours' ev_dn_copied (end of the call)
 //   upsampler     ev_up_src (the small band's last denoise)    the neighbours' pairs' ev_up_done (upsample_release)
-// The left column is Halo::ready, waited for inside the exchange; ev_mhalo and ev_dn_copied are
+//   its state     ev_ut_ready (behind ev_up_src on hi's stream) the neighbours' ev_ut_copied (before the call's kernels)
+// The left column is Halo::ready, waited for inside the exchange; ev_mhalo, ev_dn_copied and ev_ut_copied are
 // recorded by it behind a band's copies (Halo::copied); the waits of the right column stay with
 // the callers, as do ev_halo (halo_landed: after the halo rows' summaries) and ev_up_done.
 // PTX_FLAG_HALO_OVERLAP splits the spatial pass into the rows whose neighbourhood lies inside
@@ -571,16 +573,16 @@ Halo up_halo(ptx_handle *hi, ptx_handle *lo, ptx_handle *err, uint32_t top, uint
     return x;
 }
 
-// ---- What ptx_render_bands, ptx_denoise_bands and ptx_upsample_bands refuse alike, before any GPU
-// work: the bands hs[0..n) whose rows and communicators carry the exchange (ptx_upsample_bands: the
-// small bands).  err receives every message (null: the band at fault does).  The entry points call
+// ---- What ptx_render_bands, ptx_denoise_bands, ptx_upsample_bands and ptx_upsample_temporal_bands
+// refuse alike, before any GPU work: the bands hs[0..n) whose rows and communicators carry the
+// exchange (the upsampling calls: the small bands).  err receives every message (null: the band at fault does).  The entry points call
 // the checks in the order their refusals have always had, their own checks in between.
 struct BandSet {
     const char *what;  // the entry point's name
     ptx_handle *const *hs;
     int n;
     ptx_handle *err;
-    bool pairs;      // ptx_upsample_bands' wording: "pair", "small band"
+    bool pairs;      // the upsampling calls' wording: "pair", "small band"
     bool rank_form;  // one band of a frame whose other bands are other ranks' (every rank makes the call)
     ptx_handle *to(int i) const { return err ? err : hs[i]; }
     const char *band() const { return pairs ? "small band" : "band"; }
@@ -1051,6 +1053,151 @@ int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n, cons
     for (int i = 0; i < n; ++i) {
         HIP_CHECK(h0, hipSetDevice(hi[i]->device));
         if (e == hipSuccess) e = upsample_launch(hi[i], lo[i], s, sigma_plane, top[i], bot[i]);
+        if (int rc = upsample_done(h0, hi[i])) return rc;
+    }
+    // ---- a small band's next work waits until its own pair has read it and -- peer copies -- its
+    // neighbours' pairs have copied its rows (a send is complete behind the sending pair's kernels)
+    for (int i = 0; i < n; ++i) {
+        HIP_CHECK(h0, hipSetDevice(lo[i]->device));
+        if (int rc = upsample_release(h0, lo[i], hi[i])) return rc;
+        if (!nccl) {
+            if (i > 0)
+                if (int rc = upsample_release(h0, lo[i], hi[i - 1])) return rc;
+            if (i + 1 < n)
+                if (int rc = upsample_release(h0, lo[i], hi[i + 1])) return rc;
+        }
+    }
+    if (e != hipSuccess) return fail(h0, PTX_E_HIP, "%s launch: %s", what, hipGetErrorString(e));
+    return PTX_OK;
+}
+
+// ptx_upsample_temporal_bands: ptx_upsample_bands' pairs and small halo, and the halo of the state:
+// the T rows next to band i of the set its neighbours read, their own rows of their previous call
+// (Temporal upsampling, bands).  One exchange of three messages per side, before the
+// kernels; a band without a state sends rows whose n is below 0.
+int ptx_upsample_temporal_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n, const ptx_upsample_temporal_params *p) {
+    const char *what = "ptx_upsample_temporal_bands";
+    if (!hi || !hi[0]) return PTX_E_INVALID;
+    ptx_handle *h0 = hi[0];
+    // ---- refusals, all before any GPU work, all in hi[0]'s message
+    if (!lo || n < 1 || n > 64) return fail(h0, PTX_E_INVALID, "%s: a null array, or %d pairs (1..64)", what, n);
+    for (int i = 0; i < n; ++i)
+        if (!hi[i] || !lo[i]) return fail(h0, PTX_E_INVALID, "%s: pair %d has a null handle", what, i);
+    for (int i = 0; i < 2 * n; ++i)
+        for (int k = 0; k < i; ++k)
+            if ((i < n ? hi[i] : lo[i - n]) == (k < n ? hi[k] : lo[k - n]))
+                return fail(h0, PTX_E_INVALID, "%s: one handle appears twice", what);
+    ptx_handle *l0 = lo[0];
+    const bool nccl = l0->comm != nullptr, rank_form = is_rank_form(lo, n);
+    const auto whole = [](const ptx_handle *h) { return h->cfg.row_begin == 0 && h->band_h == h->cfg.height; };
+    UtCall c;
+    if (int rc = upsample_temporal_params(h0, p, c, what, true)) return rc;
+    if (n == 1 && !rank_form && whole(h0) && whole(l0)) {
+        if (!p) return ptx_upsample_temporal(h0, l0, nullptr);
+        ptx_upsample_temporal_params q = *p;
+        q.reserved[0] = 0u;
+        return ptx_upsample_temporal(h0, l0, &q);
+    }
+    // the frame's geometry first: one size and pipeline per side, one scale, rows that match and continue
+    const uint32_t h = l0->cfg.height, s = h0->cfg.width / l0->cfg.width, T = c.rows;
+    if (s < 2u || s > 4u || h0->cfg.width != s * l0->cfg.width || h0->cfg.height != s * h)
+        return fail(h0, PTX_E_INVALID, "%s: %ux%u is not 2, 3 or 4 times %ux%u", what, h0->cfg.width, h0->cfg.height,
+                    l0->cfg.width, h);
+    const uint32_t H = h0->cfg.height, W = h0->cfg.width;
+    const BandSet set{what, lo, n, h0, true, rank_form};
+    const auto few = [&](ptx_handle *to, int band, uint32_t rows) {
+        return fail(to, PTX_E_INVALID, "%s: small band %d has %u rows; every band sends %u", what, band, rows, kUpHalo);
+    };
+    // (the small bands' rows carry the check: a full-size band has s times as many)
+    const auto few_state = [&](ptx_handle *to, int band, uint32_t rows) {
+        return fail(to, PTX_E_INVALID, "%s: full-size band %d has %u rows; history_rows %u needs %u rows of every band", what, band,
+                    s * rows, T, T);
+    };
+    for (int i = 0; i < n; ++i) {
+        ptx_handle *a = hi[i], *b = lo[i];
+        if (a->cfg.width != h0->cfg.width || a->cfg.height != h0->cfg.height || a->cfg.pipeline != h0->cfg.pipeline)
+            return fail(h0, PTX_E_INVALID, "%s: pair %d differs in size or pipeline", what, i);
+        if (int rc = band_joins(set, i)) return rc;  // (the small bands: the same words for a pair's size)
+        if (a->cfg.row_begin != s * b->cfg.row_begin || a->cfg.row_end != s * b->cfg.row_end)
+            return fail(h0, PTX_E_INVALID, "%s: pair %d: the full-size band has rows %u..%u, %u times the small band's %u..%u are %u..%u",
+                        what, i, a->cfg.row_begin, a->cfg.row_end, s, b->cfg.row_begin, b->cfg.row_end, s * b->cfg.row_begin,
+                        s * b->cfg.row_end);
+    }
+    if (int rc = bands_cover(set)) return rc;
+    if (int rc = rank_rows(set, kUpHalo, few)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = band_rows(set, i, kUpHalo, few)) return rc;
+    const uint32_t need = (T + s - 1u) / s;  // s * rows >= T
+    if (int rc = rank_rows(set, need, few_state)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = band_rows(set, i, need, few_state)) return rc;
+    // then what every pair must share, the phase and the camera rule, and a band's halo rows: kUpHalo
+    // small rows and T rows of the state from either side, where the frame has them
+    std::vector<uint32_t> top(n), bot(n), ht(n), hb(n);
+    for (int i = 0; i < n; ++i) {
+        ptx_handle *a = hi[i], *b = lo[i];
+        uint32_t si = 0;
+        if (int rc = upsample_pair_check(h0, a, b, si, what, false)) return rc;
+        if (int rc = upsample_temporal_camera(h0, a, b, s, c, what)) return rc;
+        top[i] = b->cfg.row_begin ? kUpHalo : 0u;
+        bot[i] = b->cfg.row_end != h ? kUpHalo : 0u;
+        ht[i] = std::min(T, a->cfg.row_begin);
+        hb[i] = std::min(T, H - a->cfg.row_end);
+        if (b->dn_guide_top < top[i] || b->dn_guide_bot < bot[i])
+            return fail(h0, PTX_E_INVALID, "%s: small band %d has no denoised image with its neighbours' guide records "
+                                           "(ptx_denoise_bands first)", what, rank_form ? b->rank : i);
+    }
+    if (nccl)
+        for (int i = 0; i < n; ++i)
+            if (int rc = comm_health(lo[i])) return rc;
+    // ---- every pair: hi's buffers (first call); its stream behind the tail of lo's last denoise; a band
+    // without a state marks the rows it sends (n below 0: every tap of them fails its first test)
+    for (int i = 0; i < n; ++i) {
+        HIP_CHECK(h0, hipSetDevice(hi[i]->device));
+        if (int rc = upsample_temporal_alloc(h0, hi[i], top[i] + bot[i], l0->cfg.width)) return rc;
+        if (int rc = upsample_source(h0, lo[i])) return rc;
+    }
+    std::vector<Halo> x(n);
+    for (int i = 0; i < n; ++i) {
+        ptx_handle *a = hi[i], *b = lo[i];
+        const hipStream_t st = a->cur().stream;
+        HIP_CHECK(h0, hipSetDevice(a->device));
+        HIP_CHECK(h0, hipStreamWaitEvent(st, b->ev_up_src, 0));
+        const size_t own = ut_cap_top(a), end = own + a->band_h;
+        char *sg = (char *)a->d_ut_guide[a->ut_set].p, *sh = (char *)a->d_ut_hist[a->ut_set].p;
+        if (!a->ut_valid) {
+            if (ht[i]) HIP_CHECK(h0, hipMemsetAsync(sh + own * W * 16u, 0xFF, (size_t)T * W * 16u, st));
+            if (hb[i]) HIP_CHECK(h0, hipMemsetAsync(sh + (end - T) * W * 16u, 0xFF, (size_t)T * W * 16u, st));
+        }
+        // lo's rows (complete behind ev_up_src) and the state's rows are both ready at this point of hi's stream
+        if (!nccl) {
+            if (!a->ev_ut_ready) HIP_CHECK(h0, hipEventCreateWithFlags(&a->ev_ut_ready, hipEventDisableTiming));
+            if (!a->ev_ut_copied) HIP_CHECK(h0, hipEventCreateWithFlags(&a->ev_ut_copied, hipEventDisableTiming));
+            HIP_CHECK(h0, hipEventRecord(a->ev_ut_ready, st));
+        }
+        x[i] = up_halo(a, b, h0, top[i], bot[i]);
+        if (!nccl) {
+            x[i].ready = a->ev_ut_ready;
+            x[i].copied = a->ev_ut_copied;
+        }
+        // the first / last T own rows of the set this call reads go out; the halo rows of that set come in
+        x[i].add(0, sg, own, sg, own - ht[i], ht[i], (size_t)W * 32u);
+        x[i].add(0, sh, own, sh, own - ht[i], ht[i], (size_t)W * 16u);
+        x[i].add(1, sg, end - hb[i], sg, end, hb[i], (size_t)W * 32u);
+        x[i].add(1, sh, end - hb[i], sh, end, hb[i], (size_t)W * 16u);
+    }
+    // ---- the exchange, on hi's streams
+    if (int rc = exchange_halos(x.data(), n, "temporal upsampler halo")) return rc;
+    // ---- every pair: with peer copies the kernel writes the set its neighbours copied from in the
+    // previous call: behind their copies (this call's follow those on their streams); the two launches
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n; ++i) {
+        HIP_CHECK(h0, hipSetDevice(hi[i]->device));
+        if (!nccl) {
+            if (i > 0) HIP_CHECK(h0, hipStreamWaitEvent(hi[i]->cur().stream, hi[i - 1]->ev_ut_copied, 0));
+            if (i + 1 < n) HIP_CHECK(h0, hipStreamWaitEvent(hi[i]->cur().stream, hi[i + 1]->ev_ut_copied, 0));
+        }
+        if (e == hipSuccess) e = upsample_temporal_launch(hi[i], lo[i], s, c, top[i], bot[i], ht[i], hb[i]);
         if (int rc = upsample_done(h0, hi[i])) return rc;
     }
     // ---- a small band's next work waits until its own pair has read it and -- peer copies -- its

@@ -2,8 +2,8 @@
 // DESIGN.md §Denoiser): guided by the primary hit of the frame context's G-buffer, variance
 // estimated spatially from the image; in temporal mode the image is the frame colours integrated
 // over the calls, looked up through the previous call's camera (tests/denoise_temporal_ref.py).
-// All kernels one lane per pixel; the one atomic is dn_temporal's count of clipped pixels, one add
-// per wave that has any:
+// All kernels one lane per pixel; the only atomics are dn_temporal's and dn_upsample_temporal_win's
+// counts of clipped pixels, one add per wave that has any:
 //   dn_guide     G-buffer texel -> 32-byte guide record {P.xyz, key | kDnMiss}{N.xyz, r}
 //   dn_temporal  (temporal mode) history lookup + integration -> history {C.rgb, n}, moments {m1, m2}
 //   dn_variance  7x7 guide-weighted luminance moments -> working image {r, g, b, v}; <true>: on the
@@ -16,6 +16,8 @@
 //   dn_upsample_temporal  (ptx_upsample_temporal) the same inputs, the small image rendered through one
 //                phase of the S x S block: the own sample and the interpolated estimate integrated with
 //                the previous call's history {H.rgb, n}, gathered like dn_temporal's
+//                dn_upsample_temporal_win (ptx_upsample_temporal_bands): a band of it from a window of the small
+//                image and the rows of the previous state the band holds
 // Every kernel but dn_guide addresses a row window (DnWin): a W x rows image that is the whole
 // frame, or a band with the halo rows ptx_denoise_bands brought from its neighbours, filtered as if
 // it were the whole image; a launch computes rows [c0, c1) of it.
@@ -535,32 +537,53 @@ struct UpHistory {
 };
 __device__ __forceinline__ int up_floor_div(int a, int s) { return a >= 0 ? a / s : -((-a + s - 1) / s); }
 
-template <int S>
-__global__ __launch_bounds__(kBlock) void dn_upsample_temporal(uint32_t W, uint32_t H, uint32_t w, uint32_t h, const UpHistory Hs,
-                                                               const float4 *__restrict__ hg, const float4 *__restrict__ lg,
-                                                               const float4 *__restrict__ lc, const float4 *__restrict__ pguide,
-                                                               const float4 *__restrict__ phist, float4 *__restrict__ hist,
-                                                               float4 *__restrict__ out) {
+// WIN (ptx_upsample_temporal_bands): rows [win.up.Y0, win.up.Y1) of the frame -- hg, hist and out start
+// at row Y0 -- from a row window of the small frame (UpWin, as dn_upsample_tile<S, true>) and the rows
+// [win.hy0, win.hy0 + win.hrows) of the previous state, where pguide and phist start.  Every position
+// is the frame's: fx, x0, ax, fy, y0, ay, the grid test (y - py) mod S, stage 3's clamp against h, the
+// reprojection's H; the offsets enter addresses only.
+//   The small rows: for full-size row y, y0 = floor((y - py) / S).  A band of small rows [b0, b1) has
+// y in [S b0, S b1): the smallest y0 is floor((S b0 - py) / S) = b0 - 1 for py > 0 (b0 for py = 0), the
+// largest floor((S b1 - 1 - py) / S) = b1 - 1 since 0 <= S - 1 - py < S.  Stage 2 reaches y0 - 1 .. y0 + 2,
+// stage 3 y0 or y0 + 1: rows b0 - 2 .. b1 + 1, two of either neighbour for every phase.  A pixel on the
+// phase's grid has (y - py) a multiple of S that is >= S b0 - (S - 1), so >= S b0: its own sample's row
+// (y - py) / S is one of b0 .. b1 - 1, the band's own.  A row of the frame outside the window is staged
+// like a row outside the frame; no pixel of the band has a candidate there.
+//   The history: a tap inside the frame whose row is not one of the state's hrows rows is not taken (as
+// if its n' were below 0), dn_temporal's test with its unsigned row wrap, and a pixel with such a tap
+// counts in *win.clip: one ballot and one add of its popcount per wave.  Only mode 2 with a primary
+// hit and cw > 0 has taps off the pixel itself, so nothing else clips.
+// Without WIN the code is the whole image's, `win` and `lhalo` unread.
+template <int S, bool WIN>
+__device__ __forceinline__ void dn_upsample_temporal_tile(uint32_t W, uint32_t H, uint32_t w, uint32_t h, const UpHistory &Hs,
+                                                          const UtWin &win, const float4 *__restrict__ hg,
+                                                          const float4 *__restrict__ lg, const float4 *__restrict__ lc,
+                                                          const float4 *__restrict__ lhalo, const float4 *__restrict__ pguide,
+                                                          const float4 *__restrict__ phist, float4 *__restrict__ hist,
+                                                          float4 *__restrict__ out, float4 *g0, float4 *g1, float4 *cv) {
     static_assert(S >= 2 && S <= 4, "scales 2, 3, 4");
     constexpr int kN = (kDnTile + S - 2) / S + 4;
     static_assert(kN * kN <= kBlock, "one lane per staged entry");
-    __shared__ float4 g0[kN * kN], g1[kN * kN], cv[kN * kN];
     const int tx = (int)(threadIdx.x & 15u), ty = (int)(threadIdx.x >> 4);
-    const uint32_t bx = blockIdx.x * kDnTile, by = blockIdx.y * kDnTile;
+    // the tile's first pixel in the frame
+    const uint32_t Y0 = WIN ? win.up.Y0 : 0u, Y1 = WIN ? win.up.Y1 : H;
+    const uint32_t bx = blockIdx.x * kDnTile, by = Y0 + blockIdx.y * kDnTile;
     const uint32_t x = bx + (uint32_t)tx, y = by + (uint32_t)ty;
-    const bool live = x < W && y < H;
-    const size_t pix = live ? (size_t)y * W + x : 0u;  // (a lane outside the image loads pixel 0, unused)
+    const bool live = x < W && y < Y1;
+    const size_t pix = live ? (size_t)(y - Y0) * W + x : 0u;  // (a lane outside the image loads pixel 0, unused)
+    // this pixel in the previous state (a band's own rows are always covered)
+    const size_t pc = WIN ? (size_t)((live ? y : Y0) - win.hy0) * W + (live ? x : 0u) : pix;
     const float4 a = hg[2u * pix], b = hg[2u * pix + 1u];
     const uint32_t key = asu(a.w);
     const f3 Pp = rgb(a), Np = rgb(b);
     // ---- the history's taps k = 2 j + i (j outer), all loads issued ahead of the staging and the tests
     size_t q[4];
     float wq[4];
-    bool in[4];
+    bool in[4], clipped = false;
     float4 qa[4], qb[4], qh[4];
     if (Hs.mode == 1u) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { q[k] = pix; wq[k] = 1.0f; in[k] = k == 0; }
+        for (int k = 0; k < 4; ++k) { q[k] = pc; wq[k] = 1.0f; in[k] = k == 0; }
     } else if (Hs.mode == 2u) {
         const float *vp = Hs.vp;
         const float cx = ((vp[0] * Pp.x + vp[4] * Pp.y) + vp[8] * Pp.z) + vp[12];
@@ -575,7 +598,14 @@ __global__ __launch_bounds__(kBlock) void dn_upsample_temporal(uint32_t W, uint3
             const float qx = hx0 + (float)i, qy = hy0 + (float)j;
             // (a NaN or infinite projection compares false: outside)
             in[k] = key != kDnMiss && cw > 0.0f && qx >= 0.0f && qx < (float)W && qy >= 0.0f && qy < (float)H;
-            q[k] = in[k] ? (size_t)(int)qy * W + (size_t)(int)qx : pix;  // (an outside tap loads the centre, unused)
+            if (WIN) {
+                const uint32_t ry = (uint32_t)(in[k] ? (int)qy : (int)win.hy0) - win.hy0;  // (below hy0: wraps past hrows)
+                if (live && in[k] && ry >= win.hrows) clipped = true;
+                in[k] = in[k] && ry < win.hrows;
+                q[k] = in[k] ? (size_t)ry * W + (size_t)(int)qx : pc;
+            } else {
+                q[k] = in[k] ? (size_t)(int)qy * W + (size_t)(int)qx : pix;  // (an outside tap loads the centre, unused)
+            }
             wq[k] = (i ? bx1 : 1.0f - bx1) * (j ? by1 : 1.0f - by1);
         }
     }
@@ -587,12 +617,26 @@ __global__ __launch_bounds__(kBlock) void dn_upsample_temporal(uint32_t W, uint3
             qh[k] = phist[q[k]];
         }
     }
+    if (WIN && Hs.mode == 2u) {  // (wave-uniform: every lane of the wave votes)
+        const unsigned long long cm = __ballot(clipped);
+        if (clipped && __lane_id() == (uint32_t)__ffsll((long long)cm) - 1u) atomicAdd(win.clip, (unsigned long long)__popcll(cm));
+    }
     // ---- the tile's footprint in the small image
     const int ox = up_floor_div((int)bx - (int)Hs.px, S) - 1, oy = up_floor_div((int)by - (int)Hs.py, S) - 1;
     if (threadIdx.x < (uint32_t)(kN * kN)) {
         const int e = (int)threadIdx.x, gx = ox + e % kN, gy = oy + e / kN;
         float4 sa = make_float4(0.0f, 0.0f, 0.0f, asf(kUpOutside)), sb = make_float4(0.0f, 0.0f, 0.0f, 0.0f), sc4 = sb;
-        if (gx >= 0 && gy >= 0 && gx < (int)w && gy < (int)h) {
+        if (WIN) {
+            // lg starts at the window's row 0 (row win.up.y0 of the small frame); the window's rows [o0, o1)
+            // are lc's, the rows above and then the rows below them lhalo's
+            const int wy = gy - (int)win.up.y0;
+            if (gx >= 0 && gy >= 0 && gx < (int)w && gy < (int)h && wy >= 0 && wy < (int)win.up.rows) {
+                const size_t lq = (size_t)wy * w + (size_t)gx;
+                sa = lg[2u * lq];
+                sb = lg[2u * lq + 1u];
+                sc4 = dn_load(DnImage{lc, lhalo, win.up.o0, win.up.o1}, w, (uint32_t)gx, (uint32_t)wy);
+            }
+        } else if (gx >= 0 && gy >= 0 && gx < (int)w && gy < (int)h) {
             const size_t lq = (size_t)gy * w + (size_t)gx;
             sa = lg[2u * lq];
             sb = lg[2u * lq + 1u];
@@ -691,6 +735,29 @@ __global__ __launch_bounds__(kBlock) void dn_upsample_temporal(uint32_t W, uint3
     out[pix] = make_float4(Hn.x, Hn.y, Hn.z, 1.0f);
     hist[pix] = make_float4(Hn.x, Hn.y, Hn.z, n);
 }
+template <int S>
+__global__ __launch_bounds__(kBlock) void dn_upsample_temporal(uint32_t W, uint32_t H, uint32_t w, uint32_t h, const UpHistory Hs,
+                                                               const float4 *__restrict__ hg, const float4 *__restrict__ lg,
+                                                               const float4 *__restrict__ lc, const float4 *__restrict__ pguide,
+                                                               const float4 *__restrict__ phist, float4 *__restrict__ hist,
+                                                               float4 *__restrict__ out) {
+    constexpr int kN = (kDnTile + S - 2) / S + 4;
+    __shared__ float4 g0[kN * kN], g1[kN * kN], cv[kN * kN];
+    dn_upsample_temporal_tile<S, false>(W, H, w, h, Hs, UtWin{}, hg, lg, lc, nullptr, pguide, phist, hist, out, g0, g1, cv);
+}
+// A band of the full-size frame from a window of the small one and the covered rows of the previous state.
+template <int S>
+__global__ __launch_bounds__(kBlock) void dn_upsample_temporal_win(uint32_t W, uint32_t H, uint32_t w, uint32_t h,
+                                                                   const UpHistory Hs, const UtWin win,
+                                                                   const float4 *__restrict__ hg, const float4 *__restrict__ lg,
+                                                                   const float4 *__restrict__ lc, const float4 *__restrict__ lhalo,
+                                                                   const float4 *__restrict__ pguide,
+                                                                   const float4 *__restrict__ phist, float4 *__restrict__ hist,
+                                                                   float4 *__restrict__ out) {
+    constexpr int kN = (kDnTile + S - 2) / S + 4;
+    __shared__ float4 g0[kN * kN], g1[kN * kN], cv[kN * kN];
+    dn_upsample_temporal_tile<S, true>(W, H, w, h, Hs, win, hg, lg, lc, lhalo, pguide, phist, hist, out, g0, g1, cv);
+}
 
 // ---------------------------------------------------------------- launches
 static dim3 dn_grid(uint32_t W, const DnWin &win) {
@@ -772,6 +839,31 @@ hipError_t launch_denoise_upsample_temporal(uint32_t s, uint32_t W, uint32_t H, 
     if (s == 2u) hipLaunchKernelGGL(dn_upsample_temporal<2>, g, bl, 0, st, W, H, w, h, Hs, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
     else if (s == 3u) hipLaunchKernelGGL(dn_upsample_temporal<3>, g, bl, 0, st, W, H, w, h, Hs, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
     else if (s == 4u) hipLaunchKernelGGL(dn_upsample_temporal<4>, g, bl, 0, st, W, H, w, h, Hs, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_denoise_upsample_temporal_win(uint32_t s, uint32_t W, uint32_t H, uint32_t px, uint32_t py, float alpha_min,
+                                                float alpha_fill, uint32_t mode, const float *vp_prev, const UtWin &win,
+                                                const float4 *guide_hi, const float4 *guide_lo, const float4 *color_lo,
+                                                const float4 *halo_lo, const float4 *guide_prev, const float4 *hist_prev,
+                                                float4 *hist, float4 *out, hipStream_t st) {
+    const dim3 g((W + kDnTile - 1) / kDnTile, (win.up.Y1 - win.up.Y0 + kDnTile - 1) / kDnTile), bl(kBlock);
+    const uint32_t w = W / s, h = H / s;
+    if (px >= s || py >= s || W != s * w || H != s * h) return hipErrorInvalidValue;  // (the staged window's bound)
+    // the rows the kernel addresses: the band's own inside the covered rows, the window's own rows inside the window
+    if (win.up.Y0 >= win.up.Y1 || win.up.Y1 > H || win.hy0 > win.up.Y0 || win.hy0 + win.hrows < win.up.Y1 || !win.clip ||
+        win.up.o0 > win.up.o1 || win.up.o1 > win.up.rows)
+        return hipErrorInvalidValue;
+    UpHistory Hs{};
+    for (int i = 0; i < 16; ++i) Hs.vp[i] = vp_prev[i];
+    Hs.alpha_min = alpha_min;
+    Hs.alpha_fill = alpha_fill;
+    Hs.mode = mode;
+    Hs.px = px;
+    Hs.py = py;
+    if (s == 2u) hipLaunchKernelGGL(dn_upsample_temporal_win<2>, g, bl, 0, st, W, H, w, h, Hs, win, guide_hi, guide_lo, color_lo, halo_lo, guide_prev, hist_prev, hist, out);
+    else if (s == 3u) hipLaunchKernelGGL(dn_upsample_temporal_win<3>, g, bl, 0, st, W, H, w, h, Hs, win, guide_hi, guide_lo, color_lo, halo_lo, guide_prev, hist_prev, hist, out);
+    else if (s == 4u) hipLaunchKernelGGL(dn_upsample_temporal_win<4>, g, bl, 0, st, W, H, w, h, Hs, win, guide_hi, guide_lo, color_lo, halo_lo, guide_prev, hist_prev, hist, out);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -411,6 +411,9 @@ constexpr int CNT_DENOISE_CLIP = 7;  // PTX_COUNTER_DENOISE_CLIP: dn_temporal's 
 // the SIMD-utilisation profile's 8 .. 8 + 2 * PROF_REGIONS - 1)
 constexpr int CNT_REPLAY = 18;
 static_assert(CNT_REPLAY >= 8 + 2 * PROF_REGIONS && CNT_REPLAY < kCounterWords, "a free counter word");
+// PTX_COUNTER_UPSAMPLE_CLIP: dn_upsample_temporal_win's clipped pixels (ptx_upsample_temporal_bands)
+constexpr int CNT_UPSAMPLE_CLIP = 19;
+static_assert(CNT_UPSAMPLE_CLIP > CNT_REPLAY && CNT_UPSAMPLE_CLIP < kCounterWords, "a free counter word");
 __device__ __forceinline__ bool inst_may_hit(const Scene &sc, const Inst &I, f3 o, f3 winv, float omax, float vy) {
     if (!(I.wpad >= 0.0f)) return true;
     // p0 covers the rounding of the local origin lo.  The local direction ld = M^-1 (o + d) - M^-1 o

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 
 #include "../../include/ptx.h"
@@ -227,11 +228,18 @@ struct ptx_handle {
     // history (dropped by an upload, a reset and every other call that writes PTX_BUF_DENOISED).
     // dn_guide_stale: PTX_BUF_DENOISED is that call's output, whose guide records are not in d_dn_guide
     // (this handle is no ptx_upsample source until a denoise or ptx_upsample of its own)
+    // ptx_upsample_temporal_bands: a band's sets hold ut_cap_top(h) + band_h + ut_cap_bot(h) rows (the
+    // 128 rows of the largest history_rows, or what the frame has, above and below its own); its own
+    // rows are what its previous call wrote, and a call receives the halo rows of the set it reads
+    // from its neighbours' own rows of that set.  Peer copies: this band's rows of the read set are
+    // ready to be copied (ev_ut_ready) / this band has copied its neighbours' rows (ev_ut_copied: a
+    // neighbour's next call writes the set they came from)
     DevBuf d_ut_guide[2], d_ut_hist[2];
     int ut_set = 0;
     bool ut_valid = false, dn_guide_stale = false;
     uint32_t ut_camera[19] = {0};
     float ut_vp[16] = {0};
+    hipEvent_t ev_ut_ready = nullptr, ev_ut_copied = nullptr;
     // the rows [begin, end) of the ranks above and below, as ptx_comm_init's neighbour check received them
     uint32_t nb_rows[2][2] = {{0, 0}, {0, 0}};
     int present_src = PTX_BUF_ACCUM;
@@ -330,6 +338,26 @@ int upsample_source(ptx_handle *err, ptx_handle *lo);
 hipError_t upsample_launch(ptx_handle *hi, ptx_handle *lo, uint32_t s, float sigma_plane, uint32_t top, uint32_t bot);
 int upsample_done(ptx_handle *err, ptx_handle *hi);
 int upsample_release(ptx_handle *err, ptx_handle *lo, ptx_handle *hi);
+// The temporal upsampler's host side, shared by ptx_upsample_temporal and ptx_upsample_temporal_bands.
+// One call's parameters (bands: reserved[0] is history_rows, 0 = kUtRowsDefault, at most kUtRowsMax; the
+// whole-image call refuses every reserved word); the phase and the camera rule of a pair; the
+// buffers (the output, the two state sets, with halo rows the 2 x 2 small rows); and the two launches
+// with the state's bookkeeping: the mode from the handle's own state, dn_guide into the set the
+// call writes, the kernel (a whole image without halo rows: the whole-image kernel; else the window's,
+// with `top` / `bot` rows of lo's neighbours and ht / hb rows of the read set's halo), then ut_set,
+// ut_valid, ut_camera, ut_vp, dn_guide_stale and dn_stream.
+constexpr uint32_t kUtRowsDefault = 32, kUtRowsMax = 128;
+struct UtCall {
+    float sigma_plane = 0.02f, alpha_min = 0.02f, alpha_fill = 0.05f;
+    uint32_t px = 0, py = 0, rows = kUtRowsDefault;
+};
+inline uint32_t ut_cap_top(const ptx_handle *h) { return std::min(kUtRowsMax, h->cfg.row_begin); }
+inline uint32_t ut_cap_bot(const ptx_handle *h) { return std::min(kUtRowsMax, h->cfg.height - h->cfg.row_end); }
+int upsample_temporal_params(ptx_handle *err, const ptx_upsample_temporal_params *p, UtCall &c, const char *what, bool bands);
+int upsample_temporal_camera(ptx_handle *err, ptx_handle *hi, ptx_handle *lo, uint32_t s, const UtCall &c, const char *what);
+int upsample_temporal_alloc(ptx_handle *err, ptx_handle *hi, uint32_t halo_rows, uint32_t w);
+hipError_t upsample_temporal_launch(ptx_handle *hi, ptx_handle *lo, uint32_t s, const UtCall &c, uint32_t top, uint32_t bot,
+                                    uint32_t ht, uint32_t hb);
 // ptx_comm.cpp: a frame of a band handle that owns a communicator; a band frame without the
 // exchange (PTX_FLAG_HALO_SKIP, timing only); the communicator's teardown
 int render_band_nccl(ptx_handle *h);

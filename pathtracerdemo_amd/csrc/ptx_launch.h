@@ -106,6 +106,20 @@ struct UpWin {
 hipError_t launch_denoise_upsample_win(uint32_t s, uint32_t W, uint32_t H, const UpWin &win, const float4 *guide_hi,
                                        const float4 *guide_lo, const float4 *color_lo, const float4 *halo_lo, float4 *out,
                                        hipStream_t st);
+// ptx_upsample_temporal_bands: the same rows and window (`up`), integrated with the rows
+// [hy0, hy0 + hrows) of the frame the previous state covers, where guide_prev and hist_prev start;
+// hist and out start at row Y0.  *clip counts the pixels with a history tap inside the frame but
+// outside those rows (the tap is not taken).
+struct UtWin {
+    UpWin up;
+    uint32_t hy0, hrows;
+    unsigned long long *clip;
+};
+hipError_t launch_denoise_upsample_temporal_win(uint32_t s, uint32_t W, uint32_t H, uint32_t px, uint32_t py, float alpha_min,
+                                                float alpha_fill, uint32_t mode, const float *vp_prev, const UtWin &win,
+                                                const float4 *guide_hi, const float4 *guide_lo, const float4 *color_lo,
+                                                const float4 *halo_lo, const float4 *guide_prev, const float4 *hist_prev,
+                                                float4 *hist, float4 *out, hipStream_t st);
 
 // closest-hit queries for a ray array (ptx_kernels.hip)
 hipError_t launch_trace_rays(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,

@@ -339,6 +339,37 @@ class Renderer:
             raise N.PtxError(f"ptx_upsample_bands failed ({rc}): "
                              + "; ".join(m.decode(errors="replace") for m in msgs if m))
 
+    @staticmethod
+    def upsample_temporal_bands(his, los, px: int, py: int, sigma_plane: float = 0.0, alpha_min: float = 0.0,
+                                alpha_fill: float = -1.0, history_rows: int = 0) -> None:
+        """UpsampleTemporal over band pairs of this process (ptx_upsample_temporal_bands): los[i] is a band of
+        the small frame after denoise_bands, rendered through phase (px, py) (los[i].set_phase_of(his[i], s,
+        px, py) before its frame), his[i] the band of s times its rows of the full-size frame.  Each pair
+        reads 2 rows of its neighbours' denoised images and history_rows (0 = 32, at most 128) rows of
+        their previous state, brought on the device; a history tap past those rows is not taken and counts
+        in upsample_clips().  With no clips the bands' rows are the whole-image UpsampleTemporal's.
+        read_denoised / read_upsample_history work per full-size band."""
+        assert len(his) == len(los)
+        lib = N.load()
+        a = (ctypes.c_void_p * len(his))(*[r._h.value for r in his])
+        b = (ctypes.c_void_p * len(los))(*[r._h.value for r in los])
+        p = N.PtxUpsampleTemporalParams(sigma_plane=float(sigma_plane), px=int(px), py=int(py), alpha_min=float(alpha_min),
+                                        alpha_fill=float(alpha_fill))
+        p.reserved[0] = int(history_rows)
+        rc = lib.ptx_upsample_temporal_bands(a, b, len(his), ctypes.byref(p))
+        if rc != N.PTX_OK:
+            msgs = [lib.ptx_last_error(r._h) for r in list(his) + list(los)]
+            raise N.PtxError(f"ptx_upsample_temporal_bands failed ({rc}): "
+                             + "; ".join(m.decode(errors="replace") for m in msgs if m))
+
+    def upsample_clips(self) -> int:
+        """Pixels of this full-size band's upsample_temporal_bands calls (since the last reset_stats) with a
+        history candidate inside the image but outside the rows the band's state covered: not taken.  0 on
+        every band: the split is the whole image's bit for bit (PTX_COUNTER_UPSAMPLE_CLIP)."""
+        c = np.zeros(N.PTX_COUNTER_UPSAMPLE_CLIP + 1, dtype=np.uint64)
+        self._call("ptx_read_buffer", self._h, N.PTX_BUF_COUNTERS, c.ctypes.data, c.nbytes)
+        return int(c[N.PTX_COUNTER_UPSAMPLE_CLIP])
+
     def denoise_clips(self) -> int:
         """Pixels of this band's temporal denoise_bands calls (since the last reset_stats) with a history
         candidate inside the image but outside the rows the band's state covered: not taken.  0 on every

@@ -11,6 +11,10 @@
     python tools/denoise_time.py --displayed-frame [--upsample 2]   # ms per displayed frame under a yawing camera
     python tools/denoise_time.py --upsample 2 --phases  # ptx_upsample_temporal, the phases cycling (--displayed-frame,
                                                         # --no-events and --trace take --phases too)
+    python tools/denoise_time.py --bands 8 --upsample 2 --phases --width 3840 --height 2160 [--history-rows 32]
+                                                        # ptx_upsample_temporal_bands, 8 pairs
+    python tools/denoise_time.py --displayed-frame --bands 8 --upsample 2 --phases --width 3840 --height 2160 \
+        --history-rows 16,32,64                         # clipped pixels per band along the yawing camera path
 
 The whole call is timed with device events around it on the handle's stream (a torch stream set
 with ptx_set_stream): the median of --calls calls after --warmup.  The same calls on a
@@ -35,6 +39,12 @@ G-buffer pass; --width / --height are the full size.
 --bands times ptx_denoise_bands, against the whole-image ptx_upsample of the same frame on the same
 build: the sum of the bands' kernel times and device events around the call with every full-size
 handle on one stream, and the host's time from the call to its completion on the handles' own streams.
+--bands N --upsample S --phases times ptx_upsample_temporal_bands on the same N pairs, beside
+ptx_upsample_bands on them (small bands under the full-size camera) and beside the whole-image
+ptx_upsample_temporal, all in one process: kernel sums and device events around each call with every
+full-size handle on one stream.  The phases cycle and the camera yaws by --yaw-step before every call,
+so the history is reprojected.  With --displayed-frame it counts instead, for every --history-rows
+value, the pixels each band clips (PTX_COUNTER_UPSAMPLE_CLIP) over --calls displayed frames of that path.
 --displayed-frame times what a host does per displayed frame while the camera moves (it yaws by
 --yaw-step and the frame index restarts before every frame), with the host clock from the first call
 to the completion of the last: a full-size frame + ptx_denoise, or with --upsample S a frame +
@@ -494,6 +504,140 @@ def measure_upsample_bands(args):
     return out
 
 
+def measure_upsample_temporal_bands(args):
+    """ptx_upsample_temporal_bands on --bands equal pairs on this GPU (peer copies), beside ptx_upsample_bands on
+    the same pairs and the whole-image ptx_upsample_temporal; or (--displayed-frame) its clipped pixels per
+    band and history_rows along the yawing camera path."""
+    import torch
+    from pathtracerdemo_amd import _native as N
+    from pathtracerdemo_amd.renderer import Renderer
+    from pathtracerdemo_amd.scene.world import compile_scene
+    s, W, H, n = args.upsample, args.width, args.height, args.iterations
+    assert W % s == 0 and H % s == 0
+    w, h = W // s, H // s
+    cs = compile_scene(args.scene)
+    cuts = [h * i // args.bands for i in range(args.bands + 1)]
+    Ts = [int(t) for t in str(args.history_rows).split(",")]
+
+    def make(ww, hh, a=0, b=0):
+        r = Renderer(ww, hh, device=0, pipeline=args.pipeline, row_begin=a, row_end=b, time_launches=True)
+        r.Initialize(cs)
+        return r
+
+    def mmm(v):
+        return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+
+    def spent(rs):
+        return sum(r.stats()["kernel_ms_total"][N.PTX_STAT_DENOISE] for r in rs)
+
+    bands = [make(w, h, a, b) for a, b in zip(cuts, cuts[1:])]
+    his = [make(W, H, s * a, s * b) for a, b in zip(cuts, cuts[1:])]
+
+    def pose(rs, i):
+        for r in rs:
+            r.GetCamera().set_yaw(args.yaw_step * (i + 1))
+            r.ResetFrameCount()
+            r.Update()
+
+    def small_frame(los, full, phase):
+        """The small handles' frame of this camera (through the phase, if any), denoised and waited for."""
+        if phase is not None:
+            for lo, hi in zip(los, full):
+                lo.set_phase_of(hi, s, *phase)
+        if len(los) > 1:
+            Renderer.render_bands(los)
+            Renderer.denoise_bands(los, iterations=n)
+        else:
+            los[0].Render()
+            los[0].Denoise(iterations=n)
+        for r in los:
+            r.synchronize()
+
+    if args.displayed_frame:
+        clips = {}
+        for T in Ts:
+            for r in his:
+                r.reset_accumulation()  # (drops the state: every history_rows starts from a first call)
+                r.reset_stats()
+            for i in range(args.warmup + args.calls):
+                pose(bands + his, i)
+                small_frame(bands, his, phase_of(args, i))
+                for r in his:
+                    r.run_pass(N.PTX_PASS_GBUFFER)
+                px, py = phase_of(args, i)
+                Renderer.upsample_temporal_bands(his, bands, px, py, history_rows=T)
+            clips[str(T)] = [r.upsample_clips() for r in his]
+        for r in bands + his:
+            r.close()
+        return {"what": "ptx_upsample_temporal_bands clipped pixels, moving camera", "scale": s, "width": W, "height": H,
+                "scene": args.scene, "pipeline": args.pipeline, "bands": args.bands, "yaw_step": args.yaw_step,
+                "frames": args.warmup + args.calls, "clips_per_band_by_history_rows": clips}
+
+    T = Ts[0]
+    one, hi_one = make(w, h), make(W, H)
+    shared = torch.cuda.Stream()
+    for r in [hi_one] + his:
+        r.set_stream(shared.cuda_stream)
+    res = {k: ([], []) for k in ("upsample_bands", "upsample_temporal", "upsample_temporal_bands")}
+
+    def timed(kind, rs, call, keep):
+        k0 = spent(rs)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(shared)
+        call()
+        b.record(shared)
+        b.synchronize()
+        for r in rs:
+            r.synchronize()
+        if keep:
+            res[kind][0].append(spent(rs) - k0)
+            res[kind][1].append(a.elapsed_time(b))
+
+    # ptx_upsample_bands first (it drops the temporal state): the small bands under the full-size camera
+    for i in range(args.warmup + args.calls):
+        pose([one] + bands + his, i)
+        small_frame([one], [hi_one], None)  # (the whole-image small handle renders the same frames as the bands)
+        small_frame(bands, his, None)
+        for r in his:
+            r.run_pass(N.PTX_PASS_GBUFFER)
+            r.synchronize()
+        timed("upsample_bands", his, lambda: Renderer.upsample_bands(his, bands), i >= args.warmup)
+    # then the temporal calls, the whole image and the bands on the same frames
+    for i in range(args.warmup + args.calls):
+        pose([one, hi_one] + bands + his, i)
+        px, py = phase_of(args, i)
+        small_frame([one], [hi_one], (px, py))
+        small_frame(bands, his, (px, py))
+        for r in [hi_one] + his:
+            r.run_pass(N.PTX_PASS_GBUFFER)
+            r.synchronize()
+        timed("upsample_temporal", [hi_one], lambda: hi_one.UpsampleTemporal(one, px, py), i >= args.warmup)
+        timed("upsample_temporal_bands", his, lambda: Renderer.upsample_temporal_bands(his, bands, px, py, history_rows=T),
+              i >= args.warmup)
+    clips = [r.upsample_clips() for r in his]
+    same = all((b.read_denoised().view("uint32") == hi_one.read_denoised()[s * a:s * z].view("uint32")).all() and
+               (b.read_upsample_history().view("uint32") == hi_one.read_upsample_history()[s * a:s * z].view("uint32")).all()
+               for b, a, z in zip(his, cuts, cuts[1:]))
+    small_same = all((b.read_denoised().view("uint32") == one.read_denoised()[a:z].view("uint32")).all()
+                     for b, a, z in zip(bands, cuts, cuts[1:]))
+    med = {k: statistics.median(v[0]) for k, v in res.items()}
+    out = {"what": "ptx_upsample_temporal_bands", "scale": s, "width": W, "height": H, "scene": args.scene, "pipeline": args.pipeline,
+           "iterations": n, "bands": args.bands, "history_rows": T, "yaw_step": args.yaw_step, "calls": args.calls,
+           "warmup": args.warmup, "clips_per_band": clips, "equals_whole_image": bool(same),
+           "small_bands_equal_whole_image": bool(small_same),
+           "kernel_ms_sum": {k: mmm(v[0]) for k, v in res.items()},
+           "events_around_call_ms_one_stream": {k: mmm(v[1]) for k, v in res.items()},
+           "kernel_ratio_to_upsample_bands": round(med["upsample_temporal_bands"] / med["upsample_bands"], 3),
+           "kernel_ratio_to_whole_image": round(med["upsample_temporal_bands"] / med["upsample_temporal"], 3),
+           "halo_bytes_received_per_band": [[(2 * w * 16 + T * W * 48) if a else 0, (2 * w * 16 + T * W * 48) if z != h else 0]
+                                            for a, z in zip(cuts, cuts[1:])]}
+    for r in [hi_one] + his:
+        r.set_stream(None)
+    for r in [one, hi_one] + bands + his:
+        r.close()
+    return out
+
+
 def from_trace(args):
     """Median duration of each kernel of a call (guide, [temporal,] variance, iteration 0..n-1) over the traced
     calls of the last handle (the TIME_LAUNCHES one), warm-up calls dropped."""
@@ -540,11 +684,14 @@ def main():
     ap.add_argument("--bands", type=int, default=0, help="time ptx_denoise_bands on the frame as this many equal row bands")
     ap.add_argument("--upsample", type=int, default=0, help="time ptx_upsample from 1/S of --width x --height (S: 2, 3 or 4)")
     ap.add_argument("--phases", action="store_true", help="--upsample: ptx_upsample_temporal on small frames whose phase cycles")
+    ap.add_argument("--history-rows", default="32", help="--bands --upsample --phases: history_rows (--displayed-frame: a comma list)")
     ap.add_argument("--displayed-frame", action="store_true", help="host ms per displayed frame under a yawing camera")
     ap.add_argument("--no-events", action="store_true", help="only the TIME_LAUNCHES handle (the run a profiler traces)")
     ap.add_argument("--trace", help="a rocprofv3 run_kernel_trace.csv of this script: print per-kernel medians")
     args = ap.parse_args()
-    if args.displayed_frame:
+    if args.bands and args.upsample and args.phases:
+        out = measure_upsample_temporal_bands(args)
+    elif args.displayed_frame:
         out = measure_displayed_frame(args)
     elif args.upsample:
         out = upsample_from_trace(args) if args.trace else measure_upsample_bands(args) if args.bands else measure_upsample(args)
