@@ -171,6 +171,41 @@ int ptx_abi_version(void);
 int ptx_create(const ptx_config *cfg, ptx_handle **out);
 int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const uint32_t *geometry,
                      size_t n_geometry, const uint32_t *accel, size_t n_accel);
+/* Edit instances, materials and lights in place: replace the handle's scene array with one of the
+ * same layout (same length, same offsets and counts in the uniform set on the handle, same mesh
+ * descriptors); geometry and accel stay.  The array is compared with the handle's, block by block
+ * -- instances [0, 33 * n_inst), materials [off_mat, off_light), lights and their CDF
+ * [off_light, n_scene) -- and *changed_out (NULL ok) receives the PTX_EDIT_* bits of the blocks
+ * that differ; with none the call returns PTX_OK without waiting and without touching the GPU.
+ * Otherwise it waits for the frames in flight, uploads the changed words, and
+ *   PTX_EDIT_LIGHTS alone    keeps everything: PT_01 reads no light, so the kept G-buffer, the
+ *                            surface records and every history stay;
+ *   PTX_EDIT_MATERIALS       rebuilds the material table and the root records' transmission word,
+ *                            drops the kept G-buffers, surface records and neighbour summaries;
+ *   PTX_EDIT_INSTANCES       rebuilds the instance table and the cull bounds (an instance may
+ *                            switch to another loaded mesh), the same drops, and ptx_upsample_temporal's
+ *                            history (the temporal upsampler does not follow objects; the temporal
+ *                            mode of ptx_denoise does: below);
+ *   a switched mesh          drops the reuse / GI history outright: its reservoirs name triangles and
+ *                            sub-meshes of the instance's old mesh;
+ *   INSTANCES or MATERIALS   the reuse / GI history serves the next frame only if its camera words
+ *                            (uniform 4..22) are those of the frame that wrote it (the ordinary
+ *                            same-pixel temporal pass); a moved camera renders that one frame
+ *                            without history.  A LIGHTS-only edit never limits the history.
+ * After an instance or material edit the G-buffers on the handle are the old tables': ptx_denoise,
+ * ptx_upsample and their band and temporal forms are PTX_E_INVALID until a frame or a G-buffer pass
+ * has run.  The accumulation is not reset: the caller restarts the frame index as on a camera move.  Band
+ * handles and handles with a communicator: every band / rank makes the same call, nothing is exchanged.
+ * Refused with scene, tables and histories untouched, so that the next frame is the unedited one (like
+ * every error on a handle a refusal drops the kept G-buffers: that frame traces its primary rays
+ * again): PTX_E_INVALID -- a null handle or array, no scene or no frame set, another n_scene, a
+ * differing word outside the three blocks (the descriptors included); PTX_E_SCENE -- an instance whose
+ * mesh word is not a loaded mesh.  A HIP error after the upload has begun leaves the handle without a
+ * scene: ptx_upload_scene next. */
+#define PTX_EDIT_INSTANCES 1u
+#define PTX_EDIT_MATERIALS 2u
+#define PTX_EDIT_LIGHTS    4u
+int ptx_update_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, uint32_t *changed_out /* NULL ok */);
 int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]);
 /* Run the configured pipeline for the current frame; if rgba_out != NULL copy the band's
  * accumulated RGBA f32 image (band_h * W * 4) into it (blocking). Otherwise asynchronous.
@@ -295,6 +330,18 @@ int ptx_present_poll(ptx_handle *h, uint8_t *out, size_t bytes);
  * n = 0.  ptx_upload_scene and ptx_reset_accumulation drop the history; ptx_set_frame and the frame
  * index never do (the engine's ResetFrameCount on a camera move keeps it); a call with reserved[0] = 0
  * is the spatial filter exactly and neither reads nor writes the state.
+ *   Object motion: every temporal call also keeps the instance block of the scene array (33 words per
+ * instance).  While no instance differs from the previous call's, bit for bit, the call is the one
+ * above.  Otherwise (ptx_update_scene with PTX_EDIT_INSTANCES in between) every instance gets
+ * D = M_prev * Minv_cur (words 0..15 of the kept block times words 16..31 of the current one, in
+ * double, each element summed in k = 0..3 order and rounded once to f32) and a flag: 0 unchanged; 1
+ * moved rigidly -- both matrices' bottom rows exactly (0, 0, 0, 1), every element finite, the same mesh
+ * word, and max |L^T L - I| <= 1e-3 for D's upper 3x3 L; 2 anything else (a changed scale, another
+ * mesh).  A pixel with a primary hit of instance i (its key >> 16): flag 0 as above; flag 2 no lookup,
+ * it starts from the frame's colour with n = 1; flag 1 Q = D P and Nq = D N (the linear part, not
+ * renormalised) are where its point and normal were, Q is reprojected through the previous call's VP
+ * whether or not the camera words changed, taps and weights as above, and a tap is tested against
+ * Nq (dot >= 0.9) and Q (|dot(Nq, P' - Q)| <= this pixel's r).
  * Launches: 3 + iterations (guide records, dn_temporal, variance, the iterations). */
 typedef struct ptx_denoise_params {
     uint32_t iterations;      /* 1..6 (step 2^i in iteration i); 0 = default 5 */
@@ -443,6 +490,8 @@ int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n,
  * pixel beside the 16 of the output, allocated by the first call, counted in device_bytes).
  * ptx_upload_scene, ptx_reset_accumulation, ptx_upsample, ptx_upsample_bands, ptx_denoise and
  * ptx_denoise_bands on hi drop the history (the next call is a first call); ptx_set_frame never does.
+ * ptx_update_scene with PTX_EDIT_INSTANCES on hi drops it too: the temporal upsampler does not follow
+ * moved objects (the temporal mode of ptx_denoise does); a material or light edit keeps it.
  * After the call hi is no source of a ptx_upsample until it has been denoised or upsampled itself.
  *   PTX_E_INVALID with the reason in hi's ptx_last_error, before any GPU work: everything ptx_upsample
  * refuses (band handles: ptx_upsample_temporal_bands), a phase not below s, a lo whose camera is not that

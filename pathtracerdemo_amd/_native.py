@@ -45,6 +45,7 @@ PTX_FLAG_HALO_OVERLAP = 128
 PTX_FLAG_HALO_SKIP = 256  # band frame without the exchange: timing only (edge rows are not the split frame's)
 PTX_FLAG_FRAME_COLOR = 512  # keep PTX_BUF_FRAME_COLOR (needed by ptx_denoise's temporal mode)
 PTX_COMM_ID_BYTES = 128
+PTX_EDIT_INSTANCES, PTX_EDIT_MATERIALS, PTX_EDIT_LIGHTS = 1, 2, 4  # ptx_update_scene's mask of changed blocks
 VARIANT_FLAGS = {"wave": 0, "simple": PTX_FLAG_SIMPLE_KERNELS}
 
 # every symbol include/ptx.h declares (checked by tests/test_abi.py)
@@ -56,7 +57,7 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_row_census", "ptx_comm_info", "ptx_present", "ptx_present_async", "ptx_present_poll",
             "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands",
             "ptx_upsample", "ptx_upsample_bands", "ptx_phase_uniform", "ptx_upsample_temporal",
-            "ptx_trace_queries", "ptx_upsample_temporal_bands"]
+            "ptx_trace_queries", "ptx_upsample_temporal_bands", "ptx_update_scene"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -125,6 +126,7 @@ def load(path: str = LIB_PATH):
     lib.ptx_abi_version.restype = ctypes.c_int
     lib.ptx_create.argtypes = [ctypes.POINTER(PtxConfig), ctypes.POINTER(H)]
     lib.ptx_upload_scene.argtypes = [H, P, ctypes.c_size_t, P, ctypes.c_size_t, P, ctypes.c_size_t]
+    lib.ptx_update_scene.argtypes = [H, P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]
     lib.ptx_set_frame.argtypes = [H, P]
     lib.ptx_render.argtypes = [H, P]
     lib.ptx_run_pass.argtypes = [H, ctypes.c_int]

@@ -278,6 +278,70 @@ static void inst_world_box(Inst &I, const SubRoot *roots, uint32_t nsub) {
     I.wscale = std::nextafter((float)scale, HUGE_VALF);
 }
 
+// The tables that depend on the scene array's instance and material blocks, from build_layout's
+// per-mesh results (h->lay_*): the instance table with the cull bounds, and the material table with the
+// root records' transmission word.  build_layout derives both; ptx_update_scene only what an edit
+// touched.  Nothing of the handle changes when an instance names a mesh that is not loaded.
+static int layout_tables(ptx_handle *h, bool with_insts, bool with_mats) {
+    const auto &S = h->scene;
+    const uint32_t n_inst = h->n_inst, n_mesh = (uint32_t)h->lay_mesh_nsub.size();
+    std::vector<Inst> insts;
+    float cull_box = 0.0f, cull_pad = 0.0f, cull_scale = 0.0f;
+    if (with_insts) {
+        insts.resize(n_inst);
+        for (uint32_t i = 0; i < n_inst; ++i) {
+            const uint32_t *p = S.data() + STRIDE_INSTANCE * i;
+            Inst &I = insts[i];
+            std::memcpy(I.m, p, 64);
+            std::memcpy(I.minv, p + 16, 64);
+            I.mesh = p[32];
+            if (I.mesh >= n_mesh) return fail(h, PTX_E_SCENE, "instance %u references mesh %u of %u", i, I.mesh, n_mesh);
+            I.sub_base = h->lay_mesh_sub_base[I.mesh];
+            I.nsub = h->lay_mesh_nsub[I.mesh];
+            I.tri_base = h->lay_mesh_tri_base[I.mesh];
+            // exactly the identity (bitwise 1 / +0, M and M^-1): the kernels' transforms of this
+            // instance reduce to x + 0 (inst_point, ptx_device.h) with the same bits
+            static const float kId[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+            if (!std::memcmp(I.m, kId, sizeof kId) && !std::memcmp(I.minv, kId, sizeof kId)) I.mesh |= kInstIdentity;
+            inst_world_box(I, h->lay_subs.data() + I.sub_base, I.nsub);
+            if (I.wpad >= 0.0f) {  // (a culled instance's coordinates are finite: inst_world_box)
+                for (int k = 0; k < 3; ++k) cull_box = std::max({cull_box, std::fabs(I.wlo[k]), std::fabs(I.whi[k])});
+                cull_pad = std::max(cull_pad, I.wpad);
+                cull_scale = std::max(cull_scale, I.wscale);
+            }
+        }
+    }
+    if (with_mats) {
+        // GetMaterial (SH/PT_1_InitPass.wgsl:285-314) per sub-mesh: material d[2] + 15*sub.  A record
+        // past the scene buffer reads as zeros (WebGPU's robust buffer access would clamp or zero).
+        std::vector<float> mats;  // 8 floats per sub-mesh, in SubRoot order (Scene::mats)
+        for (const size_t mi : h->lay_mat_word) {
+            auto word = [&](uint32_t k) { return mi + k < S.size() ? as_f32(S[mi + k]) : 0.0f; };
+            const float trans = word(10);
+            const bool yellow = trans > 0.0f;
+            const float rec[8] = {yellow ? 1.0f : word(0), yellow ? 1.0f : word(1), yellow ? 0.0f : word(2), word(8),
+                                  std::fmax(word(9), 0.01f), trans, word(11), 0.0f};
+            mats.insert(mats.end(), rec, rec + 8);
+        }
+        if (mats.empty()) mats.resize(8, 0.0f);
+        auto &subs = h->lay_subs;
+        // each root record carries its sub-mesh's transmission (the Visibility restart test reads
+        // it from the trace kernel's LDS root table: subs_transmission)
+        if (mats.size() != 8u * subs.size()) return fail(h, PTX_E_SCENE, "material / sub-mesh tables disagree");
+        for (size_t k = 0; k < subs.size(); ++k) std::memcpy(&subs[k].pad, &mats[8u * k + 5u], 4);
+        if (int rc = upload(h, h->d_subs, subs.data(), subs.size() * sizeof(SubRoot))) return rc;
+        h->n_subs = (uint32_t)subs.size();
+        if (int rc = upload(h, h->d_mats, mats.data(), mats.size() * sizeof(float))) return rc;
+    }
+    if (with_insts) {
+        if (int rc = upload(h, h->d_insts, insts.data(), std::max<size_t>(1, insts.size()) * sizeof(Inst))) return rc;
+        h->cull_box = cull_box;
+        h->cull_pad = cull_pad;
+        h->cull_scale = cull_scale;
+    }
+    return PTX_OK;
+}
+
 // ---------------------------------------------------------------- layout derivation
 // Walks the reference's per-sub-mesh BLAS (three-mesh-bvh node format, GC/Structs.ts:73-80;
 // read by GetBlasNode, SH/PT_01_GBufferPass.wgsl:310-322) and emits the child-pair node
@@ -299,7 +363,7 @@ int build_layout(ptx_handle *h) {
     std::vector<SubRoot> subs;
     std::vector<NodePair> nodes;
     std::vector<float> tris;  // 12 floats per triangle
-    std::vector<float> mats;  // 8 floats per sub-mesh, in SubRoot order (Scene::mats)
+    std::vector<size_t> mat_word;  // per sub-mesh, in SubRoot order: its material record in the scene array
     std::vector<float> tverts;  // 20 floats per triangle, triangle-table order (Scene::tverts)
     std::vector<uint32_t> mesh_sub_base(n_mesh), mesh_nsub(n_mesh), mesh_tri_base(n_mesh);
     uint32_t max_depth = 0;
@@ -312,15 +376,7 @@ int build_layout(ptx_handle *h) {
         mesh_tri_base[m] = (uint32_t)(tris.size() / 12);
         // GetMaterial (SH/PT_1_InitPass.wgsl:285-314) per sub-mesh: material d[2] + 15*sub.  A record
         // past the scene buffer reads as zeros (WebGPU's robust buffer access would clamp or zero).
-        for (uint32_t s = 0; s < nsub; ++s) {
-            const size_t mi = (size_t)off_mat + d[2] + (size_t)STRIDE_MATERIAL * s;
-            auto word = [&](uint32_t k) { return mi + k < S.size() ? as_f32(S[mi + k]) : 0.0f; };
-            const float trans = word(10);
-            const bool yellow = trans > 0.0f;
-            const float rec[8] = {yellow ? 1.0f : word(0), yellow ? 1.0f : word(1), yellow ? 0.0f : word(2), word(8),
-                                  std::fmax(word(9), 0.01f), trans, word(11), 0.0f};
-            mats.insert(mats.end(), rec, rec + 8);
-        }
+        for (uint32_t s = 0; s < nsub; ++s) mat_word.push_back((size_t)off_mat + d[2] + (size_t)STRIDE_MATERIAL * s);
         uint32_t mesh_tris = 0;
         struct Pending { uint32_t base; std::vector<uint32_t> order; };
         std::vector<Pending> per_sub;
@@ -406,51 +462,22 @@ int build_layout(ptx_handle *h) {
             tverts.insert(tverts.end(), tv, tv + 20);
         }
     }
-    std::vector<Inst> insts(n_inst);
-    float cull_box = 0.0f, cull_pad = 0.0f, cull_scale = 0.0f;
-    for (uint32_t i = 0; i < n_inst; ++i) {
-        const uint32_t *p = S.data() + STRIDE_INSTANCE * i;
-        Inst &I = insts[i];
-        std::memcpy(I.m, p, 64);
-        std::memcpy(I.minv, p + 16, 64);
-        I.mesh = p[32];
-        if (I.mesh >= n_mesh) return fail(h, PTX_E_SCENE, "instance %u references mesh %u of %u", i, I.mesh, n_mesh);
-        I.sub_base = mesh_sub_base[I.mesh];
-        I.nsub = mesh_nsub[I.mesh];
-        I.tri_base = mesh_tri_base[I.mesh];
-        // exactly the identity (bitwise 1 / +0, M and M^-1): the kernels' transforms of this
-        // instance reduce to x + 0 (inst_point, ptx_device.h) with the same bits
-        static const float kId[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-        if (!std::memcmp(I.m, kId, sizeof kId) && !std::memcmp(I.minv, kId, sizeof kId)) I.mesh |= kInstIdentity;
-        inst_world_box(I, subs.data() + I.sub_base, I.nsub);
-        if (I.wpad >= 0.0f) {  // (a culled instance's coordinates are finite: inst_world_box)
-            for (int k = 0; k < 3; ++k) cull_box = std::max({cull_box, std::fabs(I.wlo[k]), std::fabs(I.whi[k])});
-            cull_pad = std::max(cull_pad, I.wpad);
-            cull_scale = std::max(cull_scale, I.wscale);
-        }
-    }
     if (tris.empty()) tris.resize(12, 0.0f);
     if (tverts.empty()) tverts.resize(20, 0.0f);
     if (nodes.empty()) nodes.resize(1);
     if (subs.empty()) subs.resize(1);
-    if (mats.empty()) mats.resize(8, 0.0f);
-    // each root record carries its sub-mesh's transmission (the Visibility restart test reads
-    // it from the trace kernel's LDS root table: subs_transmission)
-    if (mats.size() != 8u * subs.size()) return fail(h, PTX_E_SCENE, "material / sub-mesh tables disagree");
-    for (size_t k = 0; k < subs.size(); ++k) std::memcpy(&subs[k].pad, &mats[8u * k + 5u], 4);
+    h->lay_subs = std::move(subs);
+    h->lay_mat_word = std::move(mat_word);
+    h->lay_mesh_sub_base = std::move(mesh_sub_base);
+    h->lay_mesh_nsub = std::move(mesh_nsub);
+    h->lay_mesh_tri_base = std::move(mesh_tri_base);
+    h->n_inst = n_inst;
+    if (int rc = layout_tables(h, true, true)) return rc;
     if (int rc = upload(h, h->d_tris, tris.data(), tris.size() * sizeof(float))) return rc;
     if (int rc = upload(h, h->d_nodes, nodes.data(), nodes.size() * sizeof(NodePair))) return rc;
-    if (int rc = upload(h, h->d_subs, subs.data(), subs.size() * sizeof(SubRoot))) return rc;
-    h->n_subs = (uint32_t)subs.size();
-    if (int rc = upload(h, h->d_insts, insts.data(), std::max<size_t>(1, insts.size()) * sizeof(Inst))) return rc;
-    if (int rc = upload(h, h->d_mats, mats.data(), mats.size() * sizeof(float))) return rc;
     if (int rc = upload(h, h->d_tverts, tverts.data(), tverts.size() * sizeof(float))) return rc;
     h->n_tris = (uint32_t)(tris.size() / 12);
     h->n_nodes = (uint32_t)nodes.size();
-    h->n_inst = n_inst;
-    h->cull_box = cull_box;
-    h->cull_pad = cull_pad;
-    h->cull_scale = cull_scale;
     h->max_depth = max_depth;
     h->stack_depth = max_depth + 2u;
     if ((size_t)h->stack_depth * kBlock * 4u > 160u * 1024u)
@@ -1172,6 +1199,7 @@ void mark_history(ptx_handle *h) {
     std::memcpy(h->hist_camera, h->uniform + 4, sizeof h->hist_camera);
     h->hist_valid = true;
     h->hist_moved = false;
+    h->hist_same_only = false;
 }
 
 // 4x4 inverse of a column-major f32 matrix in double by cofactors, rounded to f32 (zeros when
@@ -1628,6 +1656,42 @@ static hipError_t denoise_timed(ptx_handle *h, hipStream_t st, hipError_t le_in,
 // The window's row 0 in the denoiser's buffers (they start dn_cap_top rows above the band).
 static size_t dn_win_px(const ptx_handle *h, const DnBand &b) { return (size_t)(h->dn_cap_top - b.top) * h->cfg.width; }
 
+// dn_temporal<true>'s table: per instance, what became of it between the previous temporal call's
+// instance block (`prev`, 33 words each: M, M^-1, mesh) and this call's (`cur`).  D = M_prev * Minv_cur
+// in double, each element summed in k = 0..3 order and rounded once to f32.  Rigid (flag 1): both
+// matrices' bottom rows exactly (0, 0, 0, 1), every element of both and of D finite, the same mesh,
+// and D's upper 3x3 L orthonormal: max |L^T L - I| <= 1e-3 in double.
+static std::vector<DnObj> denoise_objects(const uint32_t *prev, const uint32_t *cur, uint32_t n_inst) {
+    std::vector<DnObj> out(n_inst);
+    for (uint32_t i = 0; i < n_inst; ++i) {
+        const uint32_t *p = prev + (size_t)STRIDE_INSTANCE * i, *c = cur + (size_t)STRIDE_INSTANCE * i;
+        DnObj &o = out[i];
+        std::memset(&o, 0, sizeof o);
+        if (!std::memcmp(p, c, STRIDE_INSTANCE * 4u)) continue;
+        float m[16], v[16];
+        std::memcpy(m, p, sizeof m);
+        std::memcpy(v, c + 16, sizeof v);
+        bool rigid = p[32] == c[32] && m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f && v[3] == 0.0f &&
+                     v[7] == 0.0f && v[11] == 0.0f && v[15] == 1.0f;
+        for (int col = 0; col < 4; ++col)
+            for (int row = 0; row < 4; ++row) {
+                double s = 0.0;
+                for (int k = 0; k < 4; ++k) s += (double)m[row + 4 * k] * (double)v[k + 4 * col];
+                o.d[row + 4 * col] = (float)s;
+            }
+        for (int k = 0; k < 16; ++k) rigid = rigid && std::isfinite(m[k]) && std::isfinite(v[k]) && std::isfinite(o.d[k]);
+        double worst = 0.0;
+        for (int a = 0; a < 3 && rigid; ++a)
+            for (int b = 0; b < 3; ++b) {
+                double s = 0.0;
+                for (int k = 0; k < 3; ++k) s += (double)o.d[k + 4 * a] * (double)o.d[k + 4 * b];
+                worst = std::max(worst, std::fabs(s - (a == b ? 1.0 : 0.0)));
+            }
+        o.flag = rigid && worst <= 1e-3 ? 1u : 2u;
+    }
+    return out;
+}
+
 int denoise_front(ptx_handle *h, const DnCall &c, DnBand &b) {
     // on the current frame's stream, after it (ptx_present_async's place): a pipelined handle's next
     // frame records ev_prev on this stream first, and its accumulation waits for ev_prev; this
@@ -1653,13 +1717,22 @@ int denoise_front(ptx_handle *h, const DnCall &c, DnBand &b) {
         const uint32_t buf0 = h->cfg.row_begin - h->dn_cap_top;  // the frame's row of the buffers' row 0
         const uint32_t plo = mode ? h->dn_cov_lo : h->cfg.row_begin, phi = mode ? h->dn_cov_hi : h->cfg.row_end;
         const size_t ppx = (size_t)(plo - buf0) * W;
+        // object motion: an instance whose 33 words differ from the previous call's snapshot
+        const DnObj *obj = nullptr;
+        const size_t iw = (size_t)STRIDE_INSTANCE * h->n_inst;
+        if (mode && iw <= h->scene.size() && h->dn_insts.size() == iw &&
+            std::memcmp(h->dn_insts.data(), h->scene.data(), iw * 4u) != 0) {
+            const std::vector<DnObj> table = denoise_objects(h->dn_insts.data(), h->scene.data(), h->n_inst);
+            if (int rc = upload(h, h->d_dn_obj, table.data(), table.size() * sizeof(DnObj))) return rc;
+            obj = (const DnObj *)h->d_dn_obj.p;
+        }
         e = denoise_timed(h, st, e, [&] {
             return launch_denoise_temporal(W, h->cfg.height, win, h->dn_vp, c.alpha_min, mode, plo, phi - plo, guide + 2u * wpx,
                                            (const float4 *)h->d_frame_color.p, (const float4 *)h->d_accum.p,
                                            (const float4 *)h->d_dn_guide_prev.p + 2u * ppx,
                                            (const float4 *)h->d_dn_hist[rd].p + ppx, (const float2 *)h->d_dn_mom[rd].p + ppx,
                                            (float4 *)h->d_dn_hist[b.wr].p + wpx, (float2 *)h->d_dn_mom[b.wr].p + wpx,
-                                           (unsigned long long *)h->d_counters.p + CNT_DENOISE_CLIP, st);
+                                           (unsigned long long *)h->d_counters.p + CNT_DENOISE_CLIP, obj, h->n_inst, st);
         });
     }
     if (e != hipSuccess) return fail(h, PTX_E_HIP, "denoiser launch: %s", hipGetErrorString(e));
@@ -1709,6 +1782,7 @@ int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b) {
         h->dn_cov_lo = y0;
         h->dn_cov_hi = y0 + rows;
         std::memcpy(h->dn_camera, h->uniform + 4, sizeof h->dn_camera);
+        h->dn_insts.assign(h->scene.begin(), h->scene.begin() + std::min(h->scene.size(), (size_t)STRIDE_INSTANCE * h->n_inst));
         float vpinv[16];
         std::memcpy(vpinv, h->dn_camera, sizeof vpinv);
         mat4_inverse(vpinv, h->dn_vp);
@@ -2061,6 +2135,86 @@ int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const
     return PTX_OK;
 }
 
+int ptx_update_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, uint32_t *changed_out) {
+    if (!h) return PTX_E_INVALID;
+    if (!scene) return fail(h, PTX_E_INVALID, "ptx_update_scene: null scene array");
+    if (!h->scene_loaded || !h->frame_set || !h->layout_valid)
+        return fail(h, PTX_E_INVALID, "ptx_update_scene: upload a scene and set a frame first");
+    if (n_scene != h->scene.size())
+        return fail(h, PTX_E_INVALID, "ptx_update_scene: %zu words, the uploaded array has %zu", n_scene, h->scene.size());
+    // the blocks, through the uniform set on the handle: instances, (descriptors,) materials, lights + CDF
+    const uint32_t *U = h->uniform;
+    const size_t inst_end = (size_t)STRIDE_INSTANCE * h->n_inst, off_mat = U[U_OFF_MAT], off_light = U[U_OFF_LIGHT];
+    if (inst_end > off_mat || off_mat > off_light || off_light > n_scene)
+        return fail(h, PTX_E_INVALID, "ptx_update_scene: the uniform's offsets do not order the scene array's blocks");
+    const size_t lo[3] = {0, off_mat, off_light}, hi[3] = {inst_end, off_light, n_scene};
+    size_t first[3], last[3];  // the changed words of each block: [first, last)
+    uint32_t mask = 0;
+    for (int b = 0; b < 3; ++b) {
+        first[b] = last[b] = hi[b];
+        for (size_t w = lo[b]; w < hi[b]; ++w)
+            if (scene[w] != h->scene[w]) {
+                if (first[b] == hi[b]) first[b] = w;
+                last[b] = w + 1;
+            }
+        if (first[b] != hi[b]) mask |= 1u << b;
+    }
+    static_assert(PTX_EDIT_INSTANCES == 1u && PTX_EDIT_MATERIALS == 2u && PTX_EDIT_LIGHTS == 4u, "block order");
+    if (std::memcmp(scene + inst_end, h->scene.data() + inst_end, (off_mat - inst_end) * 4u) != 0)
+        return fail(h, PTX_E_INVALID, "ptx_update_scene: the mesh descriptors differ: a new layout needs ptx_upload_scene");
+    bool mesh_switched = false;  // an instance names another loaded mesh
+    if (mask & PTX_EDIT_INSTANCES) {
+        const uint32_t n_mesh = (uint32_t)h->lay_mesh_nsub.size();
+        for (uint32_t i = 0; i < h->n_inst; ++i) {
+            const uint32_t mesh = scene[STRIDE_INSTANCE * i + 32u];
+            if (mesh >= n_mesh)
+                return fail(h, PTX_E_SCENE, "ptx_update_scene: instance %u references mesh %u of %u", i, mesh, n_mesh);
+            mesh_switched = mesh_switched || mesh != h->scene[STRIDE_INSTANCE * i + 32u];
+        }
+    }
+    if (changed_out) *changed_out = mask;
+    if (!mask) return PTX_OK;
+    HIP_CHECK(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;  // frames in flight still read the scene array and the tables
+    // From here on the handle changes.  A HIP error part-way would leave the device's scene array or
+    // tables between the two scenes: the handle then holds no scene until the next ptx_upload_scene.
+    int rc = PTX_OK;
+    for (int b = 0; b < 3 && rc == PTX_OK; ++b) {
+        if (!(mask & (1u << b))) continue;
+        std::memcpy(h->scene.data() + first[b], scene + first[b], (last[b] - first[b]) * 4u);
+        if (copy_sync(h, (uint32_t *)h->d_scene.p + first[b], scene + first[b], (last[b] - first[b]) * 4u,
+                      hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(h, PTX_E_HIP, "ptx_update_scene: the copy of the changed words failed");
+    }
+    const bool tables = (mask & (PTX_EDIT_INSTANCES | PTX_EDIT_MATERIALS)) != 0;
+    if (rc == PTX_OK && tables)
+        rc = layout_tables(h, (mask & PTX_EDIT_INSTANCES) != 0, (mask & PTX_EDIT_MATERIALS) != 0);
+    if (rc != PTX_OK) {
+        h->scene_loaded = h->layout_valid = false;
+        h->hist_valid = h->dn_hist_valid = h->ut_valid = h->drawn = h->rendered = false;
+        for (auto &c : h->ctx) c.surf_valid = c.init_state_valid = c.nbr_valid = false;
+        gbuf_key_drop_all(h);
+        return rc;
+    }
+    if (!tables) return PTX_OK;  // (PT_01 reads no light: everything kept stays)
+    gbuf_key_drop_all(h);  // (hits and materials of the old tables)
+    for (auto &c : h->ctx) c.surf_valid = c.init_state_valid = c.nbr_valid = false;
+    // the G-buffers on the handle are the old tables': no denoise or upsample before a frame or a
+    // G-buffer pass has traced them again (dn_guide would decode old hits through the new tables)
+    h->drawn = h->rendered = false;
+    // the reuse history: its frame's surface records (d_psurf, what the motion pass reprojects with)
+    // were made with the old tables, so it serves that frame's camera alone
+    h->hist_same_only = true;
+    if (h->hist_moved) h->hist_valid = false;
+    // ... and not at all once an instance names another mesh: the history's reservoirs store their path
+    // vertices as (instance, triangle of its mesh, sub-mesh), which the passes decode with the new
+    // instance table -- indices of the old mesh would read another mesh's records, or past the tables
+    if (mesh_switched) h->hist_valid = false;
+    // ptx_upsample_temporal does not follow objects; ptx_denoise's temporal mode does (denoise_front)
+    if (mask & PTX_EDIT_INSTANCES) h->ut_valid = false;
+    return PTX_OK;
+}
+
 int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]) {
     if (!h || !uniform) return PTX_E_INVALID;
     HIP_CHECK(h, hipSetDevice(h->device));  // handles of one process may sit on several GPUs
@@ -2081,7 +2235,8 @@ int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]) {
     // bring the neighbours' rows of it); pass by pass it is reusable only for the camera that
     // produced it (reuse_args / gi_args)
     h->hist_moved = std::memcmp(h->hist_camera, uniform + 4, sizeof h->hist_camera) != 0;
-    if (h->hist_moved && !has_reuse(h)) h->hist_valid = false;
+    // (after an instance or material edit the history is the edited frame's camera's alone: ptx_update_scene)
+    if (h->hist_moved && (!has_reuse(h) || h->hist_same_only)) h->hist_valid = false;
     if (h->scene_loaded && !h->layout_valid) return build_layout(h);
     return PTX_OK;
 }
@@ -2275,7 +2430,7 @@ int ptx_get_stats(ptx_handle *h, ptx_stats *out) {
                         c.surf.bytes + h->d_psurf.bytes + c.direct.bytes + h->d_dn_guide.bytes + h->d_dn_work.bytes +
                         h->d_denoised.bytes + h->d_frame_color.bytes + h->d_dn_guide_prev.bytes + h->d_dn_hist[0].bytes +
                         h->d_dn_hist[1].bytes + h->d_dn_mom[0].bytes + h->d_dn_mom[1].bytes + h->d_dn_halo_g.bytes +
-                        h->d_dn_halo_c.bytes + h->d_up_halo.bytes + h->d_ut_guide[0].bytes + h->d_ut_guide[1].bytes +
+                        h->d_dn_halo_c.bytes + h->d_dn_obj.bytes + h->d_up_halo.bytes + h->d_ut_guide[0].bytes + h->d_ut_guide[1].bytes +
                         h->d_ut_hist[0].bytes + h->d_ut_hist[1].bytes;
     return PTX_OK;
 }
@@ -2676,7 +2831,7 @@ int ptx_destroy(ptx_handle *h) {
                       &h->d_insts, &h->d_mats, &h->d_tverts, &h->d_accum, &h->d_counters, &h->d_qrays, &h->d_qhits, &h->d_qcnt, &h->d_hist,
                       &h->d_jstate, &h->d_jres, &h->d_replay, &h->d_psurf, &h->d_census, &h->d_wgt, &h->d_dn_guide, &h->d_dn_work,
                       &h->d_denoised, &h->d_frame_color, &h->d_dn_guide_prev, &h->d_dn_hist[0], &h->d_dn_hist[1], &h->d_dn_mom[0],
-                      &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_up_halo, &h->d_ut_guide[0], &h->d_ut_guide[1],
+                      &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_dn_obj, &h->d_up_halo, &h->d_ut_guide[0], &h->d_ut_guide[1],
                       &h->d_ut_hist[0], &h->d_ut_hist[1]})
         free_buf(*b);
     for (auto &c : h->ctx) {

@@ -140,12 +140,19 @@ constexpr float kDnNMoments = 4.0f;  // from this length on the variance comes f
 // The four taps' records are gathered directly, all issued ahead of the tests: under
 // camera motion a tile's footprint in the previous frame is a shifted, nearly rigid tile, so
 // neighbouring lanes' taps share cache lines, but its extent is not bounded.
+// OBJ (a call that finds an instance changed since the previous one: denoise_front's table, one DnObj
+// per instance, a hit pixel's is obj[key >> 16]; past n_obj: flag 0): flag 0 as without the table;
+// flag 2 no lookup (n = 1); flag 1 the instance moved rigidly -- the hit point and normal go through
+// D = M_prev * Minv_cur to where they were at the previous call, Q and Nq (not renormalised), Q is
+// always reprojected through vp, the same camera or not, and the taps are tested against Q and Nq.
+template <bool OBJ>
 __global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, const DnWin win, const DnHistory Hs,
                                                       const float4 *__restrict__ guide, const float4 *__restrict__ frame,
                                                       const float4 *__restrict__ accum, const float4 *__restrict__ pguide,
                                                       const float4 *__restrict__ phist, const float2 *__restrict__ pmom,
                                                       float4 *__restrict__ hist, float2 *__restrict__ mom,
-                                                      unsigned long long *__restrict__ clip) {
+                                                      unsigned long long *__restrict__ clip,
+                                                      const DnObj *__restrict__ obj, uint32_t n_obj) {
     const uint32_t x = blockIdx.x * kDnTile + (threadIdx.x & 15u), y = win.c0 + blockIdx.y * kDnTile + (threadIdx.x >> 4);
     if (x >= W || y >= win.c1) return;
     const size_t pix = (size_t)y * W + x, own = (size_t)(y - win.c0) * W + x;
@@ -162,21 +169,36 @@ __global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, co
     const float l = luminance(F);
     f3 C = F;
     float m1 = l, m2 = l * l, n = 1.0f;
-    if (Hs.mode != 0u) {
+    uint32_t flag = 0u;
+    f3 Q = Pp, Nq = Np;  // the point and normal the previous call saw
+    if (OBJ) {
+        const uint32_t inst = key >> 16;
+        if (Hs.mode != 0u && inst < n_obj) flag = obj[inst].flag;
+        if (flag == 1u) {
+            const float *d = obj[inst].d;
+            Q.x = ((d[0] * Pp.x + d[4] * Pp.y) + d[8] * Pp.z) + d[12];
+            Q.y = ((d[1] * Pp.x + d[5] * Pp.y) + d[9] * Pp.z) + d[13];
+            Q.z = ((d[2] * Pp.x + d[6] * Pp.y) + d[10] * Pp.z) + d[14];
+            Nq.x = (d[0] * Np.x + d[4] * Np.y) + d[8] * Np.z;
+            Nq.y = (d[1] * Np.x + d[5] * Np.y) + d[9] * Np.z;
+            Nq.z = (d[2] * Np.x + d[6] * Np.y) + d[10] * Np.z;
+        }
+    }
+    if (Hs.mode != 0u && !(OBJ && flag == 2u)) {
         // candidate taps k = 2 j + i (j outer): pixel, bilinear weight, inside the image
         size_t q[4];
         float w[4];
         bool in[4], clipped = false;
         // this pixel in the previous state (a band's own rows are always covered)
         const size_t pc = (size_t)(win.y0 + y - Hs.y0) * W + x;
-        if (Hs.mode == 1u) {
+        if (Hs.mode == 1u && !(OBJ && flag == 1u)) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) { q[k] = pc; w[k] = 1.0f; in[k] = k == 0; }
         } else {
             const float *vp = Hs.vp;
-            const float cx = ((vp[0] * Pp.x + vp[4] * Pp.y) + vp[8] * Pp.z) + vp[12];
-            const float cy = ((vp[1] * Pp.x + vp[5] * Pp.y) + vp[9] * Pp.z) + vp[13];
-            const float cw = ((vp[3] * Pp.x + vp[7] * Pp.y) + vp[11] * Pp.z) + vp[15];
+            const float cx = ((vp[0] * Q.x + vp[4] * Q.y) + vp[8] * Q.z) + vp[12];
+            const float cy = ((vp[1] * Q.x + vp[5] * Q.y) + vp[9] * Q.z) + vp[13];
+            const float cw = ((vp[3] * Q.x + vp[7] * Q.y) + vp[11] * Q.z) + vp[15];
             const float fx = ((cx / cw + 1.0f) * 0.5f) * (float)W - 0.5f, fy = ((cy / cw + 1.0f) * 0.5f) * (float)H - 0.5f;
             const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
             const float ax = fx - x0, ay = fy - y0;
@@ -212,8 +234,8 @@ __global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, co
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (!in[k] || asu(qa[k].w) != key || !(qh[k].w >= 1.0f)) continue;
-            if (!(dot(Np, rgb(qb[k])) >= 0.9f)) continue;
-            if (!(__builtin_fabsf(dot(Np, rgb(qa[k]) - Pp)) <= b.w)) continue;
+            if (!(dot(Nq, rgb(qb[k])) >= 0.9f)) continue;
+            if (!(__builtin_fabsf(dot(Nq, rgb(qa[k]) - Q)) <= b.w)) continue;
             sw += w[k];
             sC = sC + rgb(qh[k]) * w[k];
             s1 += w[k] * qm[k].x;
@@ -784,15 +806,20 @@ hipError_t launch_denoise_variance(uint32_t W, const DnWin &win, const DnImage &
 hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const DnWin &win, const float *vp_prev, float alpha_min,
                                    uint32_t mode, uint32_t prev_y0, uint32_t prev_rows, const float4 *guide,
                                    const float4 *frame, const float4 *accum, const float4 *pguide, const float4 *phist,
-                                   const float2 *pmom, float4 *hist, float2 *mom, unsigned long long *clip, hipStream_t s) {
+                                   const float2 *pmom, float4 *hist, float2 *mom, unsigned long long *clip,
+                                   const DnObj *obj, uint32_t n_obj, hipStream_t s) {
     DnHistory Hs{};
     for (int i = 0; i < 16; ++i) Hs.vp[i] = vp_prev[i];
     Hs.alpha_min = alpha_min;
     Hs.mode = mode;
     Hs.y0 = prev_y0;
     Hs.rows = prev_rows;
-    hipLaunchKernelGGL(dn_temporal, dn_grid(W, win), dim3(kBlock), 0, s, W, H, win, Hs, guide, frame, accum, pguide, phist,
-                       pmom, hist, mom, clip);
+    if (obj)
+        hipLaunchKernelGGL(dn_temporal<true>, dn_grid(W, win), dim3(kBlock), 0, s, W, H, win, Hs, guide, frame, accum, pguide,
+                           phist, pmom, hist, mom, clip, obj, n_obj);
+    else
+        hipLaunchKernelGGL(dn_temporal<false>, dn_grid(W, win), dim3(kBlock), 0, s, W, H, win, Hs, guide, frame, accum, pguide,
+                           phist, pmom, hist, mom, clip, (const DnObj *)nullptr, 0u);
     return hipGetLastError();
 }
 hipError_t launch_denoise_variance_moments(uint32_t W, const DnWin &win, const float4 *hist, const float2 *mom,

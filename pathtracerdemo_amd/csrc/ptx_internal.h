@@ -52,6 +52,13 @@ struct ptx_handle {
     float cull_box = 0.0f, cull_pad = 0.0f, cull_scale = 0.0f;  // Scene::cull_* (build_layout)
     uint32_t layout_key[8] = {0};
     bool layout_valid = false;
+    // build_layout's per-mesh results (geometry and descriptors only), kept on the host for
+    // layout_tables: the root records in SubRoot order (pad: the transmission word, from the
+    // materials), each one's material record (its first word in the scene array), and per mesh
+    // its first root, root count and first triangle
+    std::vector<SubRoot> lay_subs;
+    std::vector<size_t> lay_mat_word;
+    std::vector<uint32_t> lay_mesh_sub_base, lay_mesh_nsub, lay_mesh_tri_base;
     bool scene_loaded = false;
     // frame
     uint32_t uniform[PTX_UNIFORM_WORDS] = {0};
@@ -81,6 +88,10 @@ struct ptx_handle {
     // the history (the motion temporal pass) with d_psurf = that frame's primary-hit surface
     // records, copied on its stream before the next frame's G-buffer may overwrite them
     bool hist_moved = false;
+    // ptx_update_scene changed instances or materials since d_hist's frame: the history serves a frame
+    // of that frame's camera only (the motion pass would read d_psurf's records, made with the old
+    // tables); a moved camera drops it (ptx_set_frame).  Cleared by the next frame (mark_history)
+    bool hist_same_only = false;
     DevBuf d_psurf;
     DevBuf d_qrays, d_qhits;  // staging for ptx_trace and ptx_trace_queries (host arrays)
     DevBuf d_qcnt;            // ptx_trace_queries: the segment counts of its one-round queue
@@ -195,6 +206,10 @@ struct ptx_handle {
     bool dn_hist_valid = false;
     uint32_t dn_camera[19] = {0};
     float dn_vp[16] = {0};
+    // the instance block of the scene array (33 words per instance) as that call saw it, and the
+    // object-motion table of a call that finds it changed (DnObj per instance: dn_temporal<true>)
+    std::vector<uint32_t> dn_insts;
+    DevBuf d_dn_obj;
     // ptx_denoise_bands: a band filters the window of its rows and up to 2^(n+1) halo rows on either
     // side, so the denoiser's buffers of a band handle hold dn_cap_top + band_h + dn_cap_bot rows (the
     // 128 rows of 6 iterations, or what the frame has: row 0 of a buffer is row

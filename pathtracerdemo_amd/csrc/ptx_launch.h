@@ -79,10 +79,18 @@ hipError_t launch_denoise_atrous(uint32_t W, const DnWin &win, uint32_t step, co
 // previous call's guide, history and moment records, which start at row prev_y0 of the W x H frame
 // and hold prev_rows rows; *clip counts the pixels with a candidate past them) -> history {C.rgb, n},
 // moments {m1, m2}; the variance pass on that history, the moments' variance where n >= 4
+// obj (nullptr: no instance changed since the previous call, dn_temporal<false>): n_obj entries, one per
+// instance -- how its pixels find their history (dn_temporal<true>, ptx_denoise.hip)
+struct DnObj {
+    float d[16];    // column-major D = M_prev * Minv_cur: a point of the instance now -> at the previous call
+    uint32_t flag;  // 0 unchanged, 1 moved rigidly (follow D), 2 anything else (no history)
+    uint32_t pad[3];
+};
 hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const DnWin &win, const float *vp_prev, float alpha_min,
                                    uint32_t mode, uint32_t prev_y0, uint32_t prev_rows, const float4 *guide,
                                    const float4 *frame, const float4 *accum, const float4 *pguide, const float4 *phist,
-                                   const float2 *pmom, float4 *hist, float2 *mom, unsigned long long *clip, hipStream_t s);
+                                   const float2 *pmom, float4 *hist, float2 *mom, unsigned long long *clip,
+                                   const DnObj *obj, uint32_t n_obj, hipStream_t s);
 hipError_t launch_denoise_variance_moments(uint32_t W, const DnWin &win, const float4 *hist, const float2 *mom,
                                            const float4 *guide, float4 *out, hipStream_t s);
 // ptx_upsample: the (W / s) x (H / s) image `color_lo` with its guide records, written at W x H under

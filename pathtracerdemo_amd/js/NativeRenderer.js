@@ -181,6 +181,30 @@ class NativeRenderer {
     addon.resetAccumulation(this.Handle);
   }
 
+  /**
+   * Edit instances, materials and lights in place (ptx_update_scene): `world` is the world of
+   * Initialize with instances moved, turned, scaled or switched to another loaded mesh, materials or
+   * lights changed -- the same meshes, counts and offsets, else a RangeError.  Returns the mask of the
+   * blocks that changed (1 instances, 2 materials, 4 lights; 0: nothing to do).  Whole-image handles;
+   * the frame count is the caller's (ResetFrameCount, as on a camera move).
+   */
+  UpdateWorld(world) {
+    if (world && world.InstancesPool instanceof Map) world = SerializeWorldData(world);
+    if (!world || !(world.scene instanceof Uint32Array) || !Array.isArray(world.offsets) || world.offsets.length !== 7) {
+      throw new TypeError('UpdateWorld: expected a World or a serialized world {scene, geometry, accel, offsets[7]}');
+    }
+    if (!this.World) throw new Error('UpdateWorld: Initialize first');
+    if (this.Options.rowBegin || this.Options.rowEnd) throw new Error('UpdateWorld: whole-image renderers only');
+    const old = this.World;
+    const same = world.offsets.every((v, i) => v === old.offsets[i]) && world.instanceCount === old.instanceCount &&
+      world.lightCount === old.lightCount && world.scene.length === old.scene.length &&
+      world.geometry.length === old.geometry.length && world.accel.length === old.accel.length;
+    if (!same) throw new RangeError('UpdateWorld: the edited world has another layout (offsets, counts, geometry or accel length): Initialize uploads it');
+    const mask = addon.updateScene(this.Handle, world.scene);
+    this.World = world;
+    return mask;
+  }
+
   /** Renderer_TEST.Update (:165-206): FrameCount++, then the uniform block. */
   Update() {
     this.FrameCount++;

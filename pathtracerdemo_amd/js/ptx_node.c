@@ -226,6 +226,28 @@ static napi_value js_upload_scene(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* updateScene(h, Uint32Array scene) -> the PTX_EDIT_* mask of the blocks that changed (ptx_update_scene) */
+static napi_value js_update_scene(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    void *p;
+    size_t n, es;
+    napi_typedarray_type t;
+    if (argc < 2 || typed_view(env, argv[1], &p, &n, &es, &t) || t != napi_uint32_array) {
+        napi_throw_type_error(env, NULL, "updateScene(h, scene) takes a Uint32Array");
+        return NULL;
+    }
+    uint32_t mask = 0;
+    int rc = ptx_update_scene(H->h, (const uint32_t *)p, n, &mask);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_update_scene");
+    napi_value r;
+    CHECK_NAPI(env, napi_create_uint32(env, mask, &r));
+    return r;
+}
+
 /* setFrame(h, Uint32Array(33)) */
 static napi_value js_set_frame(napi_env env, napi_callback_info info) {
     size_t argc = 2;
@@ -921,6 +943,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"presentSource", NULL, js_present_source, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"upsample", NULL, js_upsample, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"upsampleTemporal", NULL, js_upsample_temporal, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"updateScene", NULL, js_update_scene, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"phaseUniform", NULL, js_phase_uniform, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
     };
     if (napi_define_properties(env, exports, sizeof later / sizeof later[0], later) != napi_ok) return NULL;

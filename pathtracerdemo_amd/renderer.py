@@ -76,6 +76,28 @@ class Renderer:
                    len(cs.geometry), cs.accel.ctypes.data if len(cs.accel) else None, len(cs.accel))
         self._call("ptx_reset_accumulation", self._h)
 
+    def UpdateScene(self, world: World | CompiledScene) -> int:
+        """Edit instances, materials and lights in place (ptx_update_scene): `world` is the scene of
+        Initialize with instances moved, turned, scaled or switched to another loaded mesh, materials
+        or lights changed -- the same meshes, counts and offsets, else ValueError.  Returns the mask of
+        the blocks that changed (PTX_EDIT_INSTANCES | PTX_EDIT_MATERIALS | PTX_EDIT_LIGHTS; 0: nothing
+        to do).  Kept G-buffers and histories are dropped only as far as the edit needs; the frame
+        count is the caller's (ResetFrameCount, as on a camera move)."""
+        cs = world if isinstance(world, CompiledScene) else serialize_world(world)
+        old = self.compiled
+        if old is None:
+            raise ValueError("UpdateScene: Initialize first")
+        if (cs.offsets != old.offsets or cs.instance_count != old.instance_count or cs.light_count != old.light_count
+                or len(cs.scene) != len(old.scene) or len(cs.geometry) != len(old.geometry)
+                or len(cs.accel) != len(old.accel)):
+            raise ValueError("UpdateScene: the edited scene has another layout (offsets, counts, geometry or accel "
+                             "length): Initialize uploads it")
+        scene = np.ascontiguousarray(cs.scene, dtype=np.uint32)
+        mask = ctypes.c_uint32(0)
+        self._call("ptx_update_scene", self._h, scene.ctypes.data, len(scene), ctypes.byref(mask))
+        self.compiled = cs
+        return int(mask.value)
+
     def Update(self) -> None:
         """Renderer_TEST.Update: FrameCount++ and the 33-word uniform block."""
         self.frame_count += 1
