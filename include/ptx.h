@@ -81,6 +81,7 @@ extern "C" {
                                    (wfinal_one, or wfinal_replay behind a spatial pass that shaded),
                                    so none of their queries reached trace_queue */
 #define PTX_STAT_DENOISE 12  /* launches of the denoiser's kernels (ms with PTX_FLAG_TIME_LAUNCHES) */
+#define PTX_STAT_REFIT 13    /* launches of ptx_update_vertices' kernels (ms with PTX_FLAG_TIME_LAUNCHES) */
 
 /* buffers for ptx_read_buffer / ptx_write_buffer / ptx_device_pointer */
 #define PTX_BUF_GBUFFER 0    /* band_h * W * 4 u32   */
@@ -206,6 +207,49 @@ int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const
 #define PTX_EDIT_MATERIALS 2u
 #define PTX_EDIT_LIGHTS    4u
 int ptx_update_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, uint32_t *changed_out /* NULL ok */);
+/* Deform a loaded mesh in place and refit its BLAS on the GPU: the topology -- index buffer, node order,
+ * words 6 and 7 of every node, the sub-BLAS root offsets -- stays, every box follows the vertices.
+ * `vertices` holds n_vertices records of 8 words, as the geometry array's (position, normal, uv); they
+ * replace records [first_vertex, first_vertex + n_vertices) of mesh `mesh`'s vertex block in the
+ * handle's copy of the geometry array and in the device's.  Then, for that mesh only and on the GPU:
+ * its triangles are derived again (edge form and vertex / normal records, the expressions of the
+ * upload), and its boxes are refitted by the rule of the BLAS builder (pathtracerdemo_amd/scene/bvh.py
+ * refit_blas), in f64 rounded to f32 where written:
+ *   per triangle   mn, mx = per-axis min / max of the three positions; half = (mx - mn) / 2;
+ *                  c = f32(mn + half); h = f32(half + (|mn| + half) * 2^-24);
+ *                  lo = f32(f64(c) - f64(h)), hi = f32(f64(c) + f64(h))
+ *   a leaf         the per-axis min of lo and max of hi over its triangles
+ *   an interior    the union of its two children's boxes
+ * so unchanged vertices give the uploaded boxes bit for bit when the uploaded accel array was built by
+ * that rule, and the 2^-24 widening keeps every grazing hit.  The host then reads the mesh's root
+ * boxes back (32 bytes per sub-mesh, the only readback) and rebuilds the instance table, so the cull
+ * boxes of the instances that name the mesh follow it.  Blocking: it waits for the frames in flight first.
+ * Kept and dropped as by ptx_update_scene's PTX_EDIT_INSTANCES without a switched mesh: triangle numbers
+ * and sub-meshes stay valid, so the reuse / GI history's reservoirs decode; the kept G-buffers, the
+ * surface records and the neighbour summaries are dropped; ptx_denoise, ptx_upsample and their band
+ * and temporal forms are PTX_E_INVALID until a frame or a G-buffer pass has run; the reuse / GI history
+ * serves the next frame only if its camera words are those of the frame that wrote it; the history of
+ * ptx_upsample_temporal is dropped.  The temporal history of ptx_denoise stays and is looked up as for
+ * an unchanged instance: it does not follow vertices, so a deformed surface keeps the history of the
+ * pixels it covered.  The accumulation is not reset.  Band handles and handles with a communicator:
+ * every band / rank makes the same call, nothing is exchanged.
+ * Refused before the GPU is touched, the next frame being the unedited one: PTX_E_INVALID -- a null
+ * handle, a null array with n_vertices > 0, no scene, no frame set or no layout, a range past the
+ * mesh's vertex block (it ends at the next larger vertex offset among the descriptors, or at the index
+ * block), a position word (0..2 of a record) that is not finite; PTX_E_SCENE -- `mesh` is not a loaded
+ * mesh.  n_vertices == 0 is PTX_OK and does nothing.  A HIP error after the upload has begun leaves the
+ * handle without a scene: ptx_upload_scene next.
+ * The launches (one per triangle pass, one per tree height, one for the roots) count in stats slot
+ * PTX_STAT_REFIT, with their time under PTX_FLAG_TIME_LAUNCHES.  Memory: 4 bytes per node pair and 24
+ * per triangle of the largest mesh, allocated with the layout and counted in device_bytes. */
+int ptx_update_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uint32_t n_vertices,
+                        const uint32_t *vertices /* n_vertices * 8 words: the geometry array's vertex records */);
+/* The accel array as the handle traces it now: the uploaded array with words 0..5 of every node
+ * reachable from a sub-mesh root taken from the device's tables.  Before any ptx_update_vertices it is
+ * the uploaded array bit for bit, after one the refit -- what a host without a refit of its own keeps
+ * to serialise the scene.  Blocking; n_accel must be the uploaded length (PTX_E_INVALID otherwise, and
+ * without a scene, a frame or a layout). */
+int ptx_read_accel(ptx_handle *h, uint32_t *accel_out, size_t n_accel);
 int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]);
 /* Run the configured pipeline for the current frame; if rgba_out != NULL copy the band's
  * accumulated RGBA f32 image (band_h * W * 4) into it (blocking). Otherwise asynchronous.

@@ -25,6 +25,7 @@ PTX_STAT_WAVE_TRACE, PTX_STAT_WAVE_LOGIC, PTX_STAT_FRAME = 5, 6, 7  # stats-only
 PTX_STAT_PASS_GROUP = 10
 PTX_STAT_FINAL_FUSED = 11
 PTX_STAT_DENOISE = 12  # launches of the denoiser's kernels
+PTX_STAT_REFIT = 13  # launches of ptx_update_vertices' kernels
 PTX_BUF_GBUFFER, PTX_BUF_RESERVOIR, PTX_BUF_ACCUM, PTX_BUF_COUNTERS, PTX_BUF_RESERVOIR_HIST = 0, 1, 2, 3, 4
 PTX_BUF_DIRECT = 5
 PTX_BUF_DENOISED = 6  # ptx_denoise's output (read-only)
@@ -57,7 +58,8 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_row_census", "ptx_comm_info", "ptx_present", "ptx_present_async", "ptx_present_poll",
             "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands",
             "ptx_upsample", "ptx_upsample_bands", "ptx_phase_uniform", "ptx_upsample_temporal",
-            "ptx_trace_queries", "ptx_upsample_temporal_bands", "ptx_update_scene"]
+            "ptx_trace_queries", "ptx_upsample_temporal_bands", "ptx_update_scene", "ptx_update_vertices",
+            "ptx_read_accel"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -127,6 +129,8 @@ def load(path: str = LIB_PATH):
     lib.ptx_create.argtypes = [ctypes.POINTER(PtxConfig), ctypes.POINTER(H)]
     lib.ptx_upload_scene.argtypes = [H, P, ctypes.c_size_t, P, ctypes.c_size_t, P, ctypes.c_size_t]
     lib.ptx_update_scene.argtypes = [H, P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]
+    lib.ptx_update_vertices.argtypes = [H, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]
+    lib.ptx_read_accel.argtypes = [H, P, ctypes.c_size_t]
     lib.ptx_set_frame.argtypes = [H, P]
     lib.ptx_render.argtypes = [H, P]
     lib.ptx_run_pass.argtypes = [H, ctypes.c_int]

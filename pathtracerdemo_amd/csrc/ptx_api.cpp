@@ -366,6 +366,11 @@ int build_layout(ptx_handle *h) {
     std::vector<size_t> mat_word;  // per sub-mesh, in SubRoot order: its material record in the scene array
     std::vector<float> tverts;  // 20 floats per triangle, triangle-table order (Scene::tverts)
     std::vector<uint32_t> mesh_sub_base(n_mesh), mesh_nsub(n_mesh), mesh_tri_base(n_mesh);
+    // for ptx_update_vertices / ptx_read_accel (ptx_handle::lay_mesh_ntris ...)
+    std::vector<uint32_t> mesh_ntris(n_mesh), mesh_vertex(n_mesh), mesh_nverts(n_mesh), mesh_node_base(n_mesh), mesh_nnodes(n_mesh);
+    std::vector<std::vector<uint32_t>> mesh_levels(n_mesh);
+    std::vector<uint32_t> order, pair_words, root_word;
+    if (A.size() > 0xffffffffull) return fail(h, PTX_E_SCENE, "accel array too long");
     uint32_t max_depth = 0;
 
     for (uint32_t m = 0; m < n_mesh; ++m) {
@@ -374,6 +379,16 @@ int build_layout(ptx_handle *h) {
         mesh_sub_base[m] = (uint32_t)subs.size();
         mesh_nsub[m] = nsub;
         mesh_tri_base[m] = (uint32_t)(tris.size() / 12);
+        mesh_node_base[m] = (uint32_t)nodes.size();
+        mesh_vertex[m] = off_vertex;
+        {   // the vertex block ends at the next larger vertex offset among the descriptors, or at the index block
+            uint32_t end = off_index;
+            for (uint32_t o = 0; o < n_mesh; ++o) {
+                const uint32_t v = S[off_desc + STRIDE_DESCRIPTOR * o];
+                if (v > off_vertex && v < end) end = v;
+            }
+            mesh_nverts[m] = end > off_vertex ? (end - off_vertex) / STRIDE_VERTEX : 0u;
+        }
         // GetMaterial (SH/PT_1_InitPass.wgsl:285-314) per sub-mesh: material d[2] + 15*sub.  A record
         // past the scene buffer reads as zeros (WebGPU's robust buffer access would clamp or zero).
         for (uint32_t s = 0; s < nsub; ++s) mat_word.push_back((size_t)off_mat + d[2] + (size_t)STRIDE_MATERIAL * s);
@@ -422,6 +437,7 @@ int build_layout(ptx_handle *h) {
             for (int k = 0; k < 3; ++k) { axis[k][0] = as_f32(A[base + k]); axis[k][1] = as_f32(A[base + 3 + k]); }
             if (int rc = ref_of(0u, r.ref)) return rc;
             subs.push_back(r);
+            root_word.push_back(base);
             for (uint32_t n : interior) {
                 size_t w = (size_t)base + 8u * n;
                 uint32_t L = n + 1u, R = A[w + 6] / 8u;
@@ -435,8 +451,35 @@ int build_layout(ptx_handle *h) {
                 if (int rc = ref_of(L, np.lref)) return rc;
                 if (int rc = ref_of(R, np.rref)) return rc;
                 nodes.push_back(np);
+                pair_words.push_back((uint32_t)wl);
+                pair_words.push_back((uint32_t)wr);
             }
         }
+        // the mesh's pairs by height: a pair's interior children were numbered after it (the walk
+        // above), so the last pair first finds every child's height known
+        {
+            const uint32_t nb = mesh_node_base[m], nn = (uint32_t)nodes.size() - nb;
+            mesh_nnodes[m] = nn;
+            std::vector<uint32_t> height(nn, 0u);
+            uint32_t top = 0;
+            for (uint32_t i = nn; i-- > 0;) {
+                for (const uint32_t ref : {nodes[nb + i].lref, nodes[nb + i].rref}) {
+                    if (ref & LEAF_BIT) continue;
+                    if (ref <= nb + i || ref >= nb + nn) return fail(h, PTX_E_SCENE, "BLAS node order: a child before its parent");
+                    height[i] = std::max(height[i], height[ref - nb] + 1u);
+                }
+                top = std::max(top, height[i]);
+            }
+            auto &lv = mesh_levels[m];
+            lv.assign(nn ? top + 2u : 1u, 0u);
+            for (uint32_t i = 0; i < nn; ++i) lv[height[i] + 1u] += 1u;
+            lv[0] = (uint32_t)order.size();
+            for (size_t k = 1; k < lv.size(); ++k) lv[k] += lv[k - 1];
+            std::vector<uint32_t> at(lv.begin(), lv.end() - 1);
+            order.resize(order.size() + nn);
+            for (uint32_t i = 0; i < nn; ++i) order[at[height[i]]++] = nb + i;
+        }
+        mesh_ntris[m] = mesh_tris;
         // edge-form triangles in index (leaf) order, local space
         for (uint32_t prim = 0; prim < mesh_tris; ++prim) {
             size_t ii = (size_t)off_index + off_idx + 3u * prim;
@@ -471,6 +514,20 @@ int build_layout(ptx_handle *h) {
     h->lay_mesh_sub_base = std::move(mesh_sub_base);
     h->lay_mesh_nsub = std::move(mesh_nsub);
     h->lay_mesh_tri_base = std::move(mesh_tri_base);
+    h->lay_mesh_ntris = std::move(mesh_ntris);
+    h->lay_mesh_vertex = std::move(mesh_vertex);
+    h->lay_mesh_nverts = std::move(mesh_nverts);
+    h->lay_mesh_node_base = std::move(mesh_node_base);
+    h->lay_mesh_nnodes = std::move(mesh_nnodes);
+    h->lay_mesh_levels = std::move(mesh_levels);
+    h->lay_pair_words = std::move(pair_words);
+    h->lay_root_word = std::move(root_word);
+    if (int rc = upload(h, h->d_refit_order, order.data(), order.size() * sizeof(uint32_t))) return rc;
+    {
+        uint32_t most = 1;
+        for (const uint32_t t : h->lay_mesh_ntris) most = std::max(most, t);
+        if (int rc = alloc_buf(h, h->d_refit_box, (size_t)most * 6u * sizeof(float))) return rc;
+    }
     h->n_inst = n_inst;
     if (int rc = layout_tables(h, true, true)) return rc;
     if (int rc = upload(h, h->d_tris, tris.data(), tris.size() * sizeof(float))) return rc;
@@ -1642,15 +1699,19 @@ static DnWin denoise_stage_rows(uint32_t y0, uint32_t rows, uint32_t top, uint32
     return w;
 }
 
-// One launch with its event pair, unless an earlier one of the call failed.
+// One launch with its event pair in stats slot `slot`, unless an earlier one of the call failed.
 template <class F>
-static hipError_t denoise_timed(ptx_handle *h, hipStream_t st, hipError_t le_in, F &&launch) {
+static hipError_t slot_timed(ptx_handle *h, int slot, hipStream_t st, hipError_t le_in, F &&launch) {
     if (le_in != hipSuccess) return le_in;
-    TimedLaunch *t = event_begin(h, PTX_STAT_DENOISE, st);
+    TimedLaunch *t = event_begin(h, slot, st);
     const hipError_t le = launch();
     event_end(t, st);
-    if (!t && le == hipSuccess) h->launches[PTX_STAT_DENOISE] += 1;  // (untimed handles: the count alone)
+    if (!t && le == hipSuccess) h->launches[slot] += 1;  // (untimed handles: the count alone)
     return le;
+}
+template <class F>
+static hipError_t denoise_timed(ptx_handle *h, hipStream_t st, hipError_t le_in, F &&launch) {
+    return slot_timed(h, PTX_STAT_DENOISE, st, le_in, launch);
 }
 
 // The window's row 0 in the denoiser's buffers (they start dn_cap_top rows above the band).
@@ -2215,6 +2276,109 @@ int ptx_update_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, uint3
     return PTX_OK;
 }
 
+int ptx_update_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uint32_t n_vertices, const uint32_t *vertices) {
+    if (!h) return PTX_E_INVALID;
+    if (!h->scene_loaded || !h->frame_set || !h->layout_valid)
+        return fail(h, PTX_E_INVALID, "ptx_update_vertices: upload a scene and set a frame first");
+    const uint32_t n_mesh = (uint32_t)h->lay_mesh_nsub.size();
+    if (mesh >= n_mesh) return fail(h, PTX_E_SCENE, "ptx_update_vertices: mesh %u of %u", mesh, n_mesh);
+    if ((uint64_t)first_vertex + n_vertices > h->lay_mesh_nverts[mesh])
+        return fail(h, PTX_E_INVALID, "ptx_update_vertices: vertices [%u, %llu) of mesh %u, which has %u", first_vertex,
+                    (unsigned long long)first_vertex + n_vertices, mesh, h->lay_mesh_nverts[mesh]);
+    if (n_vertices == 0u) return PTX_OK;
+    if (!vertices) return fail(h, PTX_E_INVALID, "ptx_update_vertices: null vertex array");
+    for (uint32_t v = 0; v < n_vertices; ++v)
+        for (uint32_t k = 0; k < 3u; ++k)
+            if ((vertices[(size_t)STRIDE_VERTEX * v + k] & 0x7f800000u) == 0x7f800000u)
+                return fail(h, PTX_E_INVALID, "ptx_update_vertices: vertex %u: position word %u is not finite", first_vertex + v, k);
+    const size_t word0 = (size_t)h->lay_mesh_vertex[mesh] + (size_t)STRIDE_VERTEX * first_vertex;
+    const size_t n_words = (size_t)STRIDE_VERTEX * n_vertices;
+    if (word0 + n_words > h->geometry.size() || h->d_geometry.bytes < (word0 + n_words) * 4u)
+        return fail(h, PTX_E_INVALID, "ptx_update_vertices: the mesh's vertex block lies past the geometry array");
+    HIP_CHECK(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;  // frames in flight still read the geometry and the tables
+    // From here on the handle changes.  A HIP error part-way would leave the device's tables between the
+    // two shapes: the handle then holds no scene until the next ptx_upload_scene.
+    const hipStream_t st = h->cur().stream;
+    std::memcpy(h->geometry.data() + word0, vertices, n_words * 4u);
+    hipError_t le = copy_sync(h, (uint32_t *)h->d_geometry.p + word0, vertices, n_words * 4u, hipMemcpyHostToDevice);
+    const uint32_t *d = h->scene.data() + h->uniform[U_OFF_DESC] + STRIDE_DESCRIPTOR * mesh;
+    RefitMesh m{};
+    m.G = (const uint32_t *)h->d_geometry.p;
+    m.tris = (float4 *)h->d_tris.p;
+    m.tverts = (float4 *)h->d_tverts.p;
+    m.nodes = (NodePair *)h->d_nodes.p;
+    m.subs = (SubRoot *)h->d_subs.p;
+    m.box = (float2 *)h->d_refit_box.p;
+    m.order = (const uint32_t *)h->d_refit_order.p;
+    m.vertex = h->lay_mesh_vertex[mesh];
+    m.index = h->uniform[U_OFF_INDEX] + d[1];
+    m.tri_base = h->lay_mesh_tri_base[mesh];
+    m.n_tris = h->lay_mesh_ntris[mesh];
+    m.sub_base = h->lay_mesh_sub_base[mesh];
+    m.n_subs = h->lay_mesh_nsub[mesh];
+    le = slot_timed(h, PTX_STAT_REFIT, st, le, [&] { return launch_refit_tris(m, st); });
+    const auto &lv = h->lay_mesh_levels[mesh];  // lowest height first: a pair's interior children are lower
+    for (size_t k = 0; k + 1 < lv.size(); ++k)
+        le = slot_timed(h, PTX_STAT_REFIT, st, le, [&] { return launch_refit_level(m, lv[k], lv[k + 1] - lv[k], st); });
+    le = slot_timed(h, PTX_STAT_REFIT, st, le, [&] { return launch_refit_roots(m, st); });
+    int rc = le == hipSuccess ? PTX_OK : fail(h, PTX_E_HIP, "ptx_update_vertices: %s", hipGetErrorString(le));
+    // the mesh's root boxes (the only readback): the instance cull boxes are made from them
+    if (rc == PTX_OK && m.n_subs)
+        rc = read_to_host(h, h->lay_subs.data() + m.sub_base, m.subs + m.sub_base, (size_t)m.n_subs * sizeof(SubRoot));
+    if (rc == PTX_OK) rc = layout_tables(h, true, false);
+    if (rc != PTX_OK) {
+        h->scene_loaded = h->layout_valid = false;
+        h->hist_valid = h->dn_hist_valid = h->ut_valid = h->drawn = h->rendered = false;
+        for (auto &c : h->ctx) c.surf_valid = c.init_state_valid = c.nbr_valid = false;
+        gbuf_key_drop_all(h);
+        return rc;
+    }
+    // kept and dropped as by an instance edit without a switched mesh (ptx_update_scene): triangle numbers
+    // and sub-meshes stay valid, so the history's reservoirs decode; its frame's surface records were made
+    // from the old shape, so it serves that frame's camera alone
+    gbuf_key_drop_all(h);
+    for (auto &c : h->ctx) c.surf_valid = c.init_state_valid = c.nbr_valid = false;
+    h->drawn = h->rendered = false;
+    h->hist_same_only = true;
+    if (h->hist_moved) h->hist_valid = false;
+    h->ut_valid = false;  // (ptx_upsample_temporal does not follow vertices; neither does ptx_denoise's temporal mode,
+                          //  whose history stays and is looked up as for an unchanged instance)
+    return PTX_OK;
+}
+
+int ptx_read_accel(ptx_handle *h, uint32_t *accel_out, size_t n_accel) {
+    if (!h) return PTX_E_INVALID;
+    if (!h->scene_loaded || !h->frame_set || !h->layout_valid)
+        return fail(h, PTX_E_INVALID, "ptx_read_accel: upload a scene and set a frame first");
+    if (n_accel != h->accel.size() || (!accel_out && n_accel))
+        return fail(h, PTX_E_INVALID, "ptx_read_accel: %zu words, the uploaded array has %zu", n_accel, h->accel.size());
+    HIP_CHECK(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;
+    const size_t n_roots = h->lay_root_word.size(), n_pairs = h->lay_pair_words.size() / 2u;
+    std::vector<SubRoot> subs(n_roots);
+    std::vector<NodePair> pairs(n_pairs);
+    if (n_roots)
+        if (int rc = read_to_host(h, subs.data(), h->d_subs.p, n_roots * sizeof(SubRoot))) return rc;
+    if (n_pairs)
+        if (int rc = read_to_host(h, pairs.data(), h->d_nodes.p, n_pairs * sizeof(NodePair))) return rc;
+    if (n_accel) std::memcpy(accel_out, h->accel.data(), n_accel * 4u);
+    auto put = [&](size_t w, const float *mn_mx) { std::memcpy(accel_out + w, mn_mx, 24); };
+    for (size_t s = 0; s < n_roots; ++s) {
+        const SubRoot &r = subs[s];
+        const float b[6] = {r.x[0], r.y[0], r.z[0], r.x[1], r.y[1], r.z[1]};
+        put(h->lay_root_word[s], b);
+    }
+    for (size_t p = 0; p < n_pairs; ++p) {
+        const NodePair &q = pairs[p];
+        const float l[6] = {q.x[0], q.y[0], q.z[0], q.x[2], q.y[2], q.z[2]};
+        const float r[6] = {q.x[1], q.y[1], q.z[1], q.x[3], q.y[3], q.z[3]};
+        put(h->lay_pair_words[2u * p], l);
+        put(h->lay_pair_words[2u * p + 1u], r);
+    }
+    return PTX_OK;
+}
+
 int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]) {
     if (!h || !uniform) return PTX_E_INVALID;
     HIP_CHECK(h, hipSetDevice(h->device));  // handles of one process may sit on several GPUs
@@ -2431,7 +2595,7 @@ int ptx_get_stats(ptx_handle *h, ptx_stats *out) {
                         h->d_denoised.bytes + h->d_frame_color.bytes + h->d_dn_guide_prev.bytes + h->d_dn_hist[0].bytes +
                         h->d_dn_hist[1].bytes + h->d_dn_mom[0].bytes + h->d_dn_mom[1].bytes + h->d_dn_halo_g.bytes +
                         h->d_dn_halo_c.bytes + h->d_dn_obj.bytes + h->d_up_halo.bytes + h->d_ut_guide[0].bytes + h->d_ut_guide[1].bytes +
-                        h->d_ut_hist[0].bytes + h->d_ut_hist[1].bytes;
+                        h->d_ut_hist[0].bytes + h->d_ut_hist[1].bytes + h->d_refit_order.bytes + h->d_refit_box.bytes;
     return PTX_OK;
 }
 
@@ -2832,7 +2996,7 @@ int ptx_destroy(ptx_handle *h) {
                       &h->d_jstate, &h->d_jres, &h->d_replay, &h->d_psurf, &h->d_census, &h->d_wgt, &h->d_dn_guide, &h->d_dn_work,
                       &h->d_denoised, &h->d_frame_color, &h->d_dn_guide_prev, &h->d_dn_hist[0], &h->d_dn_hist[1], &h->d_dn_mom[0],
                       &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_dn_obj, &h->d_up_halo, &h->d_ut_guide[0], &h->d_ut_guide[1],
-                      &h->d_ut_hist[0], &h->d_ut_hist[1]})
+                      &h->d_ut_hist[0], &h->d_ut_hist[1], &h->d_refit_order, &h->d_refit_box})
         free_buf(*b);
     for (auto &c : h->ctx) {
         for (DevBuf *b : {&c.gbuf, &c.res, &c.direct, &c.nbr, &c.tjstate, &c.tjres, &c.surf, &c.wstate, &c.wrays, &c.wres[0],

@@ -59,6 +59,19 @@ struct ptx_handle {
     std::vector<SubRoot> lay_subs;
     std::vector<size_t> lay_mat_word;
     std::vector<uint32_t> lay_mesh_sub_base, lay_mesh_nsub, lay_mesh_tri_base;
+    // ... and for ptx_update_vertices / ptx_read_accel, from the same walk.  Per mesh: its triangle
+    // count, its vertex records in the geometry array (first word, count: the block ends at the next
+    // larger vertex offset among the descriptors, or at the index block), its node pairs (first, count)
+    // and, per tree height, where that height's pairs begin in the order table (heights + 1 entries;
+    // height 0: both children are leaves, else 1 + the highest interior child's; the table itself --
+    // every mesh's pairs by height -- lives on the device alone: d_refit_order).  Per pair the accel words
+    // of its two children's nodes, per root record its node's: where ptx_read_accel writes the device's boxes.
+    std::vector<uint32_t> lay_mesh_ntris, lay_mesh_vertex, lay_mesh_nverts, lay_mesh_node_base, lay_mesh_nnodes;
+    std::vector<std::vector<uint32_t>> lay_mesh_levels;
+    std::vector<uint32_t> lay_pair_words, lay_root_word;
+    // the order table on the device (4 B per pair) and the triangle boxes of one mesh's refit (24 B per
+    // triangle of the largest mesh): allocated with the layout
+    DevBuf d_refit_order, d_refit_box;
     bool scene_loaded = false;
     // frame
     uint32_t uniform[PTX_UNIFORM_WORDS] = {0};

@@ -129,6 +129,27 @@ hipError_t launch_denoise_upsample_temporal_win(uint32_t s, uint32_t W, uint32_t
                                                 const float4 *halo_lo, const float4 *guide_prev, const float4 *hist_prev,
                                                 float4 *hist, float4 *out, hipStream_t st);
 
+// ptx_update_vertices (ptx_refit.hip): one mesh's derived tables from its new vertices.  The ranges of
+// the mesh in the tables, from build_layout (ptx_handle::lay_mesh_*); G, tris, tverts, nodes and subs
+// are the whole tables, `box` the scratch {lo.xyz, hi.xyz} per triangle of the mesh, `order` the
+// mesh's pairs by height (global pair indices).
+struct RefitMesh {
+    const uint32_t *G;
+    float4 *tris, *tverts;
+    NodePair *nodes;
+    SubRoot *subs;
+    float2 *box;            // 3 float2 per triangle: {lo.x, lo.y}, {lo.z, hi.x}, {hi.y, hi.z}
+    const uint32_t *order;
+    uint32_t vertex, index;  // first word in G of the mesh's vertex records / of its index buffer
+    uint32_t tri_base, n_tris, sub_base, n_subs;
+};
+// the triangle records (edge form, vertex / normal) and boxes of the mesh's n_tris triangles
+hipError_t launch_refit_tris(const RefitMesh &m, hipStream_t s);
+// one height of the tree: the pairs order[first, first + n), whose interior children are lower
+hipError_t launch_refit_level(const RefitMesh &m, uint32_t first, uint32_t n, hipStream_t s);
+// the root records' boxes, after the last height
+hipError_t launch_refit_roots(const RefitMesh &m, hipStream_t s);
+
 // closest-hit queries for a ray array (ptx_kernels.hip)
 hipError_t launch_trace_rays(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,
                              uint32_t stack_depth, hipStream_t s);

@@ -205,6 +205,42 @@ class NativeRenderer {
     return mask;
   }
 
+  /**
+   * Deform a loaded mesh in place (ptx_update_vertices): `records` is a Uint32Array of 8 words per
+   * vertex -- position, normal, uv as in the geometry array -- that replace the vertex records
+   * [first, first + records.length / 8) of mesh `mesh`.  The library derives the mesh's triangles again
+   * and refits its BLAS on the GPU, the topology kept; histories are kept and dropped as by an
+   * instance edit.  this.World is afterwards what the handle renders: its geometry rewritten, its
+   * accel ReadAccel()'s (new arrays; the world passed to Initialize is not written).  After Update()
+   * (the handle needs a frame set); band renderers make the same call on every band; the frame count
+   * is the caller's.  A refused call throws and changes nothing.
+   */
+  UpdateVertices(mesh, first, records) {
+    if (!Number.isInteger(mesh) || mesh < 0 || !Number.isInteger(first) || first < 0 || !(records instanceof Uint32Array) ||
+        records.length % 8 !== 0) {
+      throw new TypeError('UpdateVertices: expected (mesh, first, Uint32Array of 8 words per vertex)');
+    }
+    if (!this.World) throw new Error('UpdateVertices: Initialize first');
+    addon.updateVertices(this.Handle, mesh, first, records);
+    if (records.length === 0) return;
+    const w = this.World;
+    // the mesh's vertex records: word 0 of its descriptor (6 words per mesh at offsets[0]) is their first word
+    const geometry = new Uint32Array(w.geometry);
+    geometry.set(records, w.scene[w.offsets[0] + 6 * mesh] + 8 * first);
+    this.World = Object.assign({}, w, { geometry, accel: this.ReadAccel() });
+  }
+
+  /**
+   * The accel array as the handle traces it now (ptx_read_accel): the uploaded one with every
+   * reachable node's box from the device's tables -- after UpdateVertices, the refit.  Blocking.
+   */
+  ReadAccel() {
+    if (!this.World) throw new Error('ReadAccel: Initialize first');
+    const out = new Uint32Array(this.World.accel.length);
+    addon.readAccel(this.Handle, out);
+    return out;
+  }
+
   /** Renderer_TEST.Update (:165-206): FrameCount++, then the uniform block. */
   Update() {
     this.FrameCount++;

@@ -248,6 +248,46 @@ static napi_value js_update_scene(napi_env env, napi_callback_info info) {
     return r;
 }
 
+/* updateVertices(h, mesh, first, Uint32Array records): 8 words per vertex, as the geometry array's (ptx_update_vertices) */
+static napi_value js_update_vertices(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    uint32_t mesh = 0, first = 0;
+    void *p;
+    size_t n, es;
+    napi_typedarray_type t;
+    if (argc < 4 || napi_get_value_uint32(env, argv[1], &mesh) != napi_ok || napi_get_value_uint32(env, argv[2], &first) != napi_ok ||
+        typed_view(env, argv[3], &p, &n, &es, &t) || t != napi_uint32_array || n % 8u != 0 || n / 8u > 0xffffffffu) {
+        napi_throw_type_error(env, NULL, "updateVertices(h, mesh, first, records) takes two integers and a Uint32Array of 8 words per vertex");
+        return NULL;
+    }
+    int rc = ptx_update_vertices(H->h, mesh, first, (uint32_t)(n / 8u), (const uint32_t *)p);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_update_vertices");
+    return NULL;
+}
+
+/* readAccel(h, Uint32Array out): the accel array as the handle traces it now, into `out` (ptx_read_accel) */
+static napi_value js_read_accel(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    void *p;
+    size_t n, es;
+    napi_typedarray_type t;
+    if (argc < 2 || typed_view(env, argv[1], &p, &n, &es, &t) || t != napi_uint32_array) {
+        napi_throw_type_error(env, NULL, "readAccel(h, out) takes a Uint32Array");
+        return NULL;
+    }
+    int rc = ptx_read_accel(H->h, (uint32_t *)p, n);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_read_accel");
+    return NULL;
+}
+
 /* setFrame(h, Uint32Array(33)) */
 static napi_value js_set_frame(napi_env env, napi_callback_info info) {
     size_t argc = 2;
@@ -944,6 +984,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"upsample", NULL, js_upsample, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"upsampleTemporal", NULL, js_upsample_temporal, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"updateScene", NULL, js_update_scene, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"updateVertices", NULL, js_update_vertices, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"readAccel", NULL, js_read_accel, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"phaseUniform", NULL, js_phase_uniform, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
     };
     if (napi_define_properties(env, exports, sizeof later / sizeof later[0], later) != napi_ok) return NULL;

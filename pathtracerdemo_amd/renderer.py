@@ -11,6 +11,7 @@ build-defined temporal + spatial reuse passes between PT_1 and PT_4 (DESIGN.md Â
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
 import numpy as np
 
@@ -97,6 +98,44 @@ class Renderer:
         self._call("ptx_update_scene", self._h, scene.ctypes.data, len(scene), ctypes.byref(mask))
         self.compiled = cs
         return int(mask.value)
+
+    def UpdateVertices(self, mesh: int, positions, normals=None, first: int = 0) -> None:
+        """Deform mesh `mesh` in place (ptx_update_vertices): `positions` (n, 3) f32 replace the positions
+        of its vertices [first, first + n), `normals` (optional, (n, 3)) their normals; the uv words stay.
+        The library derives the mesh's triangles again and refits its BLAS on the GPU, the topology
+        kept; histories are kept and dropped as by an instance edit (include/ptx.h).  `compiled` is
+        afterwards what the handle renders: the geometry array rewritten, the accel array read_accel()'s.
+        A refused call (a range past the mesh, a position that is not finite: PtxError) changes nothing."""
+        from .scene.world import STRIDE_VERTEX, mesh_blocks
+        cs = self.compiled
+        if cs is None or self.uniform is None:
+            raise ValueError("UpdateVertices: Initialize and Update first")
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        b = mesh_blocks(cs, int(mesh))
+        n_vert = (b["vertex_end"] - b["vertex"]) // STRIDE_VERTEX
+        if first < 0 or first + len(pos) > n_vert:
+            raise ValueError(f"UpdateVertices: vertices [{first}, {first + len(pos)}) of mesh {mesh}, which has {n_vert}")
+        w0 = b["vertex"] + STRIDE_VERTEX * first
+        rec = np.array(cs.geometry[w0:w0 + STRIDE_VERTEX * len(pos)], dtype=np.uint32).reshape(len(pos), STRIDE_VERTEX)
+        rec[:, 0:3] = pos.view(np.uint32)
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+            if len(nrm) != len(pos):
+                raise ValueError("UpdateVertices: one normal per position")
+            rec[:, 3:6] = nrm.view(np.uint32)
+        self._call("ptx_update_vertices", self._h, int(mesh), int(first), len(rec), rec.ctypes.data if len(rec) else None)
+        if not len(rec):
+            return
+        geometry = np.array(cs.geometry, dtype=np.uint32)
+        geometry[w0:w0 + rec.size] = rec.reshape(-1)
+        self.compiled = dataclasses.replace(cs, geometry=geometry, accel=self.read_accel())
+
+    def read_accel(self) -> np.ndarray:
+        """The accel array as the handle traces it now (ptx_read_accel): the uploaded one, the boxes of
+        every reachable node from the device's tables -- after UpdateVertices, the refit."""
+        out = np.zeros(len(self.compiled.accel), dtype=np.uint32)
+        self._call("ptx_read_accel", self._h, out.ctypes.data if len(out) else None, len(out))
+        return out
 
     def Update(self) -> None:
         """Renderer_TEST.Update: FrameCount++ and the 33-word uniform block."""

@@ -171,3 +171,37 @@ def build_blas(positions: np.ndarray, indices: np.ndarray, groups: list[tuple[in
                 buf[i, 7] = n[3]
         roots.append(buf.reshape(-1))
     return roots, idx3.reshape(-1).astype(np.uint32), b.max_depth_seen
+
+
+def triangle_boxes(positions: np.ndarray, indices: np.ndarray):
+    """(T,3) f32 lo and hi per triangle, as the builder sees a triangle: the centre / half-extent record
+    of _triangle_bounds (half widened by 2^-24), then lo = f32(c - h), hi = f32(c + h) in f64."""
+    tb = _triangle_bounds(np.asarray(positions, dtype=np.float32), np.asarray(indices, dtype=np.uint32))
+    c = tb[:, :, 0].astype(np.float64)
+    h = tb[:, :, 1].astype(np.float64)
+    return (c - h).astype(np.float32), (c + h).astype(np.float32)
+
+
+def refit_blas(positions: np.ndarray, indices: np.ndarray, roots: list) -> list:
+    """Refit the roots build_blas made to new vertex positions, the topology kept: a leaf's box is the
+    min / max of its triangles' boxes (triangle_boxes: the builder's rule, so unchanged positions give the
+    built arrays bit for bit), an interior node's box the union of its two children's (rounding commutes
+    with min / max, so bottom-up equals the builder's top-down bounds).  Words 6 and 7 of every node, the
+    index buffer and the node order stay.  Returns new node arrays; the inputs are not written."""
+    lo, hi = triangle_boxes(positions, indices)
+    out = []
+    for root in roots:
+        buf = np.array(root, dtype=np.uint32).reshape(-1, 8)
+        box = buf[:, 0:6].view(np.float32)  # (a view: written in place)
+        # children lie behind their parent (left = node + 1, right = w6 / 8 > node): last node first
+        for n in range(len(buf) - 1, -1, -1):
+            if buf[n, 7] & LEAF_FLAG:
+                first, count = int(buf[n, 6]), int(buf[n, 7] & 0xFFFF)
+                box[n, 0:3] = lo[first:first + count].min(axis=0)
+                box[n, 3:6] = hi[first:first + count].max(axis=0)
+            else:
+                l, r = n + 1, int(buf[n, 6]) // 8
+                box[n, 0:3] = np.minimum(box[l, 0:3], box[r, 0:3])
+                box[n, 3:6] = np.maximum(box[l, 3:6], box[r, 3:6])
+        out.append(buf.reshape(-1))
+    return out

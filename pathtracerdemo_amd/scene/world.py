@@ -356,6 +356,60 @@ def serialize_world(world: World) -> CompiledScene:
                          triangle_count=sum(len(m.indices) // 3 for m in meshes))
 
 
+def _block_end(starts, start: int, limit: int) -> int:
+    """Where the block that begins at `start` ends: the next larger start among `starts`, or `limit`."""
+    return min([int(s) for s in starts if int(s) > start], default=limit)
+
+
+def mesh_blocks(cs: CompiledScene, mesh: int) -> dict:
+    """Where mesh `mesh` of a compiled scene lies: its vertex records ([vertex, vertex_end) words of
+    `geometry`), its index block, and per sub-mesh the [begin, end) words of its BLAS root in `accel`."""
+    o = cs.offsets
+    n_mesh = (o["material"] - o["mesh_descriptor"]) // STRIDE_DESCRIPTOR
+    if not 0 <= mesh < n_mesh:
+        raise ValueError(f"mesh {mesh} of {n_mesh}")
+    desc = cs.scene[o["mesh_descriptor"]:o["material"]].reshape(n_mesh, STRIDE_DESCRIPTOR)
+    d = desc[mesh]
+    vertex, index, blas = int(d[0]), o["index"] + int(d[1]), o["blas"] + int(d[4])
+    vertex_end = _block_end(desc[:, 0], vertex, o["index"])
+    index_end = _block_end(o["index"] + desc[:, 1].astype(np.int64), index, o["sub_blas_root"])
+    blas_end = _block_end(o["blas"] + desc[:, 4].astype(np.int64), blas, len(cs.accel))
+    r0 = o["sub_blas_root"] + int(d[3])
+    starts = [blas + int(w) for w in cs.geometry[r0:r0 + int(d[5])]]
+    roots = [(s, _block_end(starts, s, blas_end)) for s in starts]
+    return dict(vertex=vertex, vertex_end=vertex_end, index=index, index_end=index_end, roots=roots)
+
+
+def refit_mesh(cs: CompiledScene, mesh: int, positions, normals=None, first: int = 0) -> CompiledScene:
+    """The compiled scene with mesh `mesh` deformed: `positions` (n, 3) f32 replace words 0..2 of its vertex
+    records [first, first + n) in `geometry`, `normals` (optional) words 3..5, the uv words stay; its BLAS
+    nodes in `accel` are refitted to the new positions (bvh.refit_blas: the builder's bounds rule on the
+    kept topology).  The scene array, offsets and counts are the same objects; nothing of `cs` is written."""
+    from .bvh import refit_blas
+    b = mesh_blocks(cs, mesh)
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    n_vert = (b["vertex_end"] - b["vertex"]) // STRIDE_VERTEX
+    if first < 0 or first + len(pos) > n_vert:
+        raise ValueError(f"vertices [{first}, {first + len(pos)}) of mesh {mesh}, which has {n_vert}")
+    if not np.isfinite(pos).all():
+        raise ValueError("positions must be finite")
+    geometry = np.array(cs.geometry, dtype=np.uint32)
+    rec = geometry[b["vertex"]:b["vertex_end"]].reshape(n_vert, STRIDE_VERTEX)  # (a view of the copy)
+    rec[first:first + len(pos), 0:3] = pos.view(np.uint32)
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if len(nrm) != len(pos):
+            raise ValueError("one normal per position")
+        rec[first:first + len(pos), 3:6] = nrm.view(np.uint32)
+    accel = np.array(cs.accel, dtype=np.uint32)
+    new = refit_blas(rec[:, 0:3].copy().view(np.float32), geometry[b["index"]:b["index_end"]],
+                     [accel[s:e] for s, e in b["roots"]])
+    for (s, e), r in zip(b["roots"], new):
+        accel[s:e] = r
+    import dataclasses
+    return dataclasses.replace(cs, geometry=geometry, accel=accel)
+
+
 def load_scene_json(name: str) -> dict:
     with open(os.path.join(SCENE_DIR, name + ".json")) as fh:
         return json.load(fh)
