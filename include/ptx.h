@@ -81,7 +81,8 @@ extern "C" {
                                    (wfinal_one, or wfinal_replay behind a spatial pass that shaded),
                                    so none of their queries reached trace_queue */
 #define PTX_STAT_DENOISE 12  /* launches of the denoiser's kernels (ms with PTX_FLAG_TIME_LAUNCHES) */
-#define PTX_STAT_REFIT 13    /* launches of ptx_update_vertices' kernels (ms with PTX_FLAG_TIME_LAUNCHES) */
+#define PTX_STAT_REFIT 13    /* launches of ptx_update_vertices' and ptx_skin_vertices' kernels (ms with
+                                PTX_FLAG_TIME_LAUNCHES) */
 
 /* buffers for ptx_read_buffer / ptx_write_buffer / ptx_device_pointer */
 #define PTX_BUF_GBUFFER 0    /* band_h * W * 4 u32   */
@@ -250,6 +251,66 @@ int ptx_update_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uin
  * to serialise the scene.  Blocking; n_accel must be the uploaded length (PTX_E_INVALID otherwise, and
  * without a scene, a frame or a layout). */
 int ptx_read_accel(ptx_handle *h, uint32_t *accel_out, size_t n_accel);
+/* Skinning and morph targets on the GPU.  ptx_set_skin binds the bind pose, the joint indices, the
+ * weights and the morph deltas of a range of one mesh's vertices into device tables the handle owns
+ * (48 bytes per vertex, 12 per vertex and target table, (256 * 12 + 8) * 4 for a call's palette and target
+ * weights; counted in device_bytes).  One skin per mesh: a second call replaces it, n_vertices == 0
+ * removes it (counts and pointers are not looked at then), ptx_upload_scene drops every skin.  The call
+ * launches nothing and changes nothing a frame reads: every history and the kept G-buffers stay.
+ * Refused before the GPU is touched: PTX_E_INVALID -- a null handle or descriptor, no scene, no frame
+ * set or no layout, a range past the mesh's vertex block, n_joints outside 1..256, n_targets above 8, a
+ * joint index >= n_joints, a weight, bind word or delta that is not finite, null joints or weights,
+ * target_pos null with targets or non-null without, target_nrm non-null without targets, a non-zero
+ * reserved word, a vertex block that does not begin on a 16-byte boundary of the geometry array (the
+ * kernel stores 16 bytes at once; the scene compiler's blocks do); PTX_E_SCENE -- `mesh` is not loaded. */
+typedef struct ptx_skin_desc {
+    uint32_t mesh, first_vertex, n_vertices;  /* the bound range of the mesh's vertex block */
+    uint32_t n_joints;                        /* 1..256 */
+    uint32_t n_targets;                       /* 0..8 morph targets */
+    uint32_t reserved[3];                     /* zero */
+    const uint32_t *joints;      /* n_vertices * 4, each < n_joints */
+    const float    *weights;     /* n_vertices * 4, finite */
+    const float    *bind;        /* n_vertices * 6 {p.xyz, n.xyz}; NULL = words 0..5 of the handle's records now */
+    const float    *target_pos;  /* n_targets * n_vertices * 3 position deltas; NULL iff n_targets == 0 */
+    const float    *target_nrm;  /* same shape, normal deltas; NULL = normals are not morphed */
+} ptx_skin_desc;
+int ptx_set_skin(ptx_handle *h, const ptx_skin_desc *d);
+/* Pose the skinned range of `mesh` and refit its BLAS.  `palette` holds n_joints affine matrices of 12
+ * f32, three rows of four, row-major (M[4r + c]); `target_weights` n_targets f32.  Per bound vertex v,
+ * everything in f32, every product and every sum rounded on its own (no fused multiply-add), in
+ * exactly this order:
+ *   q = p;  m = n                                   (bind position / normal of the vertex)
+ *   for k = 0 .. n_targets-1:  q_c = q_c + tw[k] * dP[k][v][c]          (c = x, y, z)
+ *                              m_c = m_c + tw[k] * dN[k][v][c]          (only with target_nrm)
+ *   B[e]  = ((w0*M[j0][e] + w1*M[j1][e]) + w2*M[j2][e]) + w3*M[j3][e]   (e = 0..11)
+ *   P'_r  = ((B[4r]*q.x + B[4r+1]*q.y) + B[4r+2]*q.z) + B[4r+3]         (r = 0..2)
+ *   N_r   =  (B[4r]*m.x + B[4r+1]*m.y) + B[4r+2]*m.z
+ *   l     = sqrt((N.x*N.x + N.y*N.y) + N.z*N.z);   n' = l > 0 ? N / l : N   (IEEE sqrt and divide)
+ * P' and n' replace words 0..5 of the vertex's record in the device's geometry array; words 6 and 7
+ * (uv) stay (pathtracerdemo_amd/scene/skin.py skin_vertices is the rule in numpy).  The normal uses the
+ * blend's linear part: right for rotations and uniform scales; a non-uniformly scaled joint wants the
+ * inverse transpose, which is deliberately not built.  Then the call is ptx_update_vertices from its
+ * triangle pass onward: the same refit chain, root-box readback and instance table, the same things
+ * kept and dropped, blocking; band handles and ranks each make the same call.  Launches count in
+ * PTX_STAT_REFIT: the refit chain plus one.  The handle's host copy of the geometry array is brought up
+ * to date from the device (one device-to-host copy per skinned mesh, the accel array's boxes with it)
+ * only when a changed layout key in ptx_set_frame derives the layout again; ptx_read_vertices is how a
+ * host reads the posed records.  A ptx_update_vertices over a skinned range is legal: it writes records,
+ * the bind tables are separate, and the next ptx_skin_vertices overwrites the range.
+ * Refused before the GPU is touched, the next frame being the unedited one: what ptx_update_vertices
+ * refuses about handle and mesh; PTX_E_INVALID -- a mesh with no skin, a null or non-finite palette,
+ * target_weights null or non-finite where targets exist or non-null where there are none, and the
+ * overflow bound: with Wmax the largest per-vertex sum of |w|, Pmax the largest |bind word| and Dmax
+ * the largest |delta| of the skin, m = max |palette| and T = sum |tw|, the call is refused unless
+ * 4 * Wmax * m * (3 * (Pmax + T * Dmax) + 1), evaluated in double, is below 2^96.  Below it every P' is
+ * finite by construction, so the kernel needs no flag and no state is ever partially applied. */
+int ptx_skin_vertices(ptx_handle *h, uint32_t mesh, const float *palette /* n_joints * 12 */,
+                      const float *target_weights /* n_targets; NULL iff n_targets == 0 */);
+/* The device's current vertex records [first_vertex, first_vertex + n_vertices) of `mesh`, 8 words
+ * each, into records_out.  Blocking; ptx_read_accel's preconditions (PTX_E_INVALID without a scene, a
+ * frame or a layout, for a range past the mesh's vertex block and for a null array with n_vertices > 0;
+ * PTX_E_SCENE for a mesh that is not loaded). */
+int ptx_read_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uint32_t n_vertices, uint32_t *records_out);
 int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]);
 /* Run the configured pipeline for the current frame; if rgba_out != NULL copy the band's
  * accumulated RGBA f32 image (band_h * W * 4) into it (blocking). Otherwise asynchronous.

@@ -25,7 +25,7 @@ PTX_STAT_WAVE_TRACE, PTX_STAT_WAVE_LOGIC, PTX_STAT_FRAME = 5, 6, 7  # stats-only
 PTX_STAT_PASS_GROUP = 10
 PTX_STAT_FINAL_FUSED = 11
 PTX_STAT_DENOISE = 12  # launches of the denoiser's kernels
-PTX_STAT_REFIT = 13  # launches of ptx_update_vertices' kernels
+PTX_STAT_REFIT = 13  # launches of ptx_update_vertices' and ptx_skin_vertices' kernels
 PTX_BUF_GBUFFER, PTX_BUF_RESERVOIR, PTX_BUF_ACCUM, PTX_BUF_COUNTERS, PTX_BUF_RESERVOIR_HIST = 0, 1, 2, 3, 4
 PTX_BUF_DIRECT = 5
 PTX_BUF_DENOISED = 6  # ptx_denoise's output (read-only)
@@ -59,7 +59,7 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands",
             "ptx_upsample", "ptx_upsample_bands", "ptx_phase_uniform", "ptx_upsample_temporal",
             "ptx_trace_queries", "ptx_upsample_temporal_bands", "ptx_update_scene", "ptx_update_vertices",
-            "ptx_read_accel"]
+            "ptx_read_accel", "ptx_set_skin", "ptx_skin_vertices", "ptx_read_vertices"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -88,6 +88,13 @@ class PtxUpsampleParams(ctypes.Structure):
 class PtxUpsampleTemporalParams(ctypes.Structure):
     _fields_ = [("sigma_plane", ctypes.c_float), ("px", ctypes.c_uint32), ("py", ctypes.c_uint32),
                 ("alpha_min", ctypes.c_float), ("alpha_fill", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class PtxSkinDesc(ctypes.Structure):
+    _fields_ = [("mesh", ctypes.c_uint32), ("first_vertex", ctypes.c_uint32), ("n_vertices", ctypes.c_uint32),
+                ("n_joints", ctypes.c_uint32), ("n_targets", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3),
+                ("joints", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("bind", ctypes.c_void_p),
+                ("target_pos", ctypes.c_void_p), ("target_nrm", ctypes.c_void_p)]
 
 
 class PtxError(RuntimeError):
@@ -131,6 +138,9 @@ def load(path: str = LIB_PATH):
     lib.ptx_update_scene.argtypes = [H, P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]
     lib.ptx_update_vertices.argtypes = [H, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]
     lib.ptx_read_accel.argtypes = [H, P, ctypes.c_size_t]
+    lib.ptx_set_skin.argtypes = [H, ctypes.POINTER(PtxSkinDesc)]
+    lib.ptx_skin_vertices.argtypes = [H, ctypes.c_uint32, P, P]
+    lib.ptx_read_vertices.argtypes = [H, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]
     lib.ptx_set_frame.argtypes = [H, P]
     lib.ptx_render.argtypes = [H, P]
     lib.ptx_run_pass.argtypes = [H, ctypes.c_int]

@@ -342,6 +342,54 @@ static int layout_tables(ptx_handle *h, bool with_insts, bool with_mats) {
     return PTX_OK;
 }
 
+// The boxes of every reachable node as the device's tables hold them now, written over words 0..5 of
+// their nodes in `accel` (an array of the uploaded length): ptx_read_accel's map, lay_root_word /
+// lay_pair_words, from the NodePair / SubRoot tables back to the reference's node array.
+static int device_boxes_into(ptx_handle *h, uint32_t *accel) {
+    const size_t n_roots = h->lay_root_word.size(), n_pairs = h->lay_pair_words.size() / 2u;
+    std::vector<SubRoot> subs(n_roots);
+    std::vector<NodePair> pairs(n_pairs);
+    if (n_roots)
+        if (int rc = read_to_host(h, subs.data(), h->d_subs.p, n_roots * sizeof(SubRoot))) return rc;
+    if (n_pairs)
+        if (int rc = read_to_host(h, pairs.data(), h->d_nodes.p, n_pairs * sizeof(NodePair))) return rc;
+    auto put = [&](size_t w, const float *mn_mx) { std::memcpy(accel + w, mn_mx, 24); };
+    for (size_t s = 0; s < n_roots; ++s) {
+        const SubRoot &r = subs[s];
+        const float b[6] = {r.x[0], r.y[0], r.z[0], r.x[1], r.y[1], r.z[1]};
+        put(h->lay_root_word[s], b);
+    }
+    for (size_t p = 0; p < n_pairs; ++p) {
+        const NodePair &q = pairs[p];
+        const float l[6] = {q.x[0], q.y[0], q.z[0], q.x[2], q.y[2], q.z[2]};
+        const float r[6] = {q.x[1], q.y[1], q.z[1], q.x[3], q.y[3], q.z[3]};
+        put(h->lay_pair_words[2u * p], l);
+        put(h->lay_pair_words[2u * p + 1u], r);
+    }
+    return PTX_OK;
+}
+
+// The host's copies of the geometry and accel arrays brought up to date with the device where a vertex
+// call left them behind (ptx_handle::mesh_stale): one device-to-host copy of the vertex block per mesh
+// that ptx_skin_vertices wrote, and the boxes of the refitted nodes.  build_layout reads the copies, so it
+// calls this first; the tables and the lay_* maps still describe the layout being replaced.
+static int sync_host_mirror(ptx_handle *h) {
+    uint8_t any = 0;
+    for (size_t m = 0; m < h->mesh_stale.size() && m < h->lay_mesh_vertex.size(); ++m) {
+        any |= h->mesh_stale[m];
+        if (!(h->mesh_stale[m] & kStaleGeometry)) continue;
+        const size_t w0 = h->lay_mesh_vertex[m], n = (size_t)STRIDE_VERTEX * h->lay_mesh_nverts[m];
+        if (!n || w0 + n > h->geometry.size() || h->d_geometry.bytes < (w0 + n) * 4u) continue;
+        if (int rc = read_to_host(h, h->geometry.data() + w0, (const uint32_t *)h->d_geometry.p + w0, n * 4u)) return rc;
+        h->mesh_stale[m] &= (uint8_t)~kStaleGeometry;
+    }
+    if ((any & kStaleAccel) && h->d_subs.bytes >= h->lay_root_word.size() * sizeof(SubRoot) &&
+        h->d_nodes.bytes >= h->lay_pair_words.size() / 2u * sizeof(NodePair))
+        if (int rc = device_boxes_into(h, h->accel.data())) return rc;
+    h->mesh_stale.clear();
+    return PTX_OK;
+}
+
 // ---------------------------------------------------------------- layout derivation
 // Walks the reference's per-sub-mesh BLAS (three-mesh-bvh node format, GC/Structs.ts:73-80;
 // read by GetBlasNode, SH/PT_01_GBufferPass.wgsl:310-322) and emits the child-pair node
@@ -349,6 +397,8 @@ static int layout_tables(ptx_handle *h, bool with_insts, bool with_mats) {
 int build_layout(ptx_handle *h) {
     // frames in flight (either pipelined context) still read the layout being replaced
     if (int rc = quiesce(h)) return rc;
+    if (!h->mesh_stale.empty())
+        if (int rc = sync_host_mirror(h)) return rc;
     const uint32_t *U = h->uniform;
     const auto &S = h->scene, &G = h->geometry, &A = h->accel;
     const uint32_t off_desc = U[U_OFF_DESC], off_mat = U[U_OFF_MAT], off_index = U[U_OFF_INDEX];
@@ -2171,6 +2221,15 @@ int ptx_create(const ptx_config *cfg, ptx_handle **out) {
     return PTX_OK;
 }
 
+static void free_skin(ptx_handle::Skin &k) {
+    for (DevBuf *b : {&k.bind, &k.target_pos, &k.target_nrm, &k.pose}) free_buf(*b);
+    k = ptx_handle::Skin{};
+}
+static void drop_skins(ptx_handle *h) {
+    for (auto &k : h->skins) free_skin(k);
+    h->skins.clear();
+}
+
 int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const uint32_t *geometry,
                      size_t n_geometry, const uint32_t *accel, size_t n_accel) {
     if (!h) return PTX_E_INVALID;
@@ -2180,6 +2239,8 @@ int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const
     h->scene.assign(scene, scene + n_scene);
     h->geometry.assign(geometry, geometry + n_geometry);
     h->accel.assign(accel ? accel : scene, accel ? accel + n_accel : scene);
+    h->mesh_stale.clear();
+    drop_skins(h);  // (bound to the old scene's meshes)
     if (int rc = upload(h, h->d_scene, scene, n_scene * 4u)) return rc;
     if (int rc = upload(h, h->d_geometry, geometry, n_geometry * 4u)) return rc;
     h->layout_valid = false;
@@ -2276,6 +2337,8 @@ int ptx_update_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, uint3
     return PTX_OK;
 }
 
+static int refit_after_vertices(ptx_handle *h, uint32_t mesh, hipError_t le, uint8_t stale, const char *what);
+
 int ptx_update_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uint32_t n_vertices, const uint32_t *vertices) {
     if (!h) return PTX_E_INVALID;
     if (!h->scene_loaded || !h->frame_set || !h->layout_valid)
@@ -2299,9 +2362,17 @@ int ptx_update_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uin
     if (int rc = quiesce(h)) return rc;  // frames in flight still read the geometry and the tables
     // From here on the handle changes.  A HIP error part-way would leave the device's tables between the
     // two shapes: the handle then holds no scene until the next ptx_upload_scene.
-    const hipStream_t st = h->cur().stream;
     std::memcpy(h->geometry.data() + word0, vertices, n_words * 4u);
-    hipError_t le = copy_sync(h, (uint32_t *)h->d_geometry.p + word0, vertices, n_words * 4u, hipMemcpyHostToDevice);
+    const hipError_t le = copy_sync(h, (uint32_t *)h->d_geometry.p + word0, vertices, n_words * 4u, hipMemcpyHostToDevice);
+    return refit_after_vertices(h, mesh, le, kStaleAccel, "ptx_update_vertices");
+}
+
+// The shared tail of ptx_update_vertices and ptx_skin_vertices, the device's vertex records of `mesh`
+// being the new ones (or `le` the error that kept them from it): the refit chain, the readback of the
+// mesh's root boxes, the instance table, and what the call keeps and drops.  `stale`: which of the
+// host's copies the device is now ahead of (ptx_handle::mesh_stale).
+static int refit_after_vertices(ptx_handle *h, uint32_t mesh, hipError_t le, uint8_t stale, const char *what) {
+    const hipStream_t st = h->cur().stream;
     const uint32_t *d = h->scene.data() + h->uniform[U_OFF_DESC] + STRIDE_DESCRIPTOR * mesh;
     RefitMesh m{};
     m.G = (const uint32_t *)h->d_geometry.p;
@@ -2322,7 +2393,7 @@ int ptx_update_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uin
     for (size_t k = 0; k + 1 < lv.size(); ++k)
         le = slot_timed(h, PTX_STAT_REFIT, st, le, [&] { return launch_refit_level(m, lv[k], lv[k + 1] - lv[k], st); });
     le = slot_timed(h, PTX_STAT_REFIT, st, le, [&] { return launch_refit_roots(m, st); });
-    int rc = le == hipSuccess ? PTX_OK : fail(h, PTX_E_HIP, "ptx_update_vertices: %s", hipGetErrorString(le));
+    int rc = le == hipSuccess ? PTX_OK : fail(h, PTX_E_HIP, "%s: %s", what, hipGetErrorString(le));
     // the mesh's root boxes (the only readback): the instance cull boxes are made from them
     if (rc == PTX_OK && m.n_subs)
         rc = read_to_host(h, h->lay_subs.data() + m.sub_base, m.subs + m.sub_base, (size_t)m.n_subs * sizeof(SubRoot));
@@ -2332,8 +2403,11 @@ int ptx_update_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uin
         h->hist_valid = h->dn_hist_valid = h->ut_valid = h->drawn = h->rendered = false;
         for (auto &c : h->ctx) c.surf_valid = c.init_state_valid = c.nbr_valid = false;
         gbuf_key_drop_all(h);
+        h->mesh_stale.clear();  // (nothing on the device is worth reading back)
         return rc;
     }
+    h->mesh_stale.resize(h->lay_mesh_nsub.size(), 0u);
+    h->mesh_stale[mesh] |= stale;
     // kept and dropped as by an instance edit without a switched mesh (ptx_update_scene): triangle numbers
     // and sub-meshes stay valid, so the history's reservoirs decode; its frame's surface records were made
     // from the old shape, so it serves that frame's camera alone
@@ -2355,28 +2429,158 @@ int ptx_read_accel(ptx_handle *h, uint32_t *accel_out, size_t n_accel) {
         return fail(h, PTX_E_INVALID, "ptx_read_accel: %zu words, the uploaded array has %zu", n_accel, h->accel.size());
     HIP_CHECK(h, hipSetDevice(h->device));
     if (int rc = quiesce(h)) return rc;
-    const size_t n_roots = h->lay_root_word.size(), n_pairs = h->lay_pair_words.size() / 2u;
-    std::vector<SubRoot> subs(n_roots);
-    std::vector<NodePair> pairs(n_pairs);
-    if (n_roots)
-        if (int rc = read_to_host(h, subs.data(), h->d_subs.p, n_roots * sizeof(SubRoot))) return rc;
-    if (n_pairs)
-        if (int rc = read_to_host(h, pairs.data(), h->d_nodes.p, n_pairs * sizeof(NodePair))) return rc;
     if (n_accel) std::memcpy(accel_out, h->accel.data(), n_accel * 4u);
-    auto put = [&](size_t w, const float *mn_mx) { std::memcpy(accel_out + w, mn_mx, 24); };
-    for (size_t s = 0; s < n_roots; ++s) {
-        const SubRoot &r = subs[s];
-        const float b[6] = {r.x[0], r.y[0], r.z[0], r.x[1], r.y[1], r.z[1]};
-        put(h->lay_root_word[s], b);
-    }
-    for (size_t p = 0; p < n_pairs; ++p) {
-        const NodePair &q = pairs[p];
-        const float l[6] = {q.x[0], q.y[0], q.z[0], q.x[2], q.y[2], q.z[2]};
-        const float r[6] = {q.x[1], q.y[1], q.z[1], q.x[3], q.y[3], q.z[3]};
-        put(h->lay_pair_words[2u * p], l);
-        put(h->lay_pair_words[2u * p + 1u], r);
-    }
+    return device_boxes_into(h, accel_out);
+}
+
+// What the vertex calls ask of handle, mesh and range alike (ptx_update_vertices states it first).
+static int vertex_range_check(ptx_handle *h, const char *what, uint32_t mesh, uint32_t first, uint32_t n) {
+    if (!h->scene_loaded || !h->frame_set || !h->layout_valid)
+        return fail(h, PTX_E_INVALID, "%s: upload a scene and set a frame first", what);
+    const uint32_t n_mesh = (uint32_t)h->lay_mesh_nsub.size();
+    if (mesh >= n_mesh) return fail(h, PTX_E_SCENE, "%s: mesh %u of %u", what, mesh, n_mesh);
+    if ((uint64_t)first + n > h->lay_mesh_nverts[mesh])
+        return fail(h, PTX_E_INVALID, "%s: vertices [%u, %llu) of mesh %u, which has %u", what, first,
+                    (unsigned long long)first + n, mesh, h->lay_mesh_nverts[mesh]);
+    const size_t end = (size_t)h->lay_mesh_vertex[mesh] + (size_t)STRIDE_VERTEX * ((size_t)first + n);
+    if (end > h->geometry.size() || h->d_geometry.bytes < end * 4u)
+        return fail(h, PTX_E_INVALID, "%s: the mesh's vertex block lies past the geometry array", what);
     return PTX_OK;
+}
+
+static bool all_finite(const float *p, size_t n, double &max_abs) {
+    for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(p[i])) return false;
+        max_abs = std::max(max_abs, (double)std::fabs(p[i]));
+    }
+    return true;
+}
+
+int ptx_set_skin(ptx_handle *h, const ptx_skin_desc *d) {
+    if (!h) return PTX_E_INVALID;
+    if (!d) return fail(h, PTX_E_INVALID, "ptx_set_skin: null descriptor");
+    const char *what = "ptx_set_skin";
+    if (int rc = vertex_range_check(h, what, d->mesh, d->first_vertex, d->n_vertices)) return rc;
+    if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return fail(h, PTX_E_INVALID, "%s: a reserved word is not zero", what);
+    const uint32_t mesh = d->mesh, n = d->n_vertices;
+    if (n == 0u) {  // remove the mesh's skin
+        if (mesh < h->skins.size()) free_skin(h->skins[mesh]);
+        return PTX_OK;
+    }
+    if (d->n_joints < 1u || d->n_joints > kSkinMaxJoints) return fail(h, PTX_E_INVALID, "%s: %u joints (1..256)", what, d->n_joints);
+    if (d->n_targets > kSkinMaxTargets) return fail(h, PTX_E_INVALID, "%s: %u morph targets (0..8)", what, d->n_targets);
+    if (!d->joints || !d->weights) return fail(h, PTX_E_INVALID, "%s: null joints or weights", what);
+    if ((d->target_pos != nullptr) != (d->n_targets > 0u) || (d->target_nrm && !d->n_targets))
+        return fail(h, PTX_E_INVALID, "%s: %u morph targets and a %s delta table", what, d->n_targets, d->n_targets ? "null" : "non-null");
+    const size_t word0 = (size_t)h->lay_mesh_vertex[mesh] + (size_t)STRIDE_VERTEX * d->first_vertex;
+    if (word0 % 4u) return fail(h, PTX_E_INVALID, "%s: the mesh's vertex block does not begin on a 16-byte boundary", what);
+    for (size_t i = 0; i < 4u * (size_t)n; ++i)
+        if (d->joints[i] >= d->n_joints)
+            return fail(h, PTX_E_INVALID, "%s: vertex %zu: joint %u of %u", what, d->first_vertex + i / 4u, d->joints[i], d->n_joints);
+    ptx_handle::Skin k;
+    k.first = d->first_vertex;
+    k.n = n;
+    k.n_joints = d->n_joints;
+    k.n_targets = d->n_targets;
+    double unused = 0.0;
+    if (!all_finite(d->weights, 4u * (size_t)n, unused)) return fail(h, PTX_E_INVALID, "%s: a weight is not finite", what);
+    for (size_t v = 0; v < n; ++v) {
+        const float *w = d->weights + 4u * v;
+        k.w_max = std::max(k.w_max, (double)std::fabs(w[0]) + std::fabs(w[1]) + std::fabs(w[2]) + std::fabs(w[3]));
+    }
+    const size_t n_delta = 3u * (size_t)n * d->n_targets;
+    if (d->n_targets && (!all_finite(d->target_pos, n_delta, k.d_max) || (d->target_nrm && !all_finite(d->target_nrm, n_delta, k.d_max))))
+        return fail(h, PTX_E_INVALID, "%s: a morph delta is not finite", what);
+    HIP_CHECK(h, hipSetDevice(h->device));
+    // the bind pose: the caller's, or words 0..5 of the records as they are now -- on the device, where
+    // ptx_skin_vertices has left the host's copy behind
+    std::vector<uint32_t> now;
+    if (!d->bind) {
+        now.assign(h->geometry.begin() + word0, h->geometry.begin() + word0 + (size_t)STRIDE_VERTEX * n);
+        if (mesh < h->mesh_stale.size() && (h->mesh_stale[mesh] & kStaleGeometry)) {
+            if (int rc = quiesce(h)) return rc;
+            if (int rc = read_to_host(h, now.data(), (const uint32_t *)h->d_geometry.p + word0, now.size() * 4u)) return rc;
+        }
+    }
+    std::vector<float> rec(12u * (size_t)n);
+    for (size_t v = 0; v < n; ++v) {
+        float *r = rec.data() + 12u * v;
+        if (d->bind) std::memcpy(r, d->bind + 6u * v, 24);
+        else std::memcpy(r, now.data() + STRIDE_VERTEX * v, 24);
+        std::memcpy(r + 6, d->weights + 4u * v, 16);
+        const uint32_t *j = d->joints + 4u * v;
+        const uint32_t packed[2] = {j[0] | j[1] << 16, j[2] | j[3] << 16};
+        std::memcpy(r + 10, packed, 8);
+        if (!all_finite(r, 6, k.p_max)) return fail(h, PTX_E_INVALID, "%s: vertex %zu: a bind word is not finite", what, d->first_vertex + v);
+    }
+    // From here on the GPU is touched, but nothing a frame reads: new tables, then the old skin's freed.
+    int rc = upload(h, k.bind, rec.data(), rec.size() * sizeof(float));
+    if (rc == PTX_OK && d->n_targets) rc = upload(h, k.target_pos, d->target_pos, n_delta * sizeof(float));
+    if (rc == PTX_OK && d->target_nrm) rc = upload(h, k.target_nrm, d->target_nrm, n_delta * sizeof(float));
+    if (rc == PTX_OK) rc = alloc_buf(h, k.pose, (12u * kSkinMaxJoints + kSkinMaxTargets) * sizeof(float));
+    if (rc != PTX_OK) {
+        free_skin(k);
+        return rc;
+    }
+    if (h->skins.size() <= mesh) h->skins.resize(h->lay_mesh_nsub.size());
+    free_skin(h->skins[mesh]);
+    h->skins[mesh] = k;
+    return PTX_OK;
+}
+
+int ptx_skin_vertices(ptx_handle *h, uint32_t mesh, const float *palette, const float *target_weights) {
+    if (!h) return PTX_E_INVALID;
+    const char *what = "ptx_skin_vertices";
+    if (int rc = vertex_range_check(h, what, mesh, 0u, 0u)) return rc;
+    if (mesh >= h->skins.size() || h->skins[mesh].n == 0u) return fail(h, PTX_E_INVALID, "%s: mesh %u has no skin", what, mesh);
+    ptx_handle::Skin &k = h->skins[mesh];
+    // (the layout may have been derived again since ptx_set_skin: the range is checked against this one)
+    if (int rc = vertex_range_check(h, what, mesh, k.first, k.n)) return rc;
+    const size_t word0 = (size_t)h->lay_mesh_vertex[mesh] + (size_t)STRIDE_VERTEX * k.first;
+    if (word0 % 4u || word0 > 0xffffffffull) return fail(h, PTX_E_INVALID, "%s: the mesh's vertex block moved off a 16-byte boundary", what);
+    if (!palette) return fail(h, PTX_E_INVALID, "%s: null palette", what);
+    if ((target_weights != nullptr) != (k.n_targets > 0u))
+        return fail(h, PTX_E_INVALID, "%s: the skin has %u morph targets and the target weights are %s", what, k.n_targets,
+                    target_weights ? "given" : "null");
+    double m_max = 0.0, t_sum = 0.0, unused = 0.0;
+    if (!all_finite(palette, 12u * (size_t)k.n_joints, m_max)) return fail(h, PTX_E_INVALID, "%s: a palette element is not finite", what);
+    if (k.n_targets && !all_finite(target_weights, k.n_targets, unused)) return fail(h, PTX_E_INVALID, "%s: a target weight is not finite", what);
+    for (uint32_t t = 0; t < k.n_targets; ++t) t_sum += std::fabs((double)target_weights[t]);
+    // below 2^96 every P' is finite by construction (include/ptx.h): no flag, nothing partially applied
+    const double bound = 4.0 * k.w_max * m_max * (3.0 * (k.p_max + t_sum * k.d_max) + 1.0);
+    if (!(bound < 0x1p96)) return fail(h, PTX_E_INVALID, "%s: the overflow bound %g is not below 2^96", what, bound);
+    HIP_CHECK(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;  // frames in flight still read the geometry and the tables
+    // From here on the handle changes (ptx_update_vertices: a HIP error part-way leaves it without a scene).
+    const hipStream_t st = h->cur().stream;
+    std::vector<float> pose(12u * (size_t)k.n_joints + k.n_targets);
+    std::memcpy(pose.data(), palette, 48u * (size_t)k.n_joints);
+    if (k.n_targets) std::memcpy(pose.data() + 12u * (size_t)k.n_joints, target_weights, 4u * (size_t)k.n_targets);
+    hipError_t le = copy_sync(h, k.pose.p, pose.data(), pose.size() * sizeof(float), hipMemcpyHostToDevice);
+    SkinArgs a{};
+    a.G = (uint32_t *)h->d_geometry.p;
+    a.bind = (const float4 *)k.bind.p;
+    a.target_pos = (const float *)k.target_pos.p;
+    a.target_nrm = (const float *)k.target_nrm.p;
+    a.palette = (const float4 *)k.pose.p;
+    a.target_weights = (const float *)k.pose.p + 12u * (size_t)k.n_joints;
+    a.word0 = (uint32_t)word0;
+    a.n = k.n;
+    a.n_joints = k.n_joints;
+    a.n_targets = k.n_targets;
+    le = slot_timed(h, PTX_STAT_REFIT, st, le, [&] { return launch_skin_vertices(a, st); });
+    return refit_after_vertices(h, mesh, le, kStaleGeometry | kStaleAccel, what);
+}
+
+int ptx_read_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uint32_t n_vertices, uint32_t *records_out) {
+    if (!h) return PTX_E_INVALID;
+    if (int rc = vertex_range_check(h, "ptx_read_vertices", mesh, first_vertex, n_vertices)) return rc;
+    if (n_vertices == 0u) return PTX_OK;
+    if (!records_out) return fail(h, PTX_E_INVALID, "ptx_read_vertices: null array");
+    HIP_CHECK(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;
+    const size_t word0 = (size_t)h->lay_mesh_vertex[mesh] + (size_t)STRIDE_VERTEX * first_vertex;
+    return read_to_host(h, records_out, (const uint32_t *)h->d_geometry.p + word0, (size_t)STRIDE_VERTEX * n_vertices * 4u);
 }
 
 int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]) {
@@ -2596,6 +2800,7 @@ int ptx_get_stats(ptx_handle *h, ptx_stats *out) {
                         h->d_dn_hist[1].bytes + h->d_dn_mom[0].bytes + h->d_dn_mom[1].bytes + h->d_dn_halo_g.bytes +
                         h->d_dn_halo_c.bytes + h->d_dn_obj.bytes + h->d_up_halo.bytes + h->d_ut_guide[0].bytes + h->d_ut_guide[1].bytes +
                         h->d_ut_hist[0].bytes + h->d_ut_hist[1].bytes + h->d_refit_order.bytes + h->d_refit_box.bytes;
+    for (const auto &k : h->skins) out->device_bytes += k.bind.bytes + k.target_pos.bytes + k.target_nrm.bytes + k.pose.bytes;
     return PTX_OK;
 }
 
@@ -2998,6 +3203,7 @@ int ptx_destroy(ptx_handle *h) {
                       &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_dn_obj, &h->d_up_halo, &h->d_ut_guide[0], &h->d_ut_guide[1],
                       &h->d_ut_hist[0], &h->d_ut_hist[1], &h->d_refit_order, &h->d_refit_box})
         free_buf(*b);
+    drop_skins(h);
     for (auto &c : h->ctx) {
         for (DevBuf *b : {&c.gbuf, &c.res, &c.direct, &c.nbr, &c.tjstate, &c.tjres, &c.surf, &c.wstate, &c.wrays, &c.wres[0],
                           &c.wres[1], &c.wres[2], &c.wact[0], &c.wact[1], &c.wctr})

@@ -38,6 +38,9 @@ inline bool is_motion_pass(int p) {
     return p == kPassTemporalMotion;
 }
 
+// ptx_handle::mesh_stale: the device is ahead of the host's geometry / of the host's accel boxes
+constexpr uint8_t kStaleGeometry = 1u, kStaleAccel = 2u;
+
 struct ptx_handle {
     ptx_config cfg{};
     int device = 0;
@@ -72,6 +75,19 @@ struct ptx_handle {
     // the order table on the device (4 B per pair) and the triangle boxes of one mesh's refit (24 B per
     // triangle of the largest mesh): allocated with the layout
     DevBuf d_refit_order, d_refit_box;
+    // ptx_set_skin's tables, one skin per mesh (indexed by mesh; n == 0: none): the 48-byte bind records,
+    // the target-major delta tables, a call's palette + target weights; the three maxima of the
+    // overflow bound (ptx_skin_vertices).  Dropped by ptx_upload_scene, freed by ptx_destroy.
+    struct Skin {
+        uint32_t first = 0, n = 0, n_joints = 0, n_targets = 0;
+        double w_max = 0.0, p_max = 0.0, d_max = 0.0;
+        DevBuf bind, target_pos, target_nrm, pose;
+    };
+    std::vector<Skin> skins;
+    // per mesh: the device's vertex records (kStaleGeometry: ptx_skin_vertices wrote them) or the boxes
+    // of its nodes (kStaleAccel: a refit wrote them) are newer than `geometry` / `accel` above.
+    // build_layout reads the host copies, so it brings them up to date first (sync_host_mirror).
+    std::vector<uint8_t> mesh_stale;  // kStaleGeometry | kStaleAccel
     bool scene_loaded = false;
     // frame
     uint32_t uniform[PTX_UNIFORM_WORDS] = {0};

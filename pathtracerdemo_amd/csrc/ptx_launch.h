@@ -150,6 +150,22 @@ hipError_t launch_refit_level(const RefitMesh &m, uint32_t first, uint32_t n, hi
 // the root records' boxes, after the last height
 hipError_t launch_refit_roots(const RefitMesh &m, hipStream_t s);
 
+// ptx_skin_vertices (ptx_skin.hip): the bound vertices [0, n) of one skin written over words 0..5 of
+// their records, which begin at word `word0` of G (16-byte aligned).  `bind` holds three float4 per
+// vertex -- {p.xyz, n.x}, {n.y, n.z, w0, w1}, {w2, w3, j0 | j1 << 16, j2 | j3 << 16} --, the delta tables
+// are target-major (3 floats per target and vertex; target_nrm may be null), `palette` three float4
+// per joint, all on the device.  The refit chain of ptx_update_vertices follows it on the stream.
+constexpr uint32_t kSkinMaxJoints = 256u, kSkinMaxTargets = 8u;
+struct SkinArgs {
+    uint32_t *G;
+    const float4 *bind;
+    const float *target_pos, *target_nrm;
+    const float4 *palette;
+    const float *target_weights;
+    uint32_t word0, n, n_joints, n_targets;
+};
+hipError_t launch_skin_vertices(const SkinArgs &a, hipStream_t s);
+
 // closest-hit queries for a ray array (ptx_kernels.hip)
 hipError_t launch_trace_rays(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,
                              uint32_t stack_depth, hipStream_t s);

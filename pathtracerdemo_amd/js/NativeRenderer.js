@@ -115,6 +115,7 @@ class NativeRenderer {
     this.PresentSource = 'accum';
     this.createHandle();
     this.World = null;
+    this.Skins = new Map(); // mesh -> { first, n, joints, targets } of SetSkin
     this.Camera = null;
     this.FrameCount = 0;
     this.Uniform = null;
@@ -178,6 +179,7 @@ class NativeRenderer {
     this.World = world;
     this.ResetFrameCount();
     addon.uploadScene(this.Handle, world.scene, world.geometry, world.accel);
+    this.Skins.clear(); // (the upload drops every skin)
     addon.resetAccumulation(this.Handle);
   }
 
@@ -238,6 +240,69 @@ class NativeRenderer {
     if (!this.World) throw new Error('ReadAccel: Initialize first');
     const out = new Uint32Array(this.World.accel.length);
     addon.readAccel(this.Handle, out);
+    return out;
+  }
+
+  /**
+   * Bind a skin to the vertices [first, first + joints.length / 4) of mesh `mesh` (ptx_set_skin): `joints`
+   * a Uint32Array and `weights` a Float32Array of four per vertex; optional Float32Arrays `bind` (six per
+   * vertex: position, normal; null: the records as the handle holds them now), `targets` (morph position
+   * deltas, 3 per vertex, target after target) and `targetNormals` (the same shape).  The joint count is
+   * 1 + the largest index.  Empty arrays remove the mesh's skin.  Nothing a frame reads changes; a
+   * refused call throws and binds nothing.  After Update() (the handle needs a frame set).
+   */
+  SetSkin(mesh, first, joints, weights, bind = null, targets = null, targetNormals = null) {
+    const f32 = (a) => a === null || a === undefined || a instanceof Float32Array;
+    if (!Number.isInteger(mesh) || mesh < 0 || !Number.isInteger(first) || first < 0 || !(joints instanceof Uint32Array) ||
+        joints.length % 4 !== 0 || !(weights instanceof Float32Array) || weights.length !== joints.length ||
+        !f32(bind) || !f32(targets) || !f32(targetNormals)) {
+      throw new TypeError('SetSkin: expected (mesh, first, Uint32Array and Float32Array of 4 per vertex, Float32Arrays or null)');
+    }
+    const n = joints.length / 4;
+    if ((bind && bind.length !== 6 * n) || (targets && (n === 0 || targets.length === 0 || targets.length % (3 * n) !== 0)) ||
+        (targetNormals && (!targets || targetNormals.length !== targets.length))) {
+      throw new TypeError('SetSkin: bind has 6 floats per vertex, targets 3 per vertex and target, targetNormals the shape of targets');
+    }
+    if (!this.World) throw new Error('SetSkin: Initialize first');
+    let nJoints = 1;
+    for (let i = 0; i < joints.length; i++) nJoints = Math.max(nJoints, joints[i] + 1);
+    addon.setSkin(this.Handle, mesh, first, nJoints, joints, weights, bind || null, targets || null, targetNormals || null);
+    if (n) this.Skins.set(mesh, { first, n, joints: nJoints, targets: targets ? targets.length / (3 * n) : 0 });
+    else this.Skins.delete(mesh);
+  }
+
+  /**
+   * Pose the skinned range of mesh `mesh` and refit its BLAS on the GPU (ptx_skin_vertices): `palette` is
+   * a Float32Array of 12 per joint (three rows of four, row-major), `targetWeights` a Float32Array of one
+   * per bound morph target (null without targets).  this.World is afterwards what the handle renders:
+   * the range's records ReadVertices()'s, the accel array ReadAccel()'s (new arrays).  Blocking; band
+   * renderers make the same call on every band.  A refused call throws and changes nothing.
+   */
+  SkinVertices(mesh, palette, targetWeights = null) {
+    if (!Number.isInteger(mesh) || mesh < 0 || !(palette instanceof Float32Array) || palette.length % 12 !== 0 ||
+        !(targetWeights === null || targetWeights === undefined || targetWeights instanceof Float32Array)) {
+      throw new TypeError('SkinVertices: expected (mesh, Float32Array of 12 per joint, Float32Array of target weights or null)');
+    }
+    const skin = this.Skins.get(mesh);
+    if (!skin) throw new Error(`SkinVertices: mesh ${mesh} has no skin`);
+    if (palette.length < 12 * skin.joints || (targetWeights ? targetWeights.length : 0) !== skin.targets) {
+      throw new RangeError(`SkinVertices: the skin has ${skin.joints} joints and ${skin.targets} morph targets`);
+    }
+    addon.skinVertices(this.Handle, mesh, palette.subarray(0, 12 * skin.joints), targetWeights || null);
+    const w = this.World;
+    const geometry = new Uint32Array(w.geometry);
+    geometry.set(this.ReadVertices(mesh, skin.first, skin.n), w.scene[w.offsets[0] + 6 * mesh] + 8 * skin.first);
+    this.World = Object.assign({}, w, { geometry, accel: this.ReadAccel() });
+  }
+
+  /** The device's current records [first, first + n) of mesh `mesh`, 8 words each (ptx_read_vertices).  Blocking. */
+  ReadVertices(mesh, first, n) {
+    if (!Number.isInteger(mesh) || mesh < 0 || !Number.isInteger(first) || first < 0 || !Number.isInteger(n) || n < 0) {
+      throw new TypeError('ReadVertices: expected (mesh, first, n)');
+    }
+    if (!this.World) throw new Error('ReadVertices: Initialize first');
+    const out = new Uint32Array(8 * n);
+    addon.readVertices(this.Handle, mesh, first, out);
     return out;
   }
 

@@ -288,6 +288,112 @@ static napi_value js_read_accel(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* A typed array of type `want` (0), or null / undefined (0, *p = NULL, *n = 0); anything else: -1. */
+static int opt_view(napi_env env, napi_value v, napi_typedarray_type want, void **p, size_t *n) {
+    napi_valuetype vt;
+    napi_typeof(env, v, &vt);
+    *p = NULL;
+    *n = 0;
+    if (vt == napi_undefined || vt == napi_null) return 0;
+    size_t es;
+    napi_typedarray_type t;
+    if (typed_view(env, v, p, n, &es, &t) || t != want) return -1;
+    static uint32_t empty;
+    if (!*p) *p = &empty; /* (an empty array may have no storage: it is still an array, not null) */
+    return 0;
+}
+
+/* setSkin(h, mesh, first, nJoints, Uint32Array joints, Float32Array weights, Float32Array bind | null,
+ *         Float32Array targetPos | null, Float32Array targetNrm | null): four joints and weights per vertex, six bind
+ * words, 3 * n floats per morph target (ptx_set_skin; an empty joints array removes the mesh's skin) */
+static napi_value js_set_skin(napi_env env, napi_callback_info info) {
+    size_t argc = 9;
+    napi_value argv[9];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    ptx_skin_desc d;
+    memset(&d, 0, sizeof d);
+    void *p[5] = {NULL, NULL, NULL, NULL, NULL};
+    size_t n[5] = {0, 0, 0, 0, 0};
+    static const napi_typedarray_type want[5] = {napi_uint32_array, napi_float32_array, napi_float32_array,
+                                                 napi_float32_array, napi_float32_array};
+    int bad = argc < 6 || napi_get_value_uint32(env, argv[1], &d.mesh) != napi_ok ||
+              napi_get_value_uint32(env, argv[2], &d.first_vertex) != napi_ok ||
+              napi_get_value_uint32(env, argv[3], &d.n_joints) != napi_ok;
+    for (size_t i = 0; !bad && i < 5; ++i)
+        if (4 + i < argc) bad = opt_view(env, argv[4 + i], want[i], &p[i], &n[i]) != 0;
+    const size_t nv = n[0] / 4u;
+    bad = bad || !p[0] || !p[1] || n[0] % 4u != 0 || nv > 0xffffffffu || n[1] != n[0] || (p[2] && n[2] != 6u * nv) ||
+          (p[3] && (nv == 0 || n[3] == 0 || n[3] % (3u * nv) != 0)) || (p[4] && (!p[3] || n[4] != n[3]));
+    if (bad) {
+        napi_throw_type_error(env, NULL, "setSkin(h, mesh, first, nJoints, joints, weights, bind, targetPos, targetNrm) takes three integers, "
+                                         "a Uint32Array and a Float32Array of 4 per vertex, and Float32Arrays or null: 6 per vertex, "
+                                         "3 per vertex and target, the same again");
+        return NULL;
+    }
+    d.n_vertices = (uint32_t)nv;
+    d.n_targets = p[3] ? (uint32_t)(n[3] / (3u * nv)) : 0u;
+    d.joints = (const uint32_t *)p[0];
+    d.weights = (const float *)p[1];
+    d.bind = (const float *)p[2];
+    d.target_pos = (const float *)p[3];
+    d.target_nrm = (const float *)p[4];
+    int rc = ptx_set_skin(H->h, &d);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_set_skin");
+    return NULL;
+}
+
+/* skinVertices(h, mesh, Float32Array palette, Float32Array targetWeights | null): 12 floats per joint, one per morph
+ * target (ptx_skin_vertices).  The library reads as many matrices and weights as the skin has joints and targets: it
+ * is handed zero-padded copies of the largest size, so a short array is never read past. */
+static napi_value js_skin_vertices(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    uint32_t mesh = 0;
+    void *pal = NULL, *tw = NULL;
+    size_t np = 0, nt = 0;
+    if (argc < 3 || napi_get_value_uint32(env, argv[1], &mesh) != napi_ok || opt_view(env, argv[2], napi_float32_array, &pal, &np) ||
+        !pal || np == 0 || np % 12u != 0 || np > 12u * 256u || (argc >= 4 && opt_view(env, argv[3], napi_float32_array, &tw, &nt)) ||
+        (tw && (nt == 0 || nt > 8u))) {
+        napi_throw_type_error(env, NULL, "skinVertices(h, mesh, palette, targetWeights) takes an integer, a Float32Array of 12 per joint "
+                                         "(1..256 joints) and a Float32Array of 1..8 target weights or null");
+        return NULL;
+    }
+    static float palette[12 * 256], weights[8];
+    memset(palette, 0, sizeof palette);
+    memset(weights, 0, sizeof weights);
+    memcpy(palette, pal, np * sizeof(float));
+    if (tw) memcpy(weights, tw, nt * sizeof(float));
+    int rc = ptx_skin_vertices(H->h, mesh, palette, tw ? weights : NULL);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_skin_vertices");
+    return NULL;
+}
+
+/* readVertices(h, mesh, first, Uint32Array out): the device's records [first, first + out.length / 8) of the mesh (ptx_read_vertices) */
+static napi_value js_read_vertices(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    uint32_t mesh = 0, first = 0;
+    void *p;
+    size_t n, es;
+    napi_typedarray_type t;
+    if (argc < 4 || napi_get_value_uint32(env, argv[1], &mesh) != napi_ok || napi_get_value_uint32(env, argv[2], &first) != napi_ok ||
+        typed_view(env, argv[3], &p, &n, &es, &t) || t != napi_uint32_array || n % 8u != 0 || n / 8u > 0xffffffffu) {
+        napi_throw_type_error(env, NULL, "readVertices(h, mesh, first, out) takes two integers and a Uint32Array of 8 words per vertex");
+        return NULL;
+    }
+    int rc = ptx_read_vertices(H->h, mesh, first, (uint32_t)(n / 8u), (uint32_t *)p);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_read_vertices");
+    return NULL;
+}
+
 /* setFrame(h, Uint32Array(33)) */
 static napi_value js_set_frame(napi_env env, napi_callback_info info) {
     size_t argc = 2;
@@ -986,6 +1092,9 @@ static napi_value init(napi_env env, napi_value exports) {
         {"updateScene", NULL, js_update_scene, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"updateVertices", NULL, js_update_vertices, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"readAccel", NULL, js_read_accel, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"setSkin", NULL, js_set_skin, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"skinVertices", NULL, js_skin_vertices, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"readVertices", NULL, js_read_vertices, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"phaseUniform", NULL, js_phase_uniform, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
     };
     if (napi_define_properties(env, exports, sizeof later / sizeof later[0], later) != napi_ok) return NULL;

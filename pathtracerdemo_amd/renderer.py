@@ -56,6 +56,7 @@ class Renderer:
         self.camera: Camera | None = None
         self.frame_count = 0
         self.uniform = None
+        self._skins: dict = {}  # mesh -> (first, n, joints, targets) of SetSkin
 
     # ------------------------------------------------------------------ reference surface
     def GetCamera(self) -> Camera:
@@ -75,6 +76,7 @@ class Renderer:
         cs = self.compiled
         self._call("ptx_upload_scene", self._h, cs.scene.ctypes.data, len(cs.scene), cs.geometry.ctypes.data,
                    len(cs.geometry), cs.accel.ctypes.data if len(cs.accel) else None, len(cs.accel))
+        self._skins = {}  # (the upload drops every skin)
         self._call("ptx_reset_accumulation", self._h)
 
     def UpdateScene(self, world: World | CompiledScene) -> int:
@@ -135,6 +137,78 @@ class Renderer:
         every reachable node from the device's tables -- after UpdateVertices, the refit."""
         out = np.zeros(len(self.compiled.accel), dtype=np.uint32)
         self._call("ptx_read_accel", self._h, out.ctypes.data if len(out) else None, len(out))
+        return out
+
+    def SetSkin(self, mesh: int, joints, weights, bind=None, targets=None, target_normals=None, first: int = 0) -> None:
+        """Bind a skin to vertices [first, first + n) of mesh `mesh` (ptx_set_skin): `joints` (n, 4) integers,
+        `weights` (n, 4) f32, `bind` (n, 6) f32 {p, n} (None: the records as the handle holds them now),
+        `targets` (T, n, 3) f32 morph position deltas, `target_normals` the same shape.  n == 0 removes the
+        mesh's skin.  Nothing a frame reads changes; a refused call (PtxError) binds nothing."""
+        if self.compiled is None or self.uniform is None:
+            raise ValueError("SetSkin: Initialize and Update first")
+        j = np.ascontiguousarray(joints, dtype=np.uint32).reshape(-1, 4)
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1, 4)
+        if len(j) != len(w):
+            raise ValueError("SetSkin: four joints and four weights per vertex")
+        n = len(j)
+        keep = [j, w]
+
+        def table(a, shape, what):
+            if a is None:
+                return None, 0
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != len(shape) or a.shape[1:] != shape[1:]:
+                raise ValueError(f"SetSkin: {what} must have the shape {shape}")
+            keep.append(a)
+            return a.ctypes.data if a.size else None, len(a)
+        b, nb = table(bind, (n, 6), "bind")
+        if bind is not None and nb != n:
+            raise ValueError("SetSkin: one bind record per vertex")
+        tp, nt = table(targets, (0, n, 3), "targets")
+        tn, ntn = table(target_normals, (0, n, 3), "target_normals")
+        if target_normals is not None and ntn != nt:
+            raise ValueError("SetSkin: one table of normal deltas per target")
+        n_joints = int(j.max()) + 1 if n else 1
+        d = N.PtxSkinDesc(mesh=int(mesh), first_vertex=int(first), n_vertices=n, n_joints=n_joints, n_targets=nt,
+                          joints=j.ctypes.data if n else None, weights=w.ctypes.data if n else None, bind=b,
+                          target_pos=tp, target_nrm=tn)
+        self._call("ptx_set_skin", self._h, ctypes.byref(d))
+        if n:
+            self._skins[int(mesh)] = (int(first), n, n_joints, nt)
+        else:
+            self._skins.pop(int(mesh), None)
+
+    def SkinVertices(self, mesh: int, palette, target_weights=None) -> None:
+        """Pose the skinned range of mesh `mesh` and refit its BLAS on the GPU (ptx_skin_vertices): `palette`
+        (J, 12) f32 with J at least the skin's joint count (1 + the largest bound index), `target_weights`
+        one f32 per bound morph target.  `compiled` is afterwards what the handle renders: the range's
+        records read_vertices()'s, the accel array read_accel()'s.  A refused call changes nothing."""
+        if int(mesh) not in self._skins:
+            raise ValueError(f"SkinVertices: mesh {mesh} has no skin")
+        first, n, n_joints, nt = self._skins[int(mesh)]
+        pal = np.ascontiguousarray(palette, dtype=np.float32).reshape(-1, 12)
+        if len(pal) < n_joints:
+            raise ValueError(f"SkinVertices: {len(pal)} matrices for {n_joints} joints")
+        tw = None if target_weights is None else np.ascontiguousarray(target_weights, dtype=np.float32).reshape(-1)
+        if (tw is None) != (nt == 0) or (tw is not None and len(tw) != nt):
+            raise ValueError(f"SkinVertices: the skin has {nt} morph targets")
+        self._call("ptx_skin_vertices", self._h, int(mesh), pal.ctypes.data, None if tw is None else tw.ctypes.data)
+        from .scene.world import STRIDE_VERTEX, mesh_blocks
+        cs = self.compiled
+        w0 = mesh_blocks(cs, int(mesh))["vertex"] + STRIDE_VERTEX * first
+        geometry = np.array(cs.geometry, dtype=np.uint32)
+        geometry[w0:w0 + STRIDE_VERTEX * n] = self.read_vertices(mesh, first, n).reshape(-1)
+        self.compiled = dataclasses.replace(cs, geometry=geometry, accel=self.read_accel())
+
+    def read_vertices(self, mesh: int, first: int = 0, n: int | None = None) -> np.ndarray:
+        """(n, 8) u32: the device's current records of vertices [first, first + n) of mesh `mesh`
+        (ptx_read_vertices; n None: to the end of the mesh's vertex block)."""
+        from .scene.world import STRIDE_VERTEX, mesh_blocks
+        if n is None:
+            b = mesh_blocks(self.compiled, int(mesh))
+            n = (b["vertex_end"] - b["vertex"]) // STRIDE_VERTEX - first
+        out = np.zeros((max(int(n), 0), STRIDE_VERTEX), dtype=np.uint32)
+        self._call("ptx_read_vertices", self._h, int(mesh), int(first), len(out), out.ctypes.data if len(out) else None)
         return out
 
     def Update(self) -> None:

@@ -50,6 +50,33 @@ class GltfPrimitive:
     material: GltfMaterial = field(default_factory=GltfMaterial)
 
 
+@dataclass
+class GltfSkinnedPrimitive:
+    """A skinned primitive as ptx_set_skin takes it (Glb.skinned_primitives)."""
+    primitive: GltfPrimitive         # baked: its positions and normals are the bind pose
+    joints: np.ndarray               # (V,4) u32, indices into joint_nodes
+    weights: np.ndarray              # (V,4) f32
+    inverse_bind: np.ndarray         # (J,4,4) f64, row-major
+    joint_nodes: list                # J node indices
+    mesh_world: np.ndarray           # (4,4) f64, row-major: the world matrix baked into `primitive`
+    node: int                        # the node that carries the mesh
+    target_pos: np.ndarray | None = None   # (T,V,3) f32, through mesh_world's linear part
+    target_nrm: np.ndarray | None = None
+
+
+def skin_palette(joint_world, inverse_bind, mesh_world) -> np.ndarray:
+    """(J, 12) f32, the palette of ptx_skin_vertices for a primitive of Glb.skinned_primitives:
+    joint_world_j . inverse_bind_j . mesh_world^-1 in f64, rounded once to f32, rows 0..2.  The loader
+    bakes mesh_world into the bind positions, so the palette takes it out again.  `joint_world` (J,4,4)
+    row-major f64 are the joints' world matrices of the pose (Glb.world_matrices()[joint_nodes])."""
+    jw = np.asarray(joint_world, dtype=np.float64).reshape(-1, 4, 4)
+    ib = np.asarray(inverse_bind, dtype=np.float64).reshape(-1, 4, 4)
+    if len(jw) != len(ib):
+        raise ValueError("one world matrix per inverse bind matrix")
+    inv = np.linalg.inv(np.asarray(mesh_world, dtype=np.float64).reshape(4, 4))
+    return (jw @ ib @ inv)[:, 0:3, :].reshape(-1, 12).astype(np.float32)
+
+
 def _compose(t, q, s) -> np.ndarray:
     """three.js Matrix4.compose(position, quaternion, scale): column-major 16 f64, the library's
     own operation order (so the JS host, js/gltf.js, computes the same bits)."""
@@ -245,6 +272,83 @@ class Glb:
         identity = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0]
         for root in scene["nodes"]:
             visit(root, identity)
+        return out
+
+    def world_matrices(self, local: dict | None = None) -> np.ndarray:
+        """(nodes, 4, 4) f64, row-major: every node's world matrix under the default scene, composed as
+        primitives() composes them.  `local` maps a node index to a replacement of its node object's
+        translation / rotation / scale (a pose: the host samples its animation and passes the result)."""
+        js = self.json
+        out = np.tile(np.eye(4), (len(js.get("nodes", [])), 1, 1))
+
+        def visit(node_idx: int, parent):
+            node = dict(js["nodes"][node_idx])
+            if local and node_idx in local:
+                node.pop("matrix", None)
+                node.update(local[node_idx])
+            world = _multiply(parent, _node_local_matrix(node))
+            out[node_idx] = np.array(world, dtype=np.float64).reshape(4, 4).T  # (column-major list)
+            for child in node.get("children", []):
+                visit(child, world)
+
+        identity = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0]
+        for root in js["scenes"][js.get("scene", 0)]["nodes"]:
+            visit(root, identity)
+        return out
+
+    def skinned_primitives(self) -> list[GltfSkinnedPrimitive]:
+        """Every primitive of a node with a `skin` that carries JOINTS_0 / WEIGHTS_0, in primitives()'
+        order: the baked primitive (the bind pose of ptx_set_skin), its joints and weights, the skin's
+        inverse bind matrices and joint nodes, the node's baked world matrix, and its morph targets'
+        POSITION / NORMAL deltas taken through that matrix's linear part (f64, stored as f32)."""
+        js = self.json
+        world = self.world_matrices()
+        out: list[GltfSkinnedPrimitive] = []
+
+        def visit(node_idx: int):
+            node = js["nodes"][node_idx]
+            if "mesh" in node and "skin" in node:
+                skin = js["skins"][node["skin"]]
+                n_joints = len(skin["joints"])
+                if "inverseBindMatrices" in skin:
+                    ibm = self.accessor(skin["inverseBindMatrices"]).astype(np.float64).reshape(-1, 4, 4).transpose(0, 2, 1)
+                else:
+                    ibm = np.tile(np.eye(4), (n_joints, 1, 1))
+                if len(ibm) != n_joints:
+                    raise ValueError("one inverse bind matrix per joint")
+                mw = world[node_idx]
+                col_major = [float(v) for v in mw.T.reshape(-1)]
+                for prim in js["meshes"][node["mesh"]]["primitives"]:
+                    attrs = prim["attributes"]
+                    if "JOINTS_0" not in attrs or "WEIGHTS_0" not in attrs:
+                        continue
+                    if prim.get("mode", 4) != 4:
+                        raise ValueError("only triangle lists are supported")
+                    joints = self.accessor(attrs["JOINTS_0"]).astype(np.uint32)
+                    weights = self.accessor(attrs["WEIGHTS_0"])
+                    if weights.dtype != np.float32:
+                        raise ValueError("normalized integer weights are not supported")
+                    if joints.size and joints.max() >= n_joints:
+                        raise ValueError("a joint index past the skin's joints")
+                    tp, tn = [], []
+                    lin = mw[0:3, 0:3]
+                    for t in prim.get("targets", []):
+                        n_v = len(joints)
+                        dp = self.accessor(t["POSITION"]).astype(np.float64) if "POSITION" in t else np.zeros((n_v, 3))
+                        tp.append((dp @ lin.T).astype(np.float32))
+                        if "NORMAL" in t:
+                            tn.append((self.accessor(t["NORMAL"]).astype(np.float64) @ lin.T).astype(np.float32))
+                    if tn and len(tn) != len(tp):
+                        raise ValueError("NORMAL deltas in some morph targets only")
+                    out.append(GltfSkinnedPrimitive(
+                        primitive=self._bake(prim, col_major), joints=joints, weights=weights, inverse_bind=ibm,
+                        joint_nodes=[int(j) for j in skin["joints"]], mesh_world=mw.copy(), node=node_idx,
+                        target_pos=np.stack(tp) if tp else None, target_nrm=np.stack(tn) if tn else None))
+            for child in node.get("children", []):
+                visit(child)
+
+        for root in js["scenes"][js.get("scene", 0)]["nodes"]:
+            visit(root)
         return out
 
     def _bake(self, prim, world) -> GltfPrimitive:

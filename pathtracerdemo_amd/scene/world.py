@@ -410,6 +410,16 @@ def refit_mesh(cs: CompiledScene, mesh: int, positions, normals=None, first: int
     return dataclasses.replace(cs, geometry=geometry, accel=accel)
 
 
+def skin_mesh(cs: CompiledScene, mesh: int, skin, palette, target_weights=None, first: int = 0) -> CompiledScene:
+    """The compiled scene with mesh `mesh` posed: its vertices [first, first + n) are skin.skin_vertices of
+    `skin` (a scene.skin.Skin bound to that range) under `palette` and `target_weights`, positions and
+    normals, and its BLAS is refitted to them -- refit_mesh of the rule's output, what ptx_skin_vertices
+    leaves on the device."""
+    from .skin import skin_vertices
+    pos, nrm = skin_vertices(skin.bind, skin.joints, skin.weights, palette, skin.target_pos, skin.target_nrm, target_weights)
+    return refit_mesh(cs, mesh, pos, nrm, first=first)
+
+
 def load_scene_json(name: str) -> dict:
     with open(os.path.join(SCENE_DIR, name + ".json")) as fh:
         return json.load(fh)
