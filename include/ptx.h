@@ -232,7 +232,9 @@ int ptx_update_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, uint3
  * serves the next frame only if its camera words are those of the frame that wrote it; the history of
  * ptx_upsample_temporal is dropped.  The temporal history of ptx_denoise stays and is looked up as for
  * an unchanged instance: it does not follow vertices, so a deformed surface keeps the history of the
- * pixels it covered.  The accumulation is not reset.  Band handles and handles with a communicator:
+ * pixels it covered -- unless the handle's last temporal call asked to follow them
+ * (ptx_denoise_params.reserved[2], "Vertex motion" under ptx_denoise): then this call first saves the
+ * mesh's triangle records as that call saw them.  The accumulation is not reset.  Band handles and handles with a communicator:
  * every band / rank makes the same call, nothing is exchanged.
  * Refused before the GPU is touched, the next frame being the unedited one: PTX_E_INVALID -- a null
  * handle, a null array with n_vertices > 0, no scene, no frame set or no layout, a range past the
@@ -447,13 +449,39 @@ int ptx_present_poll(ptx_handle *h, uint8_t *out, size_t bytes);
  * renormalised) are where its point and normal were, Q is reprojected through the previous call's VP
  * whether or not the camera words changed, taps and weights as above, and a tap is tested against
  * Nq (dot >= 0.9) and Q (|dot(Nq, P' - Q)| <= this pixel's r).
- * Launches: 3 + iterations (guide records, dn_temporal, variance, the iterations). */
+ *   Vertex motion (reserved[2] = 1, "follow vertices"; opt-in: with 0 every call is the one above, bit for
+ * bit).  Tracking: a temporal call with reserved[2] = 1 that is enqueued completely leaves the handle
+ * tracking, one with reserved[2] = 0 not tracking; reserved[2] > 1 is PTX_E_INVALID before the GPU is
+ * touched; reserved[2] = 1 without the temporal mode is ignored, as reserved[1] is.  Snapshot: while a
+ * handle is tracking and holds a temporal state, the first ptx_update_vertices / ptx_skin_vertices on a
+ * mesh since that call saves the mesh's triangle records (the 80 bytes per triangle the refit rewrites:
+ * three positions and normals) before the refit overwrites them -- a device-to-device copy on the call's
+ * stream, no launch, PTX_STAT_REFIT counts what it counted -- and marks the mesh deformed; later updates
+ * of the mesh before the next temporal call save nothing, so the snapshot is the shape the previous
+ * temporal call saw.  The buffer (80 bytes per triangle of the scene) is allocated by the first call with
+ * reserved[2] = 1 and counted in device_bytes.  At the next temporal call with reserved[2] = 1 every
+ * instance whose mesh word equals the previous call's and whose mesh is marked gets flag 3, whatever
+ * happened to its matrices (no rigidity is needed: a rescaled instance follows too); a switched mesh
+ * stays flag 2; instances of meshes not marked keep flags 0 / 1 / 2 as above; then the marks are cleared
+ * (a call with reserved[2] = 0 clears them unused and is the call above).  A pixel with a primary hit of
+ * a flag-3 instance: Q and Nq are GetSurface's position and normalised normal of the pixel's current
+ * G-buffer texel (instance, triangle, barycentrics) evaluated on the snapshot's triangle record under the
+ * previous call's instance matrices (words 0..15 and 16..31 of the kept block) -- the surface point where
+ * it was at that call; Q is always reprojected through that call's VP, as for flag 1, and taps, weights,
+ * the n' >= 1, key, normal and plane tests (this pixel's r), the integration and a band's clip count are
+ * unchanged.  With no mesh marked, a call with reserved[2] = 1 runs the kernels and gives the bits of the
+ * same call with reserved[2] = 0.  ptx_upload_scene, ptx_reset_accumulation and everything else that drops
+ * the temporal state drop the marks with it; a layout derived again by ptx_set_frame between two calls
+ * moves the records, so the marked meshes' instances get flag 2 for that one call.  ptx_upsample_temporal
+ * does not follow vertices and keeps dropping its history on a vertex update.
+ * Launches: 3 + iterations (guide records, dn_temporal, variance, the iterations), following or not. */
 typedef struct ptx_denoise_params {
     uint32_t iterations;      /* 1..6 (step 2^i in iteration i); 0 = default 5 */
     float sigma_lum;          /* luminance edge stop, in standard deviations; 0 = default 4 */
     float sigma_plane;        /* plane-distance edge stop, as a fraction of the distance to the camera; 0 = default 0.02 */
     uint32_t reserved[5];     /* [0] temporal: 0 = off, 1 = on; [1] alpha_min, the bit pattern of an f32: 0 = default
-                                 0.05, else finite and in (0, 1] (read in temporal mode only); [2..4] zero */
+                                 0.05, else finite and in (0, 1] (read in temporal mode only); [2] follow vertices:
+                                 0 = off, 1 = on (used in temporal mode only); [3..4] zero */
 } ptx_denoise_params;
 int ptx_denoise(ptx_handle *h, const ptx_denoise_params *p /* NULL = defaults */);
 /* The same filter on a frame split into row bands.  handles: band handles in band order that cover
@@ -490,7 +518,8 @@ int ptx_denoise(ptx_handle *h, const ptx_denoise_params *p /* NULL = defaults */
  * and in general a band's new {C, m1, m2, n} on its own rows is the whole-image definition with the
  * previous state's n' zeroed outside that band's window.  ptx_upload_scene and
  * ptx_reset_accumulation drop a band's state as ever; it then starts without history, and its
- * neighbours see n = 1 (n = 0 at misses) in the rows it sends. */
+ * neighbours see n = 1 (n = 0 at misses) in the rows it sends.  reserved[2] (follow vertices) goes to every
+ * band: each tracks, saves and marks for itself, since every band makes the same vertex calls. */
 int ptx_denoise_bands(ptx_handle *const *handles, int n, const ptx_denoise_params *p /* NULL = defaults */);
 /* Guided upsampling (Upsampling): the denoised image of `lo`, a whole-image handle of
  * w x h after at least one ptx_denoise (spatial or temporal), written at the size W x H = s*w x s*h

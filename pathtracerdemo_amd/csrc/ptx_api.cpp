@@ -590,6 +590,7 @@ int build_layout(ptx_handle *h) {
     if ((size_t)h->stack_depth * kBlock * 4u > 160u * 1024u)
         return fail(h, PTX_E_SCENE, "BLAS depth %u needs more LDS than a CU has", max_depth);
     h->layout_valid = true;
+    h->layout_gen += 1u;  // (the denoiser's saved triangle records lie at the previous layout's offsets)
     for (auto &c : h->ctx) c.surf_valid = false;  // the surface records name the old layout's materials
     gbuf_key_drop_all(h);  // (the G-buffers hold hits in the old layout)
     return PTX_OK;
@@ -1682,6 +1683,9 @@ int denoise_params(ptx_handle *h, const ptx_denoise_params *p, DnCall &c, const 
     c.temporal = p ? p->reserved[0] : 0u;
     c.alpha_min = 0.05f;
     if (c.temporal > 1u) return fail(h, PTX_E_INVALID, "%s: temporal %u (0 or 1)", what, c.temporal);
+    // follow vertices: reserved[2] (like alpha_min read in temporal mode only)
+    if (p && p->reserved[2] > 1u) return fail(h, PTX_E_INVALID, "%s: follow vertices %u (0 or 1)", what, p->reserved[2]);
+    c.follow = p && c.temporal ? p->reserved[2] : 0u;
     if (c.temporal) {
         if (p->reserved[1]) std::memcpy(&c.alpha_min, &p->reserved[1], sizeof c.alpha_min);
         if (!(c.alpha_min > 0.0f && c.alpha_min <= 1.0f))
@@ -1725,6 +1729,11 @@ int denoise_alloc(ptx_handle *h, const DnCall &c) {
             if (int rc = alloc_buf(h, h->d_dn_hist[k], px * 16u)) return rc;
             if (int rc = alloc_buf(h, h->d_dn_mom[k], px * 8u)) return rc;
         }
+    }
+    if (c.follow && h->d_dn_snap.bytes != h->d_tverts.bytes) {  // the snapshot: 80 B per triangle of the scene
+        if (int rc = alloc_buf(h, h->d_dn_snap, h->d_tverts.bytes)) return rc;
+        for (uint8_t &m : h->dn_deformed)  // (another size: a layout derived since; what was saved is gone)
+            if (m) m = 2u;
     }
     return PTX_OK;
 }
@@ -1830,11 +1839,50 @@ int denoise_front(ptx_handle *h, const DnCall &c, DnBand &b) {
         const size_t ppx = (size_t)(plo - buf0) * W;
         // object motion: an instance whose 33 words differ from the previous call's snapshot
         const DnObj *obj = nullptr;
+        DnVerts verts;
         const size_t iw = (size_t)STRIDE_INSTANCE * h->n_inst;
-        if (mode && iw <= h->scene.size() && h->dn_insts.size() == iw &&
-            std::memcmp(h->dn_insts.data(), h->scene.data(), iw * 4u) != 0) {
-            const std::vector<DnObj> table = denoise_objects(h->dn_insts.data(), h->scene.data(), h->n_inst);
-            if (int rc = upload(h, h->d_dn_obj, table.data(), table.size() * sizeof(DnObj))) return rc;
+        const bool kept = mode && iw <= h->scene.size() && h->dn_insts.size() == iw;
+        const bool edited = kept && std::memcmp(h->dn_insts.data(), h->scene.data(), iw * 4u) != 0;
+        // vertex motion: an instance of a mesh marked deformed since the previous call (refit_after_vertices)
+        std::vector<uint8_t> inst_mark(c.follow && kept ? h->n_inst : 0u, 0u);
+        bool deformed = false;
+        for (uint32_t i = 0; i < (uint32_t)inst_mark.size(); ++i) {
+            const uint32_t mesh = h->scene[(size_t)STRIDE_INSTANCE * i + 32u];
+            if (mesh != h->dn_insts[(size_t)STRIDE_INSTANCE * i + 32u] || mesh >= h->dn_deformed.size()) continue;
+            inst_mark[i] = h->dn_deformed[mesh];
+            deformed = deformed || inst_mark[i] != 0u;
+        }
+        if (edited || deformed) {
+            std::vector<DnObj> table = edited ? denoise_objects(h->dn_insts.data(), h->scene.data(), h->n_inst)
+                                              : std::vector<DnObj>(h->n_inst, DnObj{});
+            if (!deformed) {
+                if (int rc = upload(h, h->d_dn_obj, table.data(), table.size() * sizeof(DnObj))) return rc;
+            } else {
+                // flag 3 whatever became of the matrices; 2 where the records were not saved or the layout
+                // they were saved under is no longer the handle's
+                const bool usable = h->dn_track_layout == h->layout_gen && h->d_dn_snap.bytes == h->d_tverts.bytes;
+                std::vector<DnPrev> prev(h->n_inst, DnPrev{});
+                static const float kId[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+                for (uint32_t i = 0; i < h->n_inst; ++i) {
+                    if (!inst_mark[i]) continue;
+                    table[i].flag = usable && inst_mark[i] == 1u ? 3u : 2u;
+                    const uint32_t *p = h->dn_insts.data() + (size_t)STRIDE_INSTANCE * i;
+                    DnPrev &I = prev[i];
+                    std::memcpy(I.m, p, 64);
+                    std::memcpy(I.minv, p + 16, 64);
+                    I.mesh = p[32];
+                    I.tri_base = I.mesh < h->lay_mesh_tri_base.size() ? h->lay_mesh_tri_base[I.mesh] : 0u;
+                    if (!std::memcmp(I.m, kId, sizeof kId) && !std::memcmp(I.minv, kId, sizeof kId)) I.mesh |= kInstIdentity;
+                }
+                const size_t nb = table.size() * sizeof(DnObj);
+                std::vector<unsigned char> both(nb + prev.size() * sizeof(DnPrev));
+                std::memcpy(both.data(), table.data(), nb);
+                std::memcpy(both.data() + nb, prev.data(), prev.size() * sizeof(DnPrev));
+                if (int rc = upload(h, h->d_dn_obj, both.data(), both.size())) return rc;
+                verts.gbuf = gbuf_band(h);
+                verts.prev = (const DnPrev *)((const char *)h->d_dn_obj.p + nb);
+                verts.snap = (const float4 *)h->d_dn_snap.p;
+            }
             obj = (const DnObj *)h->d_dn_obj.p;
         }
         e = denoise_timed(h, st, e, [&] {
@@ -1843,7 +1891,7 @@ int denoise_front(ptx_handle *h, const DnCall &c, DnBand &b) {
                                            (const float4 *)h->d_dn_guide_prev.p + 2u * ppx,
                                            (const float4 *)h->d_dn_hist[rd].p + ppx, (const float2 *)h->d_dn_mom[rd].p + ppx,
                                            (float4 *)h->d_dn_hist[b.wr].p + wpx, (float2 *)h->d_dn_mom[b.wr].p + wpx,
-                                           (unsigned long long *)h->d_counters.p + CNT_DENOISE_CLIP, obj, h->n_inst, st);
+                                           (unsigned long long *)h->d_counters.p + CNT_DENOISE_CLIP, obj, h->n_inst, verts, st);
         });
     }
     if (e != hipSuccess) return fail(h, PTX_E_HIP, "denoiser launch: %s", hipGetErrorString(e));
@@ -1898,6 +1946,10 @@ int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b) {
         std::memcpy(vpinv, h->dn_camera, sizeof vpinv);
         mat4_inverse(vpinv, h->dn_vp);
         h->dn_hist_valid = true;
+        // vertex motion: the marks are this call's to use, used or not; the next update saves again
+        h->dn_deformed.clear();
+        h->dn_track = c.follow != 0u;
+        h->dn_track_layout = h->layout_gen;
     }
     return PTX_OK;
 }
@@ -2248,6 +2300,7 @@ int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const
     h->drawn = false;
     h->hist_valid = false;
     h->dn_hist_valid = false;  // (the denoiser's history shows the old scene)
+    h->dn_deformed.clear();    // (its marks name the old scene's meshes; without a state nothing reads them)
     h->ut_valid = false;       // (and ptx_upsample_temporal's)
     h->cur().init_state_valid = false;
     h->cur().nbr_valid = false;
@@ -2388,6 +2441,20 @@ static int refit_after_vertices(ptx_handle *h, uint32_t mesh, hipError_t le, uin
     m.n_tris = h->lay_mesh_ntris[mesh];
     m.sub_base = h->lay_mesh_sub_base[mesh];
     m.n_subs = h->lay_mesh_nsub[mesh];
+    // a tracking denoiser (include/ptx.h ptx_denoise, "Vertex motion"): the first update of the mesh since its
+    // last temporal call keeps the triangle records that call saw -- a copy on the stream, ahead of the kernel
+    // that overwrites them (every stream of the handle is idle: the callers' quiesce)
+    if (le == hipSuccess && h->dn_track && h->dn_hist_valid) {
+        h->dn_deformed.resize(h->lay_mesh_nsub.size(), 0u);
+        if (!h->dn_deformed[mesh]) {
+            const size_t off = 80u * (size_t)m.tri_base, nb = 80u * (size_t)m.n_tris;
+            const bool fits = h->d_dn_snap.p && h->d_dn_snap.bytes == h->d_tverts.bytes && off + nb <= h->d_dn_snap.bytes &&
+                              h->dn_track_layout == h->layout_gen;
+            if (fits && nb)
+                le = hipMemcpyAsync((char *)h->d_dn_snap.p + off, (const char *)h->d_tverts.p + off, nb, hipMemcpyDeviceToDevice, st);
+            h->dn_deformed[mesh] = fits ? 1u : 2u;
+        }
+    }
     le = slot_timed(h, PTX_STAT_REFIT, st, le, [&] { return launch_refit_tris(m, st); });
     const auto &lv = h->lay_mesh_levels[mesh];  // lowest height first: a pair's interior children are lower
     for (size_t k = 0; k + 1 < lv.size(); ++k)
@@ -2416,8 +2483,9 @@ static int refit_after_vertices(ptx_handle *h, uint32_t mesh, hipError_t le, uin
     h->drawn = h->rendered = false;
     h->hist_same_only = true;
     if (h->hist_moved) h->hist_valid = false;
-    h->ut_valid = false;  // (ptx_upsample_temporal does not follow vertices; neither does ptx_denoise's temporal mode,
-                          //  whose history stays and is looked up as for an unchanged instance)
+    h->ut_valid = false;  // (ptx_upsample_temporal does not follow vertices; neither does ptx_denoise's temporal mode
+                          //  unless the handle is tracking, above: its history stays and is looked up as for an
+                          //  unchanged instance)
     return PTX_OK;
 }
 
@@ -2798,7 +2866,7 @@ int ptx_get_stats(ptx_handle *h, ptx_stats *out) {
                         c.surf.bytes + h->d_psurf.bytes + c.direct.bytes + h->d_dn_guide.bytes + h->d_dn_work.bytes +
                         h->d_denoised.bytes + h->d_frame_color.bytes + h->d_dn_guide_prev.bytes + h->d_dn_hist[0].bytes +
                         h->d_dn_hist[1].bytes + h->d_dn_mom[0].bytes + h->d_dn_mom[1].bytes + h->d_dn_halo_g.bytes +
-                        h->d_dn_halo_c.bytes + h->d_dn_obj.bytes + h->d_up_halo.bytes + h->d_ut_guide[0].bytes + h->d_ut_guide[1].bytes +
+                        h->d_dn_halo_c.bytes + h->d_dn_obj.bytes + h->d_dn_snap.bytes + h->d_up_halo.bytes + h->d_ut_guide[0].bytes + h->d_ut_guide[1].bytes +
                         h->d_ut_hist[0].bytes + h->d_ut_hist[1].bytes + h->d_refit_order.bytes + h->d_refit_box.bytes;
     for (const auto &k : h->skins) out->device_bytes += k.bind.bytes + k.target_pos.bytes + k.target_nrm.bytes + k.pose.bytes;
     return PTX_OK;
@@ -3200,7 +3268,7 @@ int ptx_destroy(ptx_handle *h) {
                       &h->d_insts, &h->d_mats, &h->d_tverts, &h->d_accum, &h->d_counters, &h->d_qrays, &h->d_qhits, &h->d_qcnt, &h->d_hist,
                       &h->d_jstate, &h->d_jres, &h->d_replay, &h->d_psurf, &h->d_census, &h->d_wgt, &h->d_dn_guide, &h->d_dn_work,
                       &h->d_denoised, &h->d_frame_color, &h->d_dn_guide_prev, &h->d_dn_hist[0], &h->d_dn_hist[1], &h->d_dn_mom[0],
-                      &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_dn_obj, &h->d_up_halo, &h->d_ut_guide[0], &h->d_ut_guide[1],
+                      &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_dn_obj, &h->d_dn_snap, &h->d_up_halo, &h->d_ut_guide[0], &h->d_ut_guide[1],
                       &h->d_ut_hist[0], &h->d_ut_hist[1], &h->d_refit_order, &h->d_refit_box})
         free_buf(*b);
     drop_skins(h);

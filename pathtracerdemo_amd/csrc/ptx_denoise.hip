@@ -5,7 +5,8 @@
 // All kernels one lane per pixel; the only atomics are dn_temporal's and dn_upsample_temporal_win's
 // counts of clipped pixels, one add per wave that has any:
 //   dn_guide     G-buffer texel -> 32-byte guide record {P.xyz, key | kDnMiss}{N.xyz, r}
-//   dn_temporal  (temporal mode) history lookup + integration -> history {C.rgb, n}, moments {m1, m2}
+//   dn_temporal  (temporal mode) history lookup + integration -> history {C.rgb, n}, moments {m1, m2};
+//                dn_temporal_verts: the same for a call that follows deformed meshes (tests/denoise_follow_ref.py)
 //   dn_variance  7x7 guide-weighted luminance moments -> working image {r, g, b, v}; <true>: on the
 //                history, the integrated moments' variance where n >= 4
 //   dn_atrous    one iteration at step 2^i on the working image (ping-pong); steps 1, 2, 4 stage
@@ -131,6 +132,16 @@ struct DnHistory {
 constexpr float kDnNMax = 255.0f;    // the history length saturates here
 constexpr float kDnNMoments = 4.0f;  // from this length on the variance comes from the integrated moments
 
+// inst_point / inst_point_t for a kept instance record (DnPrev::mesh carries kInstIdentity as Inst::mesh does).
+__device__ __forceinline__ f3 dn_prev_point(bool identity, const float *m, f3 p) {
+    if (identity && finite3(p)) return f3{p.x + 0.0f, p.y + 0.0f, p.z + 0.0f};
+    return xform_point(m, p);
+}
+__device__ __forceinline__ f3 dn_prev_point_t(bool identity, const float *m, f3 p) {
+    if (identity && finite3(p)) return f3{p.x + 0.0f, p.y + 0.0f, p.z + 0.0f};
+    return xform_point_t(m, p);
+}
+
 // History lookup and integration of one pixel: reads this frame's guide record and colour and up to
 // four previous guide / history / moment records, writes the new history {C.rgb, n} and moments
 // {m1, m2}.  Pixels are projected in the W x H frame's coordinates (the window's row 0 is its row
@@ -145,14 +156,20 @@ constexpr float kDnNMoments = 4.0f;  // from this length on the variance comes f
 // flag 2 no lookup (n = 1); flag 1 the instance moved rigidly -- the hit point and normal go through
 // D = M_prev * Minv_cur to where they were at the previous call, Q and Nq (not renormalised), Q is
 // always reprojected through vp, the same camera or not, and the taps are tested against Q and Nq.
-template <bool OBJ>
-__global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, const DnWin win, const DnHistory Hs,
-                                                      const float4 *__restrict__ guide, const float4 *__restrict__ frame,
-                                                      const float4 *__restrict__ accum, const float4 *__restrict__ pguide,
-                                                      const float4 *__restrict__ phist, const float2 *__restrict__ pmom,
-                                                      float4 *__restrict__ hist, float2 *__restrict__ mom,
-                                                      unsigned long long *__restrict__ clip,
-                                                      const DnObj *__restrict__ obj, uint32_t n_obj) {
+// VERTS (a call that finds a mesh deformed since the previous one, "Vertex motion"): flag 3 -- Q and Nq are
+// get_surface's position and normalised normal of the pixel's G-buffer texel `g` (gbuf starts at row c0 of
+// the window, like frame) on the previous call's geometry: the triangle record saved before the refit
+// (snap: Scene::tverts' layout and indices) under that call's instance matrices (prev[inst]); then as flag 1.
+template <bool OBJ, bool VERTS>
+__device__ __forceinline__ void dn_temporal_px(uint32_t W, uint32_t H, const DnWin &win, const DnHistory &Hs,
+                                               const float4 *__restrict__ guide, const float4 *__restrict__ frame,
+                                               const float4 *__restrict__ accum, const float4 *__restrict__ pguide,
+                                               const float4 *__restrict__ phist, const float2 *__restrict__ pmom,
+                                               float4 *__restrict__ hist, float2 *__restrict__ mom,
+                                               unsigned long long *__restrict__ clip,
+                                               const DnObj *__restrict__ obj, uint32_t n_obj,
+                                               const uint4 *__restrict__ gbuf, const DnPrev *__restrict__ prev,
+                                               const float4 *__restrict__ snap) {
     const uint32_t x = blockIdx.x * kDnTile + (threadIdx.x & 15u), y = win.c0 + blockIdx.y * kDnTile + (threadIdx.x >> 4);
     if (x >= W || y >= win.c1) return;
     const size_t pix = (size_t)y * W + x, own = (size_t)(y - win.c0) * W + x;
@@ -165,6 +182,8 @@ __global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, co
         return;
     }
     const float4 b = guide[2u * pix + 1u];
+    uint4 g = make_uint4(0u, 0u, 0u, 0u);
+    if (VERTS) g = gbuf[own];  // (issued with the guide and colour loads: the snapshot record's address hangs on it)
     const f3 F = rgb(frame[own]), Pp = rgb(a), Np = rgb(b);
     const float l = luminance(F);
     f3 C = F;
@@ -174,6 +193,18 @@ __global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, co
     if (OBJ) {
         const uint32_t inst = key >> 16;
         if (Hs.mode != 0u && inst < n_obj) flag = obj[inst].flag;
+        if (VERTS && flag == 3u) {
+            const DnPrev &I = prev[inst];
+            const float4 *q = snap + 5u * (size_t)(I.tri_base + g.y);
+            const float4 ta = q[0], tb = q[1], tc = q[2], td = q[3], te = q[4];  // (tri_verts' record)
+            const bool id = (I.mesh & kInstIdentity) != 0u;
+            const f3 p0 = dn_prev_point(id, I.m, mk(ta.x, ta.y, ta.z)), n0 = dn_prev_point_t(id, I.minv, mk(ta.w, tb.x, tb.y));
+            const f3 p1 = dn_prev_point(id, I.m, mk(tb.z, tb.w, tc.x)), n1 = dn_prev_point_t(id, I.minv, mk(tc.y, tc.z, tc.w));
+            const f3 p2 = dn_prev_point(id, I.m, mk(td.x, td.y, td.z)), n2 = dn_prev_point_t(id, I.minv, mk(td.w, te.x, te.y));
+            const float bu = asf(g.z), bv = asf(g.w), bw = 1.0f - bu - bv;
+            Nq = normalize((n0 * bu + n1 * bv) + n2 * bw);
+            Q = (p0 * bu + p1 * bv) + p2 * bw;
+        }
         if (flag == 1u) {
             const float *d = obj[inst].d;
             Q.x = ((d[0] * Pp.x + d[4] * Pp.y) + d[8] * Pp.z) + d[12];
@@ -191,7 +222,7 @@ __global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, co
         bool in[4], clipped = false;
         // this pixel in the previous state (a band's own rows are always covered)
         const size_t pc = (size_t)(win.y0 + y - Hs.y0) * W + x;
-        if (Hs.mode == 1u && !(OBJ && flag == 1u)) {
+        if (Hs.mode == 1u && !(OBJ && flag == 1u) && !(VERTS && flag == 3u)) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) { q[k] = pc; w[k] = 1.0f; in[k] = k == 0; }
         } else {
@@ -253,6 +284,31 @@ __global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, co
     }
     hist[pix] = make_float4(C.x, C.y, C.z, n);
     mom[pix] = make_float2(m1, m2);
+}
+template <bool OBJ>
+__global__ __launch_bounds__(kBlock) void dn_temporal(uint32_t W, uint32_t H, const DnWin win, const DnHistory Hs,
+                                                      const float4 *__restrict__ guide, const float4 *__restrict__ frame,
+                                                      const float4 *__restrict__ accum, const float4 *__restrict__ pguide,
+                                                      const float4 *__restrict__ phist, const float2 *__restrict__ pmom,
+                                                      float4 *__restrict__ hist, float2 *__restrict__ mom,
+                                                      unsigned long long *__restrict__ clip,
+                                                      const DnObj *__restrict__ obj, uint32_t n_obj) {
+    dn_temporal_px<OBJ, false>(W, H, win, Hs, guide, frame, accum, pguide, phist, pmom, hist, mom, clip, obj, n_obj, nullptr,
+                               nullptr, nullptr);
+}
+// The instance that follows vertices: also the pixel's G-buffer texel (16 B) and, on a flag-3 pixel, the
+// previous call's instance record (DnPrev) and the 80-byte snapshot record.
+__global__ __launch_bounds__(kBlock) void dn_temporal_verts(uint32_t W, uint32_t H, const DnWin win, const DnHistory Hs,
+                                                            const float4 *__restrict__ guide, const float4 *__restrict__ frame,
+                                                            const float4 *__restrict__ accum, const float4 *__restrict__ pguide,
+                                                            const float4 *__restrict__ phist, const float2 *__restrict__ pmom,
+                                                            float4 *__restrict__ hist, float2 *__restrict__ mom,
+                                                            unsigned long long *__restrict__ clip,
+                                                            const DnObj *__restrict__ obj, uint32_t n_obj,
+                                                            const uint4 *__restrict__ gbuf, const DnPrev *__restrict__ prev,
+                                                            const float4 *__restrict__ snap) {
+    dn_temporal_px<true, true>(W, H, win, Hs, guide, frame, accum, pguide, phist, pmom, hist, mom, clip, obj, n_obj, gbuf, prev,
+                               snap);
 }
 
 // ---------------------------------------------------------------- variance pass
@@ -807,14 +863,18 @@ hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const DnWin &win, con
                                    uint32_t mode, uint32_t prev_y0, uint32_t prev_rows, const float4 *guide,
                                    const float4 *frame, const float4 *accum, const float4 *pguide, const float4 *phist,
                                    const float2 *pmom, float4 *hist, float2 *mom, unsigned long long *clip,
-                                   const DnObj *obj, uint32_t n_obj, hipStream_t s) {
+                                   const DnObj *obj, uint32_t n_obj, const DnVerts &verts, hipStream_t s) {
     DnHistory Hs{};
     for (int i = 0; i < 16; ++i) Hs.vp[i] = vp_prev[i];
     Hs.alpha_min = alpha_min;
     Hs.mode = mode;
     Hs.y0 = prev_y0;
     Hs.rows = prev_rows;
-    if (obj)
+    if (verts.snap) {
+        if (!obj || !verts.gbuf || !verts.prev) return hipErrorInvalidValue;  // (flag 3 lives in obj)
+        hipLaunchKernelGGL(dn_temporal_verts, dn_grid(W, win), dim3(kBlock), 0, s, W, H, win, Hs, guide, frame, accum, pguide,
+                           phist, pmom, hist, mom, clip, obj, n_obj, verts.gbuf, verts.prev, verts.snap);
+    } else if (obj)
         hipLaunchKernelGGL(dn_temporal<true>, dn_grid(W, win), dim3(kBlock), 0, s, W, H, win, Hs, guide, frame, accum, pguide,
                            phist, pmom, hist, mom, clip, obj, n_obj);
     else

@@ -239,6 +239,16 @@ struct ptx_handle {
     // object-motion table of a call that finds it changed (DnObj per instance: dn_temporal<true>)
     std::vector<uint32_t> dn_insts;
     DevBuf d_dn_obj;
+    // following vertices (ptx_denoise_params.reserved[2], include/ptx.h "Vertex motion").  dn_track: the last
+    // temporal call asked for it, under layout dn_track_layout (layout_gen then).  d_dn_snap (d_tverts' layout,
+    // allocated by the first such call): while tracking, refit_after_vertices saves a mesh's triangle records
+    // there before the first refit since that call overwrites them, and marks the mesh in dn_deformed (1 saved,
+    // 2 not saved: no history); the next temporal call uses the marks and clears them.  A call that follows
+    // uploads the instances as the previous call saw them (DnPrev) behind d_dn_obj's DnObj entries.
+    bool dn_track = false;
+    uint32_t dn_track_layout = 0, layout_gen = 0;  // layout_gen: build_layout's count
+    DevBuf d_dn_snap;
+    std::vector<uint8_t> dn_deformed;
     // ptx_denoise_bands: a band filters the window of its rows and up to 2^(n+1) halo rows on either
     // side, so the denoiser's buffers of a band handle hold dn_cap_top + band_h + dn_cap_bot rows (the
     // 128 rows of 6 iterations, or what the frame has: row 0 of a buffer is row
@@ -350,7 +360,7 @@ int first_frame_ctx(ptx_handle *h);
 // The denoiser's host side (ptx_api.cpp), shared by ptx_denoise and ptx_denoise_bands (ptx_comm.cpp).
 // One call's parameters, and per band its window: `top` / `bot` halo rows this call uses.
 struct DnCall {
-    uint32_t n = 5, temporal = 0;
+    uint32_t n = 5, temporal = 0, follow = 0;  // follow: reserved[2], read in temporal mode only
     float sigma_lum = 4.0f, sigma_plane = 0.02f, alpha_min = 0.05f;
 };
 struct DnBand {

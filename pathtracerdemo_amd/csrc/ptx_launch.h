@@ -83,14 +83,29 @@ hipError_t launch_denoise_atrous(uint32_t W, const DnWin &win, uint32_t step, co
 // instance -- how its pixels find their history (dn_temporal<true>, ptx_denoise.hip)
 struct DnObj {
     float d[16];    // column-major D = M_prev * Minv_cur: a point of the instance now -> at the previous call
-    uint32_t flag;  // 0 unchanged, 1 moved rigidly (follow D), 2 anything else (no history)
+    uint32_t flag;  // 0 unchanged, 1 moved rigidly (follow D), 2 anything else (no history); 3 its mesh was deformed
+                    // (dn_temporal_verts alone: follow the vertices)
     uint32_t pad[3];
+};
+// Following vertices (a call that finds a mesh deformed since the previous one, dn_temporal_verts): a second
+// table beside obj, an instance as the previous call saw it, in the device Inst's form; the band's G-buffer
+// texels (from its first row, like frame); and the triangle records saved before the refits, Scene::tverts'
+// layout.  snap == nullptr: the two kernels above.
+struct DnPrev {
+    float m[16], minv[16];    // words 0..15 and 16..31 of the kept instance block
+    uint32_t mesh, tri_base;  // mesh | kInstIdentity as in Inst (inst_point's shortcut); the mesh's first triangle record
+    uint32_t pad[2];
+};
+struct DnVerts {
+    const uint4 *gbuf = nullptr;
+    const DnPrev *prev = nullptr;
+    const float4 *snap = nullptr;
 };
 hipError_t launch_denoise_temporal(uint32_t W, uint32_t H, const DnWin &win, const float *vp_prev, float alpha_min,
                                    uint32_t mode, uint32_t prev_y0, uint32_t prev_rows, const float4 *guide,
                                    const float4 *frame, const float4 *accum, const float4 *pguide, const float4 *phist,
                                    const float2 *pmom, float4 *hist, float2 *mom, unsigned long long *clip,
-                                   const DnObj *obj, uint32_t n_obj, hipStream_t s);
+                                   const DnObj *obj, uint32_t n_obj, const DnVerts &verts, hipStream_t s);
 hipError_t launch_denoise_variance_moments(uint32_t W, const DnWin &win, const float4 *hist, const float2 *mom,
                                            const float4 *guide, float4 *out, hipStream_t s);
 // ptx_upsample: the (W / s) x (H / s) image `color_lo` with its guide records, written at W x H under

@@ -333,10 +333,12 @@ class NativeRenderer {
 
   /**
    * ptx_denoise behind the frame last rendered (include/ptx.h): {iterations, sigmaLum, sigmaPlane,
-   * temporal, alphaMin}, every field optional (0 = the default).  temporal: the frame colours
-   * integrated over the calls, their history reprojected across camera moves (a renderer made with
-   * {frameColor: true}); a ResetFrameCount() keeps that history.  With the source 'denoised' the
-   * canvas is painted from the result.
+   * temporal, alphaMin, followVertices}, every field optional (0 = the default).  temporal: the frame
+   * colours integrated over the calls, their history reprojected across camera moves (a renderer made
+   * with {frameColor: true}); a ResetFrameCount() keeps that history.  followVertices (with temporal): a
+   * pixel on a mesh that UpdateVertices / SkinVertices deformed since the previous temporal call looks its
+   * history up where that surface point was then.  With the source 'denoised' the canvas is painted from
+   * the result.
    */
   Denoise(opts) {
     addon.denoise(this.Handle, opts || {});

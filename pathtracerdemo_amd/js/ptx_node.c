@@ -898,9 +898,9 @@ static int get_f32_prop(napi_env env, napi_value obj, const char *name, float *o
     return 0;
 }
 
-/* denoise(handle, {iterations, sigmaLum, sigmaPlane, temporal, alphaMin}): ptx_denoise behind the frame
- * last rendered (include/ptx.h; every field optional, 0 = the default; temporal needs a handle
- * created with PTX_FLAG_FRAME_COLOR) */
+/* denoise(handle, {iterations, sigmaLum, sigmaPlane, temporal, alphaMin, followVertices}): ptx_denoise behind
+ * the frame last rendered (include/ptx.h; every field optional, 0 = the default; temporal needs a handle
+ * created with PTX_FLAG_FRAME_COLOR; followVertices: reserved[2], the temporal history follows deformed meshes) */
 static napi_value js_denoise(napi_env env, napi_callback_info info) {
     size_t argc = 2;
     napi_value argv[2];
@@ -913,17 +913,20 @@ static napi_value js_denoise(napi_env env, napi_callback_info info) {
     if (argc >= 2) napi_typeof(env, argv[1], &t);
     if (t == napi_object) {
         float alpha_min = 0.0f;
-        bool temporal = false;
-        napi_value tv;
+        bool temporal = false, follow = false;
+        napi_value tv, fv;
         if (get_u32_prop(env, argv[1], "iterations", 0, &p.iterations) || get_f32_prop(env, argv[1], "sigmaLum", &p.sigma_lum) ||
             get_f32_prop(env, argv[1], "sigmaPlane", &p.sigma_plane) || get_f32_prop(env, argv[1], "alphaMin", &alpha_min) ||
             napi_get_named_property(env, argv[1], "temporal", &tv) != napi_ok ||
-            napi_coerce_to_bool(env, tv, &tv) != napi_ok || napi_get_value_bool(env, tv, &temporal) != napi_ok) {
-            napi_throw_type_error(env, NULL, "denoise(handle, {iterations, sigmaLum, sigmaPlane, temporal, alphaMin})");
+            napi_coerce_to_bool(env, tv, &tv) != napi_ok || napi_get_value_bool(env, tv, &temporal) != napi_ok ||
+            napi_get_named_property(env, argv[1], "followVertices", &fv) != napi_ok ||
+            napi_coerce_to_bool(env, fv, &fv) != napi_ok || napi_get_value_bool(env, fv, &follow) != napi_ok) {
+            napi_throw_type_error(env, NULL, "denoise(handle, {iterations, sigmaLum, sigmaPlane, temporal, alphaMin, followVertices})");
             return NULL;
         }
         p.reserved[0] = temporal ? 1u : 0u;
         memcpy(&p.reserved[1], &alpha_min, sizeof alpha_min);
+        p.reserved[2] = follow ? 1u : 0u;
     } else if (t != napi_undefined && t != napi_null) {
         napi_throw_type_error(env, NULL, "denoise(handle, options): options must be an object");
         return NULL;

@@ -35,6 +35,9 @@ class Renderer:
         self._lib = N.load()
         self.width, self.height = int(width), int(height)
         self.pipeline = pipeline
+        # the temporal Denoise / denoise_bands follow deformed and skinned meshes (ptx_denoise_params.reserved[2]);
+        # 0 / 1 (a larger value is the library's to refuse)
+        self.follow_vertices: bool | int = False
         cfg = N.PtxConfig(width=self.width, height=self.height, row_begin=row_begin, row_end=row_end,
                           device=device,
                           pipeline=N.PIPELINES[pipeline], reuse_radius=reuse_radius,
@@ -394,10 +397,13 @@ class Renderer:
         read_denoised() or Present with source "denoised" show the result.  temporal (a renderer
         made with frame_color=True): filter the frame colours integrated over the calls instead,
         their history reprojected across camera moves; alpha_min (0 = 0.05) is the least weight of
-        the new frame."""
+        the new frame.  With the renderer's `follow_vertices` set (an attribute, False by default; read by
+        every temporal call), a pixel on a mesh that UpdateVertices / SkinVertices deformed since the previous
+        temporal call looks its history up where that surface point was then (ptx_denoise_params.reserved[2])."""
         p = N.PtxDenoiseParams(iterations=int(iterations), sigma_lum=float(sigma_lum), sigma_plane=float(sigma_plane))
         p.reserved[0] = int(temporal)
         p.reserved[1] = int(np.float32(alpha_min).view(np.uint32))
+        p.reserved[2] = int(self.follow_vertices)
         self._call("ptx_denoise", self._h, ctypes.byref(p))
 
     def Upsample(self, lo: "Renderer", sigma_plane: float = 0.0) -> None:
@@ -442,6 +448,10 @@ class Renderer:
         p = N.PtxDenoiseParams(iterations=int(iterations), sigma_lum=float(sigma_lum), sigma_plane=float(sigma_plane))
         p.reserved[0] = int(temporal)
         p.reserved[1] = int(np.float32(alpha_min).view(np.uint32))
+        follow = {int(r.follow_vertices) for r in renderers}  # (every band tracks for itself: each makes the same vertex calls)
+        if len(follow) > 1:
+            raise ValueError("denoise_bands: follow_vertices differs between the bands")
+        p.reserved[2] = follow.pop() if follow else 0
         if out is not None:
             rows = sum(r.band_rows for r in renderers)
             assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == rows * renderers[0].width * 4
