@@ -186,8 +186,9 @@ int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const
  *                            drops the kept G-buffers, surface records and neighbour summaries;
  *   PTX_EDIT_INSTANCES       rebuilds the instance table and the cull bounds (an instance may
  *                            switch to another loaded mesh), the same drops, and ptx_upsample_temporal's
- *                            history (the temporal upsampler does not follow objects; the temporal
- *                            mode of ptx_denoise does: below);
+ *                            history (the temporal upsampler does not follow objects unless the
+ *                            handle follows: ptx_upsample_follow; the temporal mode of ptx_denoise
+ *                            does: below);
  *   a switched mesh          drops the reuse / GI history outright: its reservoirs name triangles and
  *                            sub-meshes of the instance's old mesh;
  *   INSTANCES or MATERIALS   the reuse / GI history serves the next frame only if its camera words
@@ -230,7 +231,7 @@ int ptx_update_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, uint3
  * surface records and the neighbour summaries are dropped; ptx_denoise, ptx_upsample and their band
  * and temporal forms are PTX_E_INVALID until a frame or a G-buffer pass has run; the reuse / GI history
  * serves the next frame only if its camera words are those of the frame that wrote it; the history of
- * ptx_upsample_temporal is dropped.  The temporal history of ptx_denoise stays and is looked up as for
+ * ptx_upsample_temporal is dropped, unless the handle follows: ptx_upsample_follow.  The temporal history of ptx_denoise stays and is looked up as for
  * an unchanged instance: it does not follow vertices, so a deformed surface keeps the history of the
  * pixels it covered -- unless the handle's last temporal call asked to follow them
  * (ptx_denoise_params.reserved[2], "Vertex motion" under ptx_denoise): then this call first saves the
@@ -473,7 +474,8 @@ int ptx_present_poll(ptx_handle *h, uint8_t *out, size_t bytes);
  * same call with reserved[2] = 0.  ptx_upload_scene, ptx_reset_accumulation and everything else that drops
  * the temporal state drop the marks with it; a layout derived again by ptx_set_frame between two calls
  * moves the records, so the marked meshes' instances get flag 2 for that one call.  ptx_upsample_temporal
- * does not follow vertices and keeps dropping its history on a vertex update.
+ * does not follow vertices and keeps dropping its history on a vertex update, unless the handle follows:
+ * ptx_upsample_follow.
  * Launches: 3 + iterations (guide records, dn_temporal, variance, the iterations), following or not. */
 typedef struct ptx_denoise_params {
     uint32_t iterations;      /* 1..6 (step 2^i in iteration i); 0 = default 5 */
@@ -625,7 +627,8 @@ int ptx_upsample_bands(ptx_handle *const *hi, ptx_handle *const *lo, int n,
  * ptx_upload_scene, ptx_reset_accumulation, ptx_upsample, ptx_upsample_bands, ptx_denoise and
  * ptx_denoise_bands on hi drop the history (the next call is a first call); ptx_set_frame never does.
  * ptx_update_scene with PTX_EDIT_INSTANCES on hi drops it too: the temporal upsampler does not follow
- * moved objects (the temporal mode of ptx_denoise does); a material or light edit keeps it.
+ * moved objects unless the handle follows: ptx_upsample_follow (the temporal mode of ptx_denoise always
+ * does); a material or light edit keeps it.
  * After the call hi is no source of a ptx_upsample until it has been denoised or upsampled itself.
  *   PTX_E_INVALID with the reason in hi's ptx_last_error, before any GPU work: everything ptx_upsample
  * refuses (band handles: ptx_upsample_temporal_bands), a phase not below s, a lo whose camera is not that
@@ -646,6 +649,46 @@ typedef struct ptx_upsample_temporal_params {
     uint32_t reserved[3]; /* zero */
 } ptx_upsample_temporal_params; /* 32 bytes */
 int ptx_upsample_temporal(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_temporal_params *p /* NULL = defaults, phase (0, 0) */);
+/* Following (opt-in: a switch on the full-size handle, whole image or band; 0 = off, the default, 1 = on.
+ * With the switch never set every call and every drop is the one above, launch for launch and bit for bit).
+ * The call itself launches nothing and touches no GPU memory; PTX_E_INVALID for a null handle or follow > 1.
+ *   A handle is tracking when its last completely enqueued ptx_upsample_temporal / _bands call was made
+ * with the switch on; switching off ends the tracking, and if an edit is pending (below) drops the state, so
+ * that the next call is the first call it would have been.  Every call made with the switch on keeps the
+ * instance block of the scene array (33 words per instance) and the layout it ran under; the first one
+ * allocates a snapshot buffer of the upsampler's own, 80 bytes per triangle of the scene (counted in
+ * device_bytes; the denoiser's snapshot is the shape *its* previous temporal call saw, another moment).
+ *   While tracking with a state, ptx_update_scene with PTX_EDIT_INSTANCES, ptx_update_vertices and
+ * ptx_skin_vertices on hi keep the state and mark an edit pending.  The first vertex call on a mesh since the
+ * last upsample call first saves the mesh's triangle records -- a device-to-device copy on the call's stream
+ * ahead of the refit, no launch -- and marks the mesh; later updates before the next call save nothing.  The
+ * G-buffer rule is unchanged: the next call is refused until hi has run a G-buffer pass or a frame.
+ *   The next call with the switch on, a state and a pending edit gives every instance a flag from the kept
+ * block and the current one, by ptx_denoise's rule ("Object motion"): 0 unchanged, 1 moved rigidly
+ * (D = M_prev * Minv_cur), 2 anything else, a switched mesh included; and 3 for an instance with the same mesh
+ * word whose mesh is marked, whatever became of its matrices ("Vertex motion") -- 2 instead where the records
+ * were not saved, the layout was derived again since, or the buffer sizes differ.  The table (and, with a
+ * flag 3, the kept instances) is uploaded with a synchronous copy on hi's stream: this one call waits for
+ * the frame it follows, as the denoiser's does.  A hit pixel's history lookup then goes by the flag of its
+ * instance (key >> 16; past the table: 0); the estimate u, the own sample d and the integration are unchanged:
+ *   flag 0   as above;
+ *   flag 2   no lookup (sampled: H = d, n = 1; otherwise H = u, n = 0);
+ *   flag 1   Q = D P, Nq = D N (linear part, not renormalised) are where the point and its normal were at the
+ *            previous call; Q is always projected through that call's VP, under the same camera words too;
+ *            the four taps and bilinear weights are the reprojection's, and a tap counts inside the image with
+ *            the same key, n' >= 0, dot(Nq, N') >= 0.9 and |dot(Nq, P' - Q)| <= this pixel's r;
+ *   flag 3   Q and Nq are the position and normalised normal of this pixel's G-buffer texel (triangle,
+ *            barycentrics) on the snapshot's triangle record under the previous call's instance matrices;
+ *            then as flag 1.
+ * A pixel without a primary hit is unchanged.  A call with the switch off on a handle with a pending edit is
+ * a first call.  The marks and the pending edit are cleared by the next upsample call, used or not, and by
+ * everything that drops the state (ptx_upload_scene, ptx_reset_accumulation, ptx_upsample*, ptx_denoise* on hi).
+ *   Bands: every band makes the same edits and builds its table from its own kept block; nothing new is
+ * exchanged, and a band that keeps its state across an edit sends its state rows as ever.  A flag-1 or flag-3
+ * pixel has taps off itself under the same camera too: such a tap inside the image but outside the covered
+ * history rows is not taken and counts in PTX_COUNTER_UPSAMPLE_CLIP, as a reprojected one.
+ * Launches: 2, following or not (guide records; dn_upsample_temporal, with a table its FOLLOW instance). */
+int ptx_upsample_follow(ptx_handle *hi, uint32_t follow);
 /* ptx_upsample_temporal for a frame split into row bands (Temporal upsampling, bands):
  * n pairs in band order, lo[i] a band of the small frame after ptx_denoise_bands, hi[i] the band of
  * the full-size frame with s times its rows.  The forms are ptx_upsample_bands': n pairs of one

@@ -59,7 +59,8 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_build_info", "ptx_denoise", "ptx_present_source", "ptx_denoise_bands",
             "ptx_upsample", "ptx_upsample_bands", "ptx_phase_uniform", "ptx_upsample_temporal",
             "ptx_trace_queries", "ptx_upsample_temporal_bands", "ptx_update_scene", "ptx_update_vertices",
-            "ptx_read_accel", "ptx_set_skin", "ptx_skin_vertices", "ptx_read_vertices"]
+            "ptx_read_accel", "ptx_set_skin", "ptx_skin_vertices", "ptx_read_vertices",
+            "ptx_upsample_follow"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -167,6 +168,7 @@ def load(path: str = LIB_PATH):
     lib.ptx_upsample_temporal.argtypes = [H, H, ctypes.POINTER(PtxUpsampleTemporalParams)]
     lib.ptx_upsample_temporal_bands.argtypes = [ctypes.POINTER(H), ctypes.POINTER(H), ctypes.c_int,
                                                 ctypes.POINTER(PtxUpsampleTemporalParams)]
+    lib.ptx_upsample_follow.argtypes = [H, ctypes.c_uint32]
     lib.ptx_present_source.argtypes = [H, ctypes.c_int]
     lib.ptx_run_passes.argtypes = [H, P, ctypes.c_int]
     lib.ptx_halo_rows.argtypes = [H, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),

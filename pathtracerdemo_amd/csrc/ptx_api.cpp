@@ -1931,7 +1931,7 @@ int denoise_back(ptx_handle *h, const DnCall &c, const DnBand &b) {
     if (e != hipSuccess) return fail(h, PTX_E_HIP, "denoiser launch: %s", hipGetErrorString(e));
     h->dn_guide_swapped = c.temporal != 0u;  // (ptx_upsample reads this call's guide records)
     h->dn_guide_stale = false;
-    h->ut_valid = false;  // (PTX_BUF_DENOISED is no longer ptx_upsample_temporal's)
+    ut_drop(h);  // (PTX_BUF_DENOISED is no longer ptx_upsample_temporal's)
     h->dn_guide_top = b.top;                 // (ptx_upsample_bands: and those of its neighbours' rows)
     h->dn_guide_bot = b.bot;
     h->dn_stream = st;
@@ -2012,7 +2012,7 @@ hipError_t upsample_launch(ptx_handle *hi, ptx_handle *lo, uint32_t s, float sig
     if (e != hipSuccess) return e;
     hi->dn_guide_swapped = false;  // (this handle's output and the guide records it was written under)
     hi->dn_guide_stale = false;
-    hi->ut_valid = false;  // (PTX_BUF_DENOISED is no longer ptx_upsample_temporal's)
+    ut_drop(hi);  // (PTX_BUF_DENOISED is no longer ptx_upsample_temporal's)
     hi->dn_guide_top = hi->dn_guide_bot = 0u;
     hi->dn_stream = st;
     return hipSuccess;
@@ -2088,6 +2088,72 @@ int upsample_temporal_camera(ptx_handle *err, ptx_handle *hi, ptx_handle *lo, ui
     return PTX_OK;
 }
 
+// ptx_upsample_follow: what a call of a following handle needs beside the state's buffers -- the snapshot
+// buffer (the first call with the switch on; another size: a layout derived since, what was saved is gone) and,
+// with a state and a pending edit, the table dn_upsample_temporal<S, FOLLOW> reads (hi->ut_fo, consumed by
+// upsample_temporal_launch): denoise_objects on the kept instance block and the current one, flag 3 for an
+// instance of a marked mesh whatever became of its matrices -- 2 where the records were not saved or the
+// layout they were saved under is no longer the handle's --, and the kept instances as DnPrev behind the
+// DnObj entries, one upload of one size.  The copy is synchronous on hi's stream, as denoise_front's is: this
+// one call waits for the frame it follows.  A table without a flag is no table: the unchanged kernel runs.
+// A pending edit on a handle whose switch is off drops the state: the call is a first call.
+static int upsample_follow_table(ptx_handle *h) {
+    h->ut_fo = UtFollow{};
+    if (h->ut_pending && !h->ut_follow) ut_drop(h);
+    if (!h->ut_follow) return PTX_OK;
+    if (h->d_ut_snap.bytes != h->d_tverts.bytes) {  // the snapshot: 80 B per triangle of the scene
+        if (int rc = alloc_buf(h, h->d_ut_snap, h->d_tverts.bytes)) return rc;
+        for (uint8_t &m : h->ut_deformed)
+            if (m) m = 2u;
+    }
+    if (!h->ut_valid || !h->ut_pending) return PTX_OK;
+    const size_t iw = (size_t)STRIDE_INSTANCE * h->n_inst;
+    if (iw > h->scene.size() || h->ut_insts.size() != iw) {  // (no kept block to compare with: nothing to follow by)
+        ut_drop(h);
+        return PTX_OK;
+    }
+    std::vector<DnObj> table = std::memcmp(h->ut_insts.data(), h->scene.data(), iw * 4u) != 0
+                                   ? denoise_objects(h->ut_insts.data(), h->scene.data(), h->n_inst)
+                                   : std::vector<DnObj>(h->n_inst, DnObj{});
+    const bool usable = h->ut_track_layout == h->layout_gen && h->d_ut_snap.p && h->d_ut_snap.bytes == h->d_tverts.bytes;
+    std::vector<DnPrev> prev(h->n_inst, DnPrev{});
+    static const float kId[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    bool any = false, verts = false;
+    for (uint32_t i = 0; i < h->n_inst; ++i) {
+        const uint32_t *p = h->ut_insts.data() + (size_t)STRIDE_INSTANCE * i;
+        const uint32_t mesh = h->scene[(size_t)STRIDE_INSTANCE * i + 32u];
+        if (mesh == p[32] && mesh < h->ut_deformed.size() && h->ut_deformed[mesh]) {
+            const bool saved = usable && h->ut_deformed[mesh] == 1u && mesh < h->lay_mesh_tri_base.size();
+            table[i].flag = saved ? 3u : 2u;
+            if (saved) {
+                DnPrev &I = prev[i];
+                std::memcpy(I.m, p, 64);
+                std::memcpy(I.minv, p + 16, 64);
+                I.mesh = p[32];
+                I.tri_base = h->lay_mesh_tri_base[mesh];
+                if (!std::memcmp(I.m, kId, sizeof kId) && !std::memcmp(I.minv, kId, sizeof kId)) I.mesh |= kInstIdentity;
+                verts = true;
+            }
+        }
+        any = any || table[i].flag != 0u;
+    }
+    if (!any) return PTX_OK;
+    const size_t nb = table.size() * sizeof(DnObj);
+    std::vector<unsigned char> both(nb + prev.size() * sizeof(DnPrev));
+    std::memcpy(both.data(), table.data(), nb);
+    std::memcpy(both.data() + nb, prev.data(), prev.size() * sizeof(DnPrev));
+    if (int rc = upload(h, h->d_ut_obj, both.data(), both.size())) return rc;
+    h->ut_fo.obj = (const DnObj *)h->d_ut_obj.p;
+    h->ut_fo.n_obj = h->n_inst;
+    if (verts) {
+        h->ut_fo.verts.gbuf = gbuf_band(h);
+        h->ut_fo.verts.prev = (const DnPrev *)((const char *)h->d_ut_obj.p + nb);
+        h->ut_fo.verts.snap = (const float4 *)h->d_ut_snap.p;
+        h->ut_fo.n_snap = (uint32_t)(h->d_ut_snap.bytes / 80u);
+    }
+    return PTX_OK;
+}
+
 int upsample_temporal_alloc(ptx_handle *err, ptx_handle *hi, uint32_t halo_rows, uint32_t w) {
     if (!hi->d_dn_guide.p) {  // (the layout a band's first ptx_denoise_bands would give the output: denoise_alloc)
         hi->dn_cap_top = std::min(dn_reach(6u), hi->cfg.row_begin);
@@ -2102,6 +2168,7 @@ int upsample_temporal_alloc(ptx_handle *err, ptx_handle *hi, uint32_t halo_rows,
         if (!rc) rc = alloc_buf(hi, hi->d_ut_hist[k], spx * 16u);
     }
     if (!rc && halo_rows) rc = alloc_buf(hi, hi->d_up_halo, (size_t)4u * w * 16u);  // the neighbours' small rows: 2 above, 2 below
+    if (!rc) rc = upsample_follow_table(hi);
     if (rc && err != hi) fail(err, rc, "%s", hi->err.c_str());  // (alloc_buf's message, where the call's refusals go)
     return rc;
 }
@@ -2112,6 +2179,8 @@ hipError_t upsample_temporal_launch(ptx_handle *hi, ptx_handle *lo, uint32_t s, 
     const bool band = top || bot || hi->band_h != H;  // (a whole image without halo rows: ptx_upsample_temporal's launch)
     const hipStream_t st = hi->cur().stream;
     const int rd = hi->ut_set, wr = hi->ut_set ^ 1;
+    const UtFollow fo = hi->ut_valid ? hi->ut_fo : UtFollow{};  // (upsample_temporal_alloc's, with a state alone)
+    hi->ut_fo = UtFollow{};
     const uint32_t mode = !hi->ut_valid ? 0u : std::memcmp(hi->ut_camera, hi->uniform + 4, sizeof hi->ut_camera) == 0 ? 1u : 2u;
     hi->ut_valid = false;  // (until both launches are enqueued)
     const Scene sc = make_scene(hi);
@@ -2127,17 +2196,21 @@ hipError_t upsample_temporal_launch(ptx_handle *hi, ptx_handle *lo, uint32_t s, 
     hipError_t e = denoise_timed(hi, st, hipSuccess, [&] { return launch_denoise_guide(sc, gbuf_band(hi), guide, c.sigma_plane, st); });
     e = denoise_timed(hi, st, e, [&] {
         if (!band)
-            return launch_denoise_upsample_temporal(s, W, H, c.px, c.py, c.alpha_min, c.alpha_fill, mode, hi->ut_vp, guide, lguide,
-                                                    lcolor, pguide, phist, hist, out, st);
+            return launch_denoise_upsample_temporal(s, W, H, c.px, c.py, c.alpha_min, c.alpha_fill, mode, hi->ut_vp, fo, guide,
+                                                    lguide, lcolor, pguide, phist, hist, out, st);
         UtWin win;
         win.up = UpWin{lo->cfg.row_begin - top, top + lo->band_h + bot, top, top + lo->band_h, hi->cfg.row_begin, hi->cfg.row_end};
         win.hy0 = hi->cfg.row_begin - ht;
         win.hrows = ht + hi->band_h + hb;
         win.clip = (unsigned long long *)hi->d_counters.p + CNT_UPSAMPLE_CLIP;
-        return launch_denoise_upsample_temporal_win(s, W, H, c.px, c.py, c.alpha_min, c.alpha_fill, mode, hi->ut_vp, win, guide, lguide,
-                                                    lcolor, (const float4 *)hi->d_up_halo.p, pguide + 2u * cov, phist + cov, hist,
-                                                    out, st);
+        return launch_denoise_upsample_temporal_win(s, W, H, c.px, c.py, c.alpha_min, c.alpha_fill, mode, hi->ut_vp, win, fo, guide,
+                                                    lguide, lcolor, (const float4 *)hi->d_up_halo.p, pguide + 2u * cov, phist + cov,
+                                                    hist, out, st);
     });
+    // the marks and the pending edit were this call's to use, used or not; the next update saves again
+    hi->ut_pending = false;
+    hi->ut_deformed.clear();
+    hi->ut_track = false;
     if (e == hipSuccess) {  // this call is the next one's previous call
         hi->ut_set = wr;
         std::memcpy(hi->ut_camera, hi->uniform + 4, sizeof hi->ut_camera);
@@ -2145,6 +2218,11 @@ hipError_t upsample_temporal_launch(ptx_handle *hi, ptx_handle *lo, uint32_t s, 
         std::memcpy(vpinv, hi->ut_camera, sizeof vpinv);
         mat4_inverse(vpinv, hi->ut_vp);
         hi->ut_valid = true;
+        if (hi->ut_follow) {  // tracking: the instances and the layout this call saw
+            hi->ut_insts.assign(hi->scene.begin(), hi->scene.begin() + std::min(hi->scene.size(), (size_t)STRIDE_INSTANCE * hi->n_inst));
+            hi->ut_track_layout = hi->layout_gen;
+            hi->ut_track = true;
+        }
         hi->dn_guide_stale = true;  // (PTX_BUF_DENOISED's guide records are in the state, not in d_dn_guide)
         hi->dn_stream = st;
     }
@@ -2301,7 +2379,7 @@ int ptx_upload_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, const
     h->hist_valid = false;
     h->dn_hist_valid = false;  // (the denoiser's history shows the old scene)
     h->dn_deformed.clear();    // (its marks name the old scene's meshes; without a state nothing reads them)
-    h->ut_valid = false;       // (and ptx_upsample_temporal's)
+    ut_drop(h);                // (and ptx_upsample_temporal's, with its marks)
     h->cur().init_state_valid = false;
     h->cur().nbr_valid = false;
     for (auto &c : h->ctx) c.surf_valid = false;
@@ -2366,7 +2444,8 @@ int ptx_update_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, uint3
         rc = layout_tables(h, (mask & PTX_EDIT_INSTANCES) != 0, (mask & PTX_EDIT_MATERIALS) != 0);
     if (rc != PTX_OK) {
         h->scene_loaded = h->layout_valid = false;
-        h->hist_valid = h->dn_hist_valid = h->ut_valid = h->drawn = h->rendered = false;
+        h->hist_valid = h->dn_hist_valid = h->drawn = h->rendered = false;
+        ut_drop(h);
         for (auto &c : h->ctx) c.surf_valid = c.init_state_valid = c.nbr_valid = false;
         gbuf_key_drop_all(h);
         return rc;
@@ -2385,8 +2464,13 @@ int ptx_update_scene(ptx_handle *h, const uint32_t *scene, size_t n_scene, uint3
     // vertices as (instance, triangle of its mesh, sub-mesh), which the passes decode with the new
     // instance table -- indices of the old mesh would read another mesh's records, or past the tables
     if (mesh_switched) h->hist_valid = false;
-    // ptx_upsample_temporal does not follow objects; ptx_denoise's temporal mode does (denoise_front)
-    if (mask & PTX_EDIT_INSTANCES) h->ut_valid = false;
+    // ptx_upsample_temporal does not follow objects unless the handle follows (ptx_upsample_follow): a tracking
+    // handle keeps its state and the next call compares the instance blocks (upsample_follow_table);
+    // ptx_denoise's temporal mode always does (denoise_front)
+    if (mask & PTX_EDIT_INSTANCES) {
+        if (h->ut_track && h->ut_valid) h->ut_pending = true;
+        else ut_drop(h);
+    }
     return PTX_OK;
 }
 
@@ -2455,6 +2539,19 @@ static int refit_after_vertices(ptx_handle *h, uint32_t mesh, hipError_t le, uin
             h->dn_deformed[mesh] = fits ? 1u : 2u;
         }
     }
+    // a tracking temporal upsampler (ptx_upsample_follow): the same for the shape *its* last call saw, in a
+    // buffer of its own -- a full-size handle may hold a denoiser state from another moment
+    if (le == hipSuccess && h->ut_track && h->ut_valid) {
+        h->ut_deformed.resize(h->lay_mesh_nsub.size(), 0u);
+        if (!h->ut_deformed[mesh]) {
+            const size_t off = 80u * (size_t)m.tri_base, nb = 80u * (size_t)m.n_tris;
+            const bool fits = h->d_ut_snap.p && h->d_ut_snap.bytes == h->d_tverts.bytes && off + nb <= h->d_ut_snap.bytes &&
+                              h->ut_track_layout == h->layout_gen;
+            if (fits && nb)
+                le = hipMemcpyAsync((char *)h->d_ut_snap.p + off, (const char *)h->d_tverts.p + off, nb, hipMemcpyDeviceToDevice, st);
+            h->ut_deformed[mesh] = fits ? 1u : 2u;
+        }
+    }
     le = slot_timed(h, PTX_STAT_REFIT, st, le, [&] { return launch_refit_tris(m, st); });
     const auto &lv = h->lay_mesh_levels[mesh];  // lowest height first: a pair's interior children are lower
     for (size_t k = 0; k + 1 < lv.size(); ++k)
@@ -2467,7 +2564,8 @@ static int refit_after_vertices(ptx_handle *h, uint32_t mesh, hipError_t le, uin
     if (rc == PTX_OK) rc = layout_tables(h, true, false);
     if (rc != PTX_OK) {
         h->scene_loaded = h->layout_valid = false;
-        h->hist_valid = h->dn_hist_valid = h->ut_valid = h->drawn = h->rendered = false;
+        h->hist_valid = h->dn_hist_valid = h->drawn = h->rendered = false;
+        ut_drop(h);
         for (auto &c : h->ctx) c.surf_valid = c.init_state_valid = c.nbr_valid = false;
         gbuf_key_drop_all(h);
         h->mesh_stale.clear();  // (nothing on the device is worth reading back)
@@ -2483,9 +2581,11 @@ static int refit_after_vertices(ptx_handle *h, uint32_t mesh, hipError_t le, uin
     h->drawn = h->rendered = false;
     h->hist_same_only = true;
     if (h->hist_moved) h->hist_valid = false;
-    h->ut_valid = false;  // (ptx_upsample_temporal does not follow vertices; neither does ptx_denoise's temporal mode
-                          //  unless the handle is tracking, above: its history stays and is looked up as for an
-                          //  unchanged instance)
+    // ptx_upsample_temporal does not follow vertices unless the handle follows (ptx_upsample_follow: tracking,
+    // above, the state stays and the edit is pending); neither does ptx_denoise's temporal mode unless the
+    // handle is tracking, above: its history stays and is looked up as for an unchanged instance
+    if (h->ut_track && h->ut_valid) h->ut_pending = true;
+    else ut_drop(h);
     return PTX_OK;
 }
 
@@ -2836,7 +2936,7 @@ int ptx_reset_accumulation(ptx_handle *h) {
     HIP_CHECK(h, hipMemsetAsync(h->d_accum.p, 0, h->d_accum.bytes, h->cur().stream));
     h->hist_valid = false;
     h->dn_hist_valid = false;
-    h->ut_valid = false;
+    ut_drop(h);
     return PTX_OK;
 }
 
@@ -2867,7 +2967,7 @@ int ptx_get_stats(ptx_handle *h, ptx_stats *out) {
                         h->d_denoised.bytes + h->d_frame_color.bytes + h->d_dn_guide_prev.bytes + h->d_dn_hist[0].bytes +
                         h->d_dn_hist[1].bytes + h->d_dn_mom[0].bytes + h->d_dn_mom[1].bytes + h->d_dn_halo_g.bytes +
                         h->d_dn_halo_c.bytes + h->d_dn_obj.bytes + h->d_dn_snap.bytes + h->d_up_halo.bytes + h->d_ut_guide[0].bytes + h->d_ut_guide[1].bytes +
-                        h->d_ut_hist[0].bytes + h->d_ut_hist[1].bytes + h->d_refit_order.bytes + h->d_refit_box.bytes;
+                        h->d_ut_hist[0].bytes + h->d_ut_hist[1].bytes + h->d_ut_snap.bytes + h->d_ut_obj.bytes + h->d_refit_order.bytes + h->d_refit_box.bytes;
     for (const auto &k : h->skins) out->device_bytes += k.bind.bytes + k.target_pos.bytes + k.target_nrm.bytes + k.pose.bytes;
     return PTX_OK;
 }
@@ -3132,6 +3232,18 @@ int ptx_upsample_temporal(ptx_handle *hi, ptx_handle *lo, const ptx_upsample_tem
     return PTX_OK;
 }
 
+int ptx_upsample_follow(ptx_handle *hi, uint32_t follow) {
+    if (!hi) return PTX_E_INVALID;
+    if (follow > 1u) return fail(hi, PTX_E_INVALID, "ptx_upsample_follow: follow %u (0 off, 1 on)", follow);
+    if (!follow) {  // no longer tracking; an edit the state was kept across drops it after all
+        if (hi->ut_pending) hi->ut_valid = false;
+        hi->ut_track = hi->ut_pending = false;
+        hi->ut_deformed.clear();
+    }
+    hi->ut_follow = follow != 0u;
+    return PTX_OK;
+}
+
 int ptx_present_source(ptx_handle *h, int which) {
     if (!h) return PTX_E_INVALID;
     if (which != PTX_BUF_ACCUM && which != PTX_BUF_DENOISED)
@@ -3269,7 +3381,7 @@ int ptx_destroy(ptx_handle *h) {
                       &h->d_jstate, &h->d_jres, &h->d_replay, &h->d_psurf, &h->d_census, &h->d_wgt, &h->d_dn_guide, &h->d_dn_work,
                       &h->d_denoised, &h->d_frame_color, &h->d_dn_guide_prev, &h->d_dn_hist[0], &h->d_dn_hist[1], &h->d_dn_mom[0],
                       &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_dn_obj, &h->d_dn_snap, &h->d_up_halo, &h->d_ut_guide[0], &h->d_ut_guide[1],
-                      &h->d_ut_hist[0], &h->d_ut_hist[1], &h->d_refit_order, &h->d_refit_box})
+                      &h->d_ut_hist[0], &h->d_ut_hist[1], &h->d_ut_snap, &h->d_ut_obj, &h->d_refit_order, &h->d_refit_box})
         free_buf(*b);
     drop_skins(h);
     for (auto &c : h->ctx) {

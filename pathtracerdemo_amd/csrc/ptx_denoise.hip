@@ -632,9 +632,18 @@ __device__ __forceinline__ int up_floor_div(int a, int s) { return a >= 0 ? a / 
 // counts in *win.clip: one ballot and one add of its popcount per wave.  Only mode 2 with a primary
 // hit and cw > 0 has taps off the pixel itself, so nothing else clips.
 // Without WIN the code is the whole image's, `win` and `lhalo` unread.
-template <int S, bool WIN>
+// FOLLOW (a call of a following handle that finds an instance changed or a mesh deformed since the previous
+// one, ptx_upsample_follow; tests/upsample_follow_ref.py): 0 the code above, `fo` unread.  1: a hit pixel's
+// lookup goes by its instance's flag, fo.obj[key >> 16] (past fo.n_obj: 0), as dn_temporal<true>'s does -- flag 0
+// as without the table; flag 2 no tap; flag 1 Q = D P and Nq = D N (dn_temporal_px's element order, not
+// renormalised), Q always projected through vp, in mode 1 too, and the taps tested against Q and Nq with this
+// pixel's r.  2: also flag 3, Q and Nq from the snapshot's triangle record under the previous call's instance
+// matrices at the barycentrics of this pixel's G-buffer texel (fo.verts.gbuf starts at row Y0, like hg), by
+// dn_temporal_px<true, true>'s expressions; then as flag 1.  A flag-1 or flag-3 pixel has taps off itself in
+// mode 1 as well, so with a table a band's pixels can clip in either mode.
+template <int S, bool WIN, int FOLLOW>
 __device__ __forceinline__ void dn_upsample_temporal_tile(uint32_t W, uint32_t H, uint32_t w, uint32_t h, const UpHistory &Hs,
-                                                          const UtWin &win, const float4 *__restrict__ hg,
+                                                          const UtWin &win, const UtFollow &fo, const float4 *__restrict__ hg,
                                                           const float4 *__restrict__ lg, const float4 *__restrict__ lc,
                                                           const float4 *__restrict__ lhalo, const float4 *__restrict__ pguide,
                                                           const float4 *__restrict__ phist, float4 *__restrict__ hist,
@@ -654,19 +663,52 @@ __device__ __forceinline__ void dn_upsample_temporal_tile(uint32_t W, uint32_t H
     const float4 a = hg[2u * pix], b = hg[2u * pix + 1u];
     const uint32_t key = asu(a.w);
     const f3 Pp = rgb(a), Np = rgb(b);
+    // ---- where the previous call saw this pixel's point: Q, Nq (the flag, the texel and the snapshot record
+    // are issued with the guide loads)
+    uint32_t flag = 0u;
+    f3 Q = Pp, Nq = Np;
+    if (FOLLOW) {
+        uint4 g = make_uint4(0u, 0u, 0u, 0u);
+        if (FOLLOW == 2) g = fo.verts.gbuf[pix];
+        const uint32_t inst = key >> 16;
+        if (Hs.mode != 0u && key != kDnMiss && inst < fo.n_obj) flag = fo.obj[inst].flag;
+        if (FOLLOW == 2 && flag == 3u) {
+            const DnPrev &I = fo.verts.prev[inst];
+            // (clamped: a G-buffer the host wrote may name any triangle; the handle's own never reaches the bound)
+            const float4 *t = fo.verts.snap + 5u * (size_t)min(I.tri_base + g.y, fo.n_snap - 1u);
+            const float4 ta = t[0], tb = t[1], tc = t[2], td = t[3], te = t[4];  // (tri_verts' record)
+            const bool id = (I.mesh & kInstIdentity) != 0u;
+            const f3 p0 = dn_prev_point(id, I.m, mk(ta.x, ta.y, ta.z)), n0 = dn_prev_point_t(id, I.minv, mk(ta.w, tb.x, tb.y));
+            const f3 p1 = dn_prev_point(id, I.m, mk(tb.z, tb.w, tc.x)), n1 = dn_prev_point_t(id, I.minv, mk(tc.y, tc.z, tc.w));
+            const f3 p2 = dn_prev_point(id, I.m, mk(td.x, td.y, td.z)), n2 = dn_prev_point_t(id, I.minv, mk(td.w, te.x, te.y));
+            const float bu = asf(g.z), bv = asf(g.w), bw = 1.0f - bu - bv;
+            Nq = normalize((n0 * bu + n1 * bv) + n2 * bw);
+            Q = (p0 * bu + p1 * bv) + p2 * bw;
+        }
+        if (flag == 1u) {
+            const float *d = fo.obj[inst].d;
+            Q.x = ((d[0] * Pp.x + d[4] * Pp.y) + d[8] * Pp.z) + d[12];
+            Q.y = ((d[1] * Pp.x + d[5] * Pp.y) + d[9] * Pp.z) + d[13];
+            Q.z = ((d[2] * Pp.x + d[6] * Pp.y) + d[10] * Pp.z) + d[14];
+            Nq.x = (d[0] * Np.x + d[4] * Np.y) + d[8] * Np.z;
+            Nq.y = (d[1] * Np.x + d[5] * Np.y) + d[9] * Np.z;
+            Nq.z = (d[2] * Np.x + d[6] * Np.y) + d[10] * Np.z;
+        }
+    }
     // ---- the history's taps k = 2 j + i (j outer), all loads issued ahead of the staging and the tests
     size_t q[4];
     float wq[4];
     bool in[4], clipped = false;
     float4 qa[4], qb[4], qh[4];
-    if (Hs.mode == 1u) {
+    const bool moved = FOLLOW && (flag == 1u || flag == 3u);  // (followed: through vp under the same camera too)
+    if (Hs.mode == 1u && !moved) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { q[k] = pc; wq[k] = 1.0f; in[k] = k == 0; }
-    } else if (Hs.mode == 2u) {
+        for (int k = 0; k < 4; ++k) { q[k] = pc; wq[k] = 1.0f; in[k] = k == 0 && !(FOLLOW && flag == 2u); }
+    } else if (Hs.mode != 0u) {
         const float *vp = Hs.vp;
-        const float cx = ((vp[0] * Pp.x + vp[4] * Pp.y) + vp[8] * Pp.z) + vp[12];
-        const float cy = ((vp[1] * Pp.x + vp[5] * Pp.y) + vp[9] * Pp.z) + vp[13];
-        const float cw = ((vp[3] * Pp.x + vp[7] * Pp.y) + vp[11] * Pp.z) + vp[15];
+        const float cx = ((vp[0] * Q.x + vp[4] * Q.y) + vp[8] * Q.z) + vp[12];
+        const float cy = ((vp[1] * Q.x + vp[5] * Q.y) + vp[9] * Q.z) + vp[13];
+        const float cw = ((vp[3] * Q.x + vp[7] * Q.y) + vp[11] * Q.z) + vp[15];
         const float hx = ((cx / cw + 1.0f) * 0.5f) * (float)W - 0.5f, hy = ((cy / cw + 1.0f) * 0.5f) * (float)H - 0.5f;
         const float hx0 = __builtin_floorf(hx), hy0 = __builtin_floorf(hy);
         const float bx1 = hx - hx0, by1 = hy - hy0;
@@ -675,7 +717,8 @@ __device__ __forceinline__ void dn_upsample_temporal_tile(uint32_t W, uint32_t H
             const int i = k & 1, j = k >> 1;
             const float qx = hx0 + (float)i, qy = hy0 + (float)j;
             // (a NaN or infinite projection compares false: outside)
-            in[k] = key != kDnMiss && cw > 0.0f && qx >= 0.0f && qx < (float)W && qy >= 0.0f && qy < (float)H;
+            in[k] = key != kDnMiss && !(FOLLOW && flag == 2u) && cw > 0.0f && qx >= 0.0f && qx < (float)W && qy >= 0.0f &&
+                    qy < (float)H;
             if (WIN) {
                 const uint32_t ry = (uint32_t)(in[k] ? (int)qy : (int)win.hy0) - win.hy0;  // (below hy0: wraps past hrows)
                 if (live && in[k] && ry >= win.hrows) clipped = true;
@@ -695,7 +738,7 @@ __device__ __forceinline__ void dn_upsample_temporal_tile(uint32_t W, uint32_t H
             qh[k] = phist[q[k]];
         }
     }
-    if (WIN && Hs.mode == 2u) {  // (wave-uniform: every lane of the wave votes)
+    if (WIN && (Hs.mode == 2u || (FOLLOW && Hs.mode != 0u))) {  // (wave-uniform: every lane of the wave votes)
         const unsigned long long cm = __ballot(clipped);
         if (clipped && __lane_id() == (uint32_t)__ffsll((long long)cm) - 1u) atomicAdd(win.clip, (unsigned long long)__popcll(cm));
     }
@@ -784,8 +827,8 @@ __device__ __forceinline__ void dn_upsample_temporal_tile(uint32_t W, uint32_t H
         for (int k = 0; k < 4; ++k) {
             if (!in[k] || asu(qa[k].w) != key || !(qh[k].w >= 0.0f)) continue;
             if (key != kDnMiss) {
-                if (!(dot(Np, rgb(qb[k])) >= 0.9f)) continue;
-                if (!(__builtin_fabsf(dot(Np, rgb(qa[k]) - Pp)) <= b.w)) continue;
+                if (!(dot(Nq, rgb(qb[k])) >= 0.9f)) continue;
+                if (!(__builtin_fabsf(dot(Nq, rgb(qa[k]) - Q)) <= b.w)) continue;
             }
             hw += wq[k];
             hC = hC + rgb(qh[k]) * wq[k];
@@ -813,20 +856,22 @@ __device__ __forceinline__ void dn_upsample_temporal_tile(uint32_t W, uint32_t H
     out[pix] = make_float4(Hn.x, Hn.y, Hn.z, 1.0f);
     hist[pix] = make_float4(Hn.x, Hn.y, Hn.z, n);
 }
-template <int S>
+template <int S, int FOLLOW>
 __global__ __launch_bounds__(kBlock) void dn_upsample_temporal(uint32_t W, uint32_t H, uint32_t w, uint32_t h, const UpHistory Hs,
-                                                               const float4 *__restrict__ hg, const float4 *__restrict__ lg,
-                                                               const float4 *__restrict__ lc, const float4 *__restrict__ pguide,
+                                                               const UtFollow fo, const float4 *__restrict__ hg,
+                                                               const float4 *__restrict__ lg, const float4 *__restrict__ lc,
+                                                               const float4 *__restrict__ pguide,
                                                                const float4 *__restrict__ phist, float4 *__restrict__ hist,
                                                                float4 *__restrict__ out) {
     constexpr int kN = (kDnTile + S - 2) / S + 4;
     __shared__ float4 g0[kN * kN], g1[kN * kN], cv[kN * kN];
-    dn_upsample_temporal_tile<S, false>(W, H, w, h, Hs, UtWin{}, hg, lg, lc, nullptr, pguide, phist, hist, out, g0, g1, cv);
+    dn_upsample_temporal_tile<S, false, FOLLOW>(W, H, w, h, Hs, UtWin{}, fo, hg, lg, lc, nullptr, pguide, phist, hist, out, g0, g1,
+                                                cv);
 }
 // A band of the full-size frame from a window of the small one and the covered rows of the previous state.
-template <int S>
+template <int S, int FOLLOW>
 __global__ __launch_bounds__(kBlock) void dn_upsample_temporal_win(uint32_t W, uint32_t H, uint32_t w, uint32_t h,
-                                                                   const UpHistory Hs, const UtWin win,
+                                                                   const UpHistory Hs, const UtWin win, const UtFollow fo,
                                                                    const float4 *__restrict__ hg, const float4 *__restrict__ lg,
                                                                    const float4 *__restrict__ lc, const float4 *__restrict__ lhalo,
                                                                    const float4 *__restrict__ pguide,
@@ -834,7 +879,7 @@ __global__ __launch_bounds__(kBlock) void dn_upsample_temporal_win(uint32_t W, u
                                                                    float4 *__restrict__ out) {
     constexpr int kN = (kDnTile + S - 2) / S + 4;
     __shared__ float4 g0[kN * kN], g1[kN * kN], cv[kN * kN];
-    dn_upsample_temporal_tile<S, true>(W, H, w, h, Hs, win, hg, lg, lc, lhalo, pguide, phist, hist, out, g0, g1, cv);
+    dn_upsample_temporal_tile<S, true, FOLLOW>(W, H, w, h, Hs, win, fo, hg, lg, lc, lhalo, pguide, phist, hist, out, g0, g1, cv);
 }
 
 // ---------------------------------------------------------------- launches
@@ -909,13 +954,38 @@ hipError_t launch_denoise_upsample(uint32_t s, uint32_t W, uint32_t H, const flo
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
+// FOLLOW by what the call carries: no table the unchanged instantiation, a table dn_temporal<true>'s rule,
+// a snapshot beside it dn_temporal_verts' too.
+static int ut_follow_kind(const UtFollow &fo) {
+    if (!fo.obj) return fo.verts.snap || fo.verts.gbuf || fo.verts.prev ? -1 : 0;
+    if (!fo.verts.snap) return 1;
+    return fo.verts.gbuf && fo.verts.prev && fo.n_snap ? 2 : -1;  // (flag 3 lives in obj)
+}
+template <int S>
+static void ut_launch(int kind, dim3 g, dim3 bl, hipStream_t st, uint32_t W, uint32_t H, uint32_t w, uint32_t h, const UpHistory &Hs,
+                      const UtFollow &fo, const float4 *hg, const float4 *lg, const float4 *lc, const float4 *pg, const float4 *ph,
+                      float4 *hist, float4 *out) {
+    if (kind == 0) hipLaunchKernelGGL((dn_upsample_temporal<S, 0>), g, bl, 0, st, W, H, w, h, Hs, fo, hg, lg, lc, pg, ph, hist, out);
+    else if (kind == 1) hipLaunchKernelGGL((dn_upsample_temporal<S, 1>), g, bl, 0, st, W, H, w, h, Hs, fo, hg, lg, lc, pg, ph, hist, out);
+    else hipLaunchKernelGGL((dn_upsample_temporal<S, 2>), g, bl, 0, st, W, H, w, h, Hs, fo, hg, lg, lc, pg, ph, hist, out);
+}
+template <int S>
+static void ut_launch_win(int kind, dim3 g, dim3 bl, hipStream_t st, uint32_t W, uint32_t H, uint32_t w, uint32_t h,
+                          const UpHistory &Hs, const UtWin &win, const UtFollow &fo, const float4 *hg, const float4 *lg,
+                          const float4 *lc, const float4 *lh, const float4 *pg, const float4 *ph, float4 *hist, float4 *out) {
+    if (kind == 0) hipLaunchKernelGGL((dn_upsample_temporal_win<S, 0>), g, bl, 0, st, W, H, w, h, Hs, win, fo, hg, lg, lc, lh, pg, ph, hist, out);
+    else if (kind == 1) hipLaunchKernelGGL((dn_upsample_temporal_win<S, 1>), g, bl, 0, st, W, H, w, h, Hs, win, fo, hg, lg, lc, lh, pg, ph, hist, out);
+    else hipLaunchKernelGGL((dn_upsample_temporal_win<S, 2>), g, bl, 0, st, W, H, w, h, Hs, win, fo, hg, lg, lc, lh, pg, ph, hist, out);
+}
 hipError_t launch_denoise_upsample_temporal(uint32_t s, uint32_t W, uint32_t H, uint32_t px, uint32_t py, float alpha_min,
-                                            float alpha_fill, uint32_t mode, const float *vp_prev, const float4 *guide_hi,
-                                            const float4 *guide_lo, const float4 *color_lo, const float4 *guide_prev,
-                                            const float4 *hist_prev, float4 *hist, float4 *out, hipStream_t st) {
+                                            float alpha_fill, uint32_t mode, const float *vp_prev, const UtFollow &fo,
+                                            const float4 *guide_hi, const float4 *guide_lo, const float4 *color_lo,
+                                            const float4 *guide_prev, const float4 *hist_prev, float4 *hist, float4 *out,
+                                            hipStream_t st) {
     const dim3 g((W + kDnTile - 1) / kDnTile, (H + kDnTile - 1) / kDnTile), bl(kBlock);
     const uint32_t w = W / s, h = H / s;
-    if (px >= s || py >= s || W != s * w || H != s * h) return hipErrorInvalidValue;  // (the staged window's bound)
+    const int kind = ut_follow_kind(fo);
+    if (px >= s || py >= s || W != s * w || H != s * h || kind < 0) return hipErrorInvalidValue;  // (the staged window's bound)
     UpHistory Hs{};
     for (int i = 0; i < 16; ++i) Hs.vp[i] = vp_prev[i];
     Hs.alpha_min = alpha_min;
@@ -923,20 +993,21 @@ hipError_t launch_denoise_upsample_temporal(uint32_t s, uint32_t W, uint32_t H, 
     Hs.mode = mode;
     Hs.px = px;
     Hs.py = py;
-    if (s == 2u) hipLaunchKernelGGL(dn_upsample_temporal<2>, g, bl, 0, st, W, H, w, h, Hs, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
-    else if (s == 3u) hipLaunchKernelGGL(dn_upsample_temporal<3>, g, bl, 0, st, W, H, w, h, Hs, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
-    else if (s == 4u) hipLaunchKernelGGL(dn_upsample_temporal<4>, g, bl, 0, st, W, H, w, h, Hs, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
+    if (s == 2u) ut_launch<2>(kind, g, bl, st, W, H, w, h, Hs, fo, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
+    else if (s == 3u) ut_launch<3>(kind, g, bl, st, W, H, w, h, Hs, fo, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
+    else if (s == 4u) ut_launch<4>(kind, g, bl, st, W, H, w, h, Hs, fo, guide_hi, guide_lo, color_lo, guide_prev, hist_prev, hist, out);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 hipError_t launch_denoise_upsample_temporal_win(uint32_t s, uint32_t W, uint32_t H, uint32_t px, uint32_t py, float alpha_min,
                                                 float alpha_fill, uint32_t mode, const float *vp_prev, const UtWin &win,
-                                                const float4 *guide_hi, const float4 *guide_lo, const float4 *color_lo,
-                                                const float4 *halo_lo, const float4 *guide_prev, const float4 *hist_prev,
-                                                float4 *hist, float4 *out, hipStream_t st) {
+                                                const UtFollow &fo, const float4 *guide_hi, const float4 *guide_lo,
+                                                const float4 *color_lo, const float4 *halo_lo, const float4 *guide_prev,
+                                                const float4 *hist_prev, float4 *hist, float4 *out, hipStream_t st) {
     const dim3 g((W + kDnTile - 1) / kDnTile, (win.up.Y1 - win.up.Y0 + kDnTile - 1) / kDnTile), bl(kBlock);
     const uint32_t w = W / s, h = H / s;
-    if (px >= s || py >= s || W != s * w || H != s * h) return hipErrorInvalidValue;  // (the staged window's bound)
+    const int kind = ut_follow_kind(fo);
+    if (px >= s || py >= s || W != s * w || H != s * h || kind < 0) return hipErrorInvalidValue;  // (the staged window's bound)
     // the rows the kernel addresses: the band's own inside the covered rows, the window's own rows inside the window
     if (win.up.Y0 >= win.up.Y1 || win.up.Y1 > H || win.hy0 > win.up.Y0 || win.hy0 + win.hrows < win.up.Y1 || !win.clip ||
         win.up.o0 > win.up.o1 || win.up.o1 > win.up.rows)
@@ -948,9 +1019,9 @@ hipError_t launch_denoise_upsample_temporal_win(uint32_t s, uint32_t W, uint32_t
     Hs.mode = mode;
     Hs.px = px;
     Hs.py = py;
-    if (s == 2u) hipLaunchKernelGGL(dn_upsample_temporal_win<2>, g, bl, 0, st, W, H, w, h, Hs, win, guide_hi, guide_lo, color_lo, halo_lo, guide_prev, hist_prev, hist, out);
-    else if (s == 3u) hipLaunchKernelGGL(dn_upsample_temporal_win<3>, g, bl, 0, st, W, H, w, h, Hs, win, guide_hi, guide_lo, color_lo, halo_lo, guide_prev, hist_prev, hist, out);
-    else if (s == 4u) hipLaunchKernelGGL(dn_upsample_temporal_win<4>, g, bl, 0, st, W, H, w, h, Hs, win, guide_hi, guide_lo, color_lo, halo_lo, guide_prev, hist_prev, hist, out);
+    if (s == 2u) ut_launch_win<2>(kind, g, bl, st, W, H, w, h, Hs, win, fo, guide_hi, guide_lo, color_lo, halo_lo, guide_prev, hist_prev, hist, out);
+    else if (s == 3u) ut_launch_win<3>(kind, g, bl, st, W, H, w, h, Hs, win, fo, guide_hi, guide_lo, color_lo, halo_lo, guide_prev, hist_prev, hist, out);
+    else if (s == 4u) ut_launch_win<4>(kind, g, bl, st, W, H, w, h, Hs, win, fo, guide_hi, guide_lo, color_lo, halo_lo, guide_prev, hist_prev, hist, out);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -294,6 +294,21 @@ struct ptx_handle {
     uint32_t ut_camera[19] = {0};
     float ut_vp[16] = {0};
     hipEvent_t ev_ut_ready = nullptr, ev_ut_copied = nullptr;
+    // ptx_upsample_follow (include/ptx.h ptx_upsample_temporal, "Following").  ut_follow: the switch.  ut_track:
+    // the last completely enqueued call was made with the switch on; it kept the instance block (ut_insts) under
+    // layout ut_track_layout.  While tracking with a state, an instance edit or a vertex update keeps ut_valid
+    // and sets ut_pending; refit_after_vertices saves a mesh's triangle records in d_ut_snap (d_tverts' layout,
+    // allocated by the first call with the switch on; the denoiser's d_dn_snap is the shape *its* previous call
+    // saw) before the first refit since that call and marks the mesh in ut_deformed (1 saved, 2 not saved).  The
+    // next call with the switch on builds the table from them (d_ut_obj: DnObj entries, DnPrev behind them);
+    // one with the switch off runs as a first call.  Every call, and everything that drops the state, clears
+    // the marks and the pending flag (ut_drop).
+    bool ut_follow = false, ut_track = false, ut_pending = false;
+    uint32_t ut_track_layout = 0;
+    std::vector<uint32_t> ut_insts;
+    std::vector<uint8_t> ut_deformed;
+    DevBuf d_ut_snap, d_ut_obj;
+    UtFollow ut_fo;  // the table of the call being made (upsample_temporal_alloc -> upsample_temporal_launch)
     // the rows [begin, end) of the ranks above and below, as ptx_comm_init's neighbour check received them
     uint32_t nb_rows[2][2] = {{0, 0}, {0, 0}};
     int present_src = PTX_BUF_ACCUM;
@@ -405,6 +420,11 @@ struct UtCall {
     float sigma_plane = 0.02f, alpha_min = 0.02f, alpha_fill = 0.05f;
     uint32_t px = 0, py = 0, rows = kUtRowsDefault;
 };
+// everything that drops the temporal upsampler's state drops the marks and the pending edit with it
+inline void ut_drop(ptx_handle *h) {
+    h->ut_valid = h->ut_pending = false;
+    h->ut_deformed.clear();
+}
 inline uint32_t ut_cap_top(const ptx_handle *h) { return std::min(kUtRowsMax, h->cfg.row_begin); }
 inline uint32_t ut_cap_bot(const ptx_handle *h) { return std::min(kUtRowsMax, h->cfg.height - h->cfg.row_end); }
 int upsample_temporal_params(ptx_handle *err, const ptx_upsample_temporal_params *p, UtCall &c, const char *what, bool bands);

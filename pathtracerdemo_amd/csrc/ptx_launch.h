@@ -115,10 +115,21 @@ hipError_t launch_denoise_upsample(uint32_t s, uint32_t W, uint32_t H, const flo
 // ptx_upsample_temporal: the same inputs, `color_lo` rendered through phase (px, py) of the s x s block,
 // integrated with the previous call's guide records and history {H.rgb, n} (mode: 0 none, 1 the same
 // camera words, 2 reprojected through vp_prev) into `hist` and, with alpha 1, `out`
+// fo (ptx_upsample_follow): the table of a following call that finds an instance changed or a mesh deformed
+// since the previous one -- DnObj per instance and, with a flag 3 among them, DnVerts, both as
+// launch_denoise_temporal takes them (gbuf: the full-size band's texels from its first row).  obj == nullptr:
+// the kernel without the table (FOLLOW = 0).
+struct UtFollow {
+    const DnObj *obj = nullptr;
+    uint32_t n_obj = 0;
+    uint32_t n_snap = 0;  // triangle records verts.snap holds (a texel's triangle is clamped to them)
+    DnVerts verts;
+};
 hipError_t launch_denoise_upsample_temporal(uint32_t s, uint32_t W, uint32_t H, uint32_t px, uint32_t py, float alpha_min,
-                                            float alpha_fill, uint32_t mode, const float *vp_prev, const float4 *guide_hi,
-                                            const float4 *guide_lo, const float4 *color_lo, const float4 *guide_prev,
-                                            const float4 *hist_prev, float4 *hist, float4 *out, hipStream_t st);
+                                            float alpha_fill, uint32_t mode, const float *vp_prev, const UtFollow &fo,
+                                            const float4 *guide_hi, const float4 *guide_lo, const float4 *color_lo,
+                                            const float4 *guide_prev, const float4 *hist_prev, float4 *hist, float4 *out,
+                                            hipStream_t st);
 // ptx_upsample_bands: rows [Y0, Y1) of the W x H frame (guide_hi and out start at row Y0) from a row
 // window of the small frame: `rows` rows from its row y0 on, where guide_lo starts; the window's rows
 // [o0, o1) are color_lo's (a band's own rows), the rows above and then the rows below them halo_lo's.
@@ -132,7 +143,7 @@ hipError_t launch_denoise_upsample_win(uint32_t s, uint32_t W, uint32_t H, const
 // ptx_upsample_temporal_bands: the same rows and window (`up`), integrated with the rows
 // [hy0, hy0 + hrows) of the frame the previous state covers, where guide_prev and hist_prev start;
 // hist and out start at row Y0.  *clip counts the pixels with a history tap inside the frame but
-// outside those rows (the tap is not taken).
+// outside those rows (the tap is not taken): under a moved camera, and with a table (fo) under any.
 struct UtWin {
     UpWin up;
     uint32_t hy0, hrows;
@@ -140,9 +151,9 @@ struct UtWin {
 };
 hipError_t launch_denoise_upsample_temporal_win(uint32_t s, uint32_t W, uint32_t H, uint32_t px, uint32_t py, float alpha_min,
                                                 float alpha_fill, uint32_t mode, const float *vp_prev, const UtWin &win,
-                                                const float4 *guide_hi, const float4 *guide_lo, const float4 *color_lo,
-                                                const float4 *halo_lo, const float4 *guide_prev, const float4 *hist_prev,
-                                                float4 *hist, float4 *out, hipStream_t st);
+                                                const UtFollow &fo, const float4 *guide_hi, const float4 *guide_lo,
+                                                const float4 *color_lo, const float4 *halo_lo, const float4 *guide_prev,
+                                                const float4 *hist_prev, float4 *hist, float4 *out, hipStream_t st);
 
 // ptx_update_vertices (ptx_refit.hip): one mesh's derived tables from its new vertices.  The ranges of
 // the mesh in the tables, from build_layout (ptx_handle::lay_mesh_*); G, tris, tverts, nodes and subs

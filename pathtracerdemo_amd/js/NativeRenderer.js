@@ -370,6 +370,17 @@ class NativeRenderer {
   }
 
   /**
+   * ptx_upsample_follow: this full-size renderer's UpsampleTemporal follows moved instances and deformed or
+   * skinned meshes.  From the first UpsampleTemporal made with it on, UpdateWorld, UpdateVertices and
+   * SkinVertices keep the history and the next call looks a moved surface's history up where it was; off (the
+   * default) an instance edit and a vertex update drop it.  No GPU work.
+   */
+  SetUpsampleFollow(on) {
+    addon.upsampleFollow(this.Handle, !!on);
+    this.UpsampleFollow = !!on;
+  }
+
+  /**
    * ptx_phase_uniform: this (small) renderer's frame looks through pixel (px, py) of every s x s block
    * of `hi`'s current frame (its Uniform, frame index included); call it where Update() would be.
    */

@@ -1050,6 +1050,29 @@ static napi_value js_present_source(napi_env env, napi_callback_info info) {
     return NULL;
 }
 
+/* upsampleFollow(handle, on): ptx_upsample_follow -- the full-size handle's temporal upsampler follows moved
+ * instances and deformed meshes from the first call made with it on (no GPU work) */
+static napi_value js_upsample_follow(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    uint32_t on = 0;
+    napi_valuetype type = napi_undefined;
+    bool flag = false;
+    if (argc >= 2) napi_typeof(env, argv[1], &type);
+    if (type == napi_boolean && napi_get_value_bool(env, argv[1], &flag) == napi_ok) {
+        on = flag ? 1u : 0u;
+    } else if (type != napi_number || napi_get_value_uint32(env, argv[1], &on) != napi_ok) {
+        napi_throw_type_error(env, NULL, "upsampleFollow(handle, on) needs a boolean (or 0 / 1)");
+        return NULL;
+    }
+    int rc = ptx_upsample_follow(H->h, on);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_upsample_follow");
+    return NULL;
+}
+
 /* buildInfo() -> the JSON string of ptx_build_info (which libptx.so build is loaded) */
 static napi_value js_build_info(napi_env env, napi_callback_info info) {
     (void)info;
@@ -1099,6 +1122,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"skinVertices", NULL, js_skin_vertices, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"readVertices", NULL, js_read_vertices, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"phaseUniform", NULL, js_phase_uniform, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"upsampleFollow", NULL, js_upsample_follow, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
     };
     if (napi_define_properties(env, exports, sizeof later / sizeof later[0], later) != napi_ok) return NULL;
     return exports;

@@ -38,6 +38,7 @@ class Renderer:
         # the temporal Denoise / denoise_bands follow deformed and skinned meshes (ptx_denoise_params.reserved[2]);
         # 0 / 1 (a larger value is the library's to refuse)
         self.follow_vertices: bool | int = False
+        self._upsample_follow = False  # set_upsample_follow: the handle's ptx_upsample_follow switch
         cfg = N.PtxConfig(width=self.width, height=self.height, row_begin=row_begin, row_end=row_end,
                           device=device,
                           pipeline=N.PIPELINES[pipeline], reuse_radius=reuse_radius,
@@ -426,6 +427,19 @@ class Renderer:
                                         alpha_fill=float(alpha_fill))
         self._call("ptx_upsample_temporal", self._h, lo._h, ctypes.byref(p))
 
+    def set_upsample_follow(self, on: bool | int) -> None:
+        """Switch this full-size renderer's UpsampleTemporal / upsample_temporal_bands to follow moved instances
+        and deformed or skinned meshes (ptx_upsample_follow): from the first call made with it on, UpdateScene,
+        UpdateVertices and SkinVertices keep the history, and the next call looks a moved surface's history up
+        where it was.  Off (the default): an instance edit and a vertex update drop the history.  No GPU work."""
+        self._call("ptx_upsample_follow", self._h, int(on))
+        self._upsample_follow = bool(on)
+
+    @property
+    def upsample_follow(self) -> bool:
+        """The switch set_upsample_follow last set."""
+        return self._upsample_follow
+
     def set_phase_of(self, hi: "Renderer", s: int, px: int, py: int) -> None:
         """Set this (small) renderer's uniform to the one that looks through pixel (px, py) of every s x s
         block of `hi`'s current frame (ptx_phase_uniform); the frame index is hi's."""
@@ -495,6 +509,8 @@ class Renderer:
         in upsample_clips().  With no clips the bands' rows are the whole-image UpsampleTemporal's.
         read_denoised / read_upsample_history work per full-size band."""
         assert len(his) == len(los)
+        if len({r.upsample_follow for r in his}) > 1:  # (every band tracks for itself: each makes the same edits)
+            raise ValueError("upsample_temporal_bands: upsample_follow differs between the bands")
         lib = N.load()
         a = (ctypes.c_void_p * len(his))(*[r._h.value for r in his])
         b = (ctypes.c_void_p * len(los))(*[r._h.value for r in los])

@@ -15,6 +15,11 @@
                                                         # ptx_upsample_temporal_bands, 8 pairs
     python tools/denoise_time.py --displayed-frame --bands 8 --upsample 2 --phases --width 3840 --height 2160 \
         --history-rows 16,32,64                         # clipped pixels per band along the yawing camera path
+    python tools/denoise_time.py --upsample 2 --phases --follow            # the same call on a following handle, no edit
+    python tools/denoise_time.py --upsample 2 --phases --edit move|pose [--follow]   # the chair moved / posed before
+                                                        # every call (ptx_upsample_follow: DESIGN.md §4.6)
+    python tools/denoise_time.py --upsample 2 --phases --edit pose --error --width 960 --height 540 --calls 64
+                                                        # the error on the animated chair, following and not
 
 The whole call is timed with device events around it on the handle's stream (a torch stream set
 with ptx_set_stream): the median of --calls calls after --warmup.  The same calls on a
@@ -185,6 +190,8 @@ def upsample_pair(args, **kw):
     hi = Renderer(args.width, args.height, device=0, pipeline=args.pipeline, **kw)
     for r in (lo, hi):
         r.Initialize(cs)
+    if args.follow:
+        hi.set_upsample_follow(True)
     for _ in range(args.frames):
         lo.Update()
         lo.Render()
@@ -234,6 +241,187 @@ def measure_upsample(args):
     for r in (hi, lo):
         r.close()
     out["kernel_sum_ms"] = round(statistics.median(per_call), 4)
+    out["kernel_sum_ms_min_max"] = [round(min(per_call), 4), round(max(per_call), 4)]
+    out["follow"] = bool(args.follow)
+    return out
+
+
+def measure_upsample_edits(args):
+    """--upsample S --phases --edit move|pose [--follow]: ptx_upsample_temporal on a scene that is edited before
+    every call, on both handles: "move" the chair between two places (ptx_update_scene), "pose" the chair between
+    two palettes of a --joints skin (ptx_skin_vertices).  Per call: device events around the call on the full-size
+    handle's stream (they span the table's synchronous upload), the sum of the two kernels' own times on a
+    TIME_LAUNCHES handle, and the host's time for the full-size handle's edit itself (the handle idle), which on a
+    following handle includes the copy of the mesh's triangle records.  share_n_above_1: pixels of the last call
+    whose history holds more than one own sample."""
+    import copy
+    import time
+
+    import numpy as np
+    import torch
+    from pathtracerdemo_amd import _native as N
+    from pathtracerdemo_amd.renderer import Renderer
+    from pathtracerdemo_amd.scene import world as world_mod
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from skin_cost import make_palette, make_skin
+    s = args.upsample
+    base = world_mod.compile_scene(args.scene)
+    CHAIR_MESH, CHAIR = 2, 2
+    sc = copy.deepcopy(world_mod.load_scene_json(args.scene))
+    [a for a in sc["assets"] if a["type"] == "object"][CHAIR]["transform"]["position"] = [25, -90, 10]
+    places = [base, world_mod.serialize_world(world_mod.World().load_from_scene(sc))]
+    blk = world_mod.mesh_blocks(base, CHAIR_MESH)
+    joints, weights, bind = make_skin(base.geometry[blk["vertex"]:blk["vertex_end"]].reshape(-1, 8), args.joints, np)
+    palettes = [make_palette(bind, args.joints, d, np) for d in (25.0, -15.0)]
+
+    def pair(**kw):
+        lo = Renderer(args.width // s, args.height // s, device=0, pipeline=args.pipeline)
+        hi = Renderer(args.width, args.height, device=0, pipeline=args.pipeline, **kw)
+        for r in (lo, hi):
+            r.Initialize(base)
+            r.Update()
+            if args.edit == "pose":
+                r.SetSkin(CHAIR_MESH, joints, weights, bind)
+        if args.follow:
+            hi.set_upsample_follow(True)
+        return lo, hi
+
+    def edit(r, i):
+        if args.edit == "move":
+            cs = places[(i + 1) % 2]
+            return lambda: r._call("ptx_update_scene", r._h, cs.scene.ctypes.data, len(cs.scene), None)
+        pal = palettes[i % 2]
+        return lambda: r._call("ptx_skin_vertices", r._h, CHAIR_MESH, pal.ctypes.data, None)
+
+    def step(lo, hi, i):
+        """Edit both handles, hi's G-buffer pass, lo's frame through the phase, denoised; hi's edit's host ms."""
+        hi.synchronize()
+        t0 = time.perf_counter()
+        edit(hi, i)()
+        t = (time.perf_counter() - t0) * 1e3
+        edit(lo, i)()
+        px, py = phase_of(args, i)
+        hi.Update()
+        hi.run_pass(N.PTX_PASS_GBUFFER)
+        lo.set_phase_of(hi, s, px, py)
+        lo.Render()
+        lo.Denoise(iterations=args.iterations)
+        lo.synchronize()
+        hi.synchronize()
+        return px, py, t
+
+    def mmm(v):
+        return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+
+    out = {"what": "ptx_upsample_temporal after an edit", "edit": args.edit, "follow": bool(args.follow), "scale": s,
+           "width": args.width, "height": args.height, "scene": args.scene, "pipeline": args.pipeline, "joints": args.joints,
+           "calls": args.calls, "warmup": args.warmup}
+    lo, hi = pair()
+    stream = torch.cuda.Stream()
+    hi.set_stream(stream.cuda_stream)
+    ms, edits = [], []
+    for i in range(args.warmup + args.calls):
+        px, py, t = step(lo, hi, i)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        hi.UpsampleTemporal(lo, px, py)
+        b.record(stream)
+        b.synchronize()
+        if i >= args.warmup:
+            ms.append(a.elapsed_time(b))
+            edits.append(t)
+    n = hi.read_upsample_history()[..., 3]
+    out["share_n_above_1"] = round(float((n > 1).mean()), 4)
+    hi.set_stream(None)
+    for r in (hi, lo):
+        r.close()
+    out["whole_call_ms"] = mmm(ms)
+    out["edit_host_ms"] = mmm(edits)
+    lo, hi = pair(time_launches=True)
+    per_call = []
+    for i in range(args.warmup + args.calls):
+        px, py, _ = step(lo, hi, i)
+        before = hi.stats()
+        hi.UpsampleTemporal(lo, px, py)
+        hi.synchronize()
+        after = hi.stats()
+        if i >= args.warmup:
+            per_call.append(after["kernel_ms_total"][N.PTX_STAT_DENOISE] - before["kernel_ms_total"][N.PTX_STAT_DENOISE])
+        out["launches_per_call"] = after["kernel_launches"][N.PTX_STAT_DENOISE] - before["kernel_launches"][N.PTX_STAT_DENOISE]
+    for r in (hi, lo):
+        r.close()
+    out["kernel_sum_ms"] = mmm(per_call)
+    return out
+
+
+def measure_upsample_error(args):
+    """--upsample S --phases --edit pose --error: what following buys on the animated chair.  The chair is posed
+    before every call (two palettes alternating, still camera, 1 spp per small frame); one small handle (temporal
+    denoise, following vertices) feeds two full-size handles, one following and one not, for --calls phase-cycled
+    frames after --warmup.  The reference of a pose is the full-size scene accumulated over --converge frames with
+    the pose held; the error is the mean squared difference of PTX_BUF_DENOISED over the chair's pixels (the
+    pose's own G-buffer), averaged over the frames."""
+    import numpy as np
+    from pathtracerdemo_amd import _native as N
+    from pathtracerdemo_amd.renderer import Renderer
+    from pathtracerdemo_amd.scene import world as world_mod
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from skin_cost import make_palette, make_skin
+    s, CHAIR_MESH, CHAIR = args.upsample, 2, 2
+    base = world_mod.compile_scene(args.scene)
+    blk = world_mod.mesh_blocks(base, CHAIR_MESH)
+    joints, weights, bind = make_skin(base.geometry[blk["vertex"]:blk["vertex_end"]].reshape(-1, 8), args.joints, np)
+    palettes = [make_palette(bind, args.joints, d, np) for d in (25.0, -15.0)]
+
+    def make(w, h):
+        r = Renderer(w, h, device=0, pipeline=args.pipeline, frame_color=True)
+        r.Initialize(base)
+        r.Update()
+        r.SetSkin(CHAIR_MESH, joints, weights, bind)
+        return r
+
+    ref, mask = [], []
+    r = make(args.width, args.height)
+    for pal in palettes:
+        r.SkinVertices(CHAIR_MESH, pal)
+        r.ResetFrameCount()
+        for _ in range(args.converge):
+            r.Update()
+            r.Render()
+        ref.append(r.read_image()[..., :3].astype(np.float64))
+        g = r.read_gbuffer()[..., 0]
+        mask.append((g >> 31 == 1) & ((g >> 16) & 0x7FFF == CHAIR))
+    r.close()
+    lo = make(args.width // s, args.height // s)
+    lo.follow_vertices = True
+    his = {"follow": make(args.width, args.height), "not_following": make(args.width, args.height)}
+    his["follow"].set_upsample_follow(True)
+    err = {k: [] for k in his}
+    for i in range(args.warmup + args.calls):
+        px, py = phase_of(args, i)
+        for r in [lo] + list(his.values()):
+            r.SkinVertices(CHAIR_MESH, palettes[i % 2])
+        for hi in his.values():
+            hi.Update()
+            hi.run_pass(N.PTX_PASS_GBUFFER)
+        lo.set_phase_of(his["follow"], s, px, py)
+        lo.Render()
+        lo.Denoise(iterations=args.iterations, temporal=True)
+        for name, hi in his.items():
+            hi.UpsampleTemporal(lo, px, py)
+            if i >= args.warmup:
+                d = hi.read_denoised()[..., :3].astype(np.float64) - ref[i % 2]
+                err[name].append(float((d[mask[i % 2]] ** 2).mean()))
+    last = (args.warmup + args.calls - 1) % 2
+    out = {"what": "ptx_upsample_temporal on the animated chair, error against the converged pose", "scale": s,
+           "width": args.width, "height": args.height, "scene": args.scene, "pipeline": args.pipeline, "joints": args.joints,
+           "iterations": args.iterations, "frames": args.calls, "warmup": args.warmup, "converge": args.converge,
+           "chair_pixels": [int(m.sum()) for m in mask],
+           "mse_on_chair": {k: float(np.mean(v)) for k, v in err.items()},
+           "mean_n_on_chair": {k: round(float(hi.read_upsample_history()[..., 3][mask[last]].mean()), 2) for k, hi in his.items()}}
+    out["follow_over_not_following"] = round(out["mse_on_chair"]["follow"] / out["mse_on_chair"]["not_following"], 4)
+    for r in [lo] + list(his.values()):
+        r.close()
     return out
 
 
@@ -688,8 +876,23 @@ def main():
     ap.add_argument("--displayed-frame", action="store_true", help="host ms per displayed frame under a yawing camera")
     ap.add_argument("--no-events", action="store_true", help="only the TIME_LAUNCHES handle (the run a profiler traces)")
     ap.add_argument("--trace", help="a rocprofv3 run_kernel_trace.csv of this script: print per-kernel medians")
+    ap.add_argument("--follow", action="store_true", help="--upsample --phases: the full-size handle follows (ptx_upsample_follow)")
+    ap.add_argument("--edit", choices=("move", "pose"), help="--upsample --phases: edit the scene before every call "
+                    "(move: the chair's instance, pose: the chair through a skin), on both handles")
+    ap.add_argument("--joints", type=int, default=32, help="--edit pose: joints of the chair's skin")
+    ap.add_argument("--error", action="store_true", help="--edit pose: the error on the animated chair, following and not, "
+                    "over --calls phase-cycled frames")
+    ap.add_argument("--converge", type=int, default=256, help="--error: frames a pose's reference accumulates")
+    ap.add_argument("--repo", help="the tree whose package is measured (an older one: without --follow), "
+                    "its library or PTX_LIB_PATH's")
     args = ap.parse_args()
-    if args.bands and args.upsample and args.phases:
+    if args.repo:
+        sys.path.insert(0, os.path.abspath(args.repo))
+    if args.edit:
+        assert args.upsample and args.phases and not args.bands, "--edit goes with --upsample S --phases"
+        assert not args.error or args.edit == "pose", "--error goes with --edit pose"
+        out = measure_upsample_error(args) if args.error else measure_upsample_edits(args)
+    elif args.bands and args.upsample and args.phases:
         out = measure_upsample_temporal_bands(args)
     elif args.displayed_frame:
         out = measure_displayed_frame(args)
