@@ -26,6 +26,7 @@ PTX_STAT_PASS_GROUP = 10
 PTX_STAT_FINAL_FUSED = 11
 PTX_STAT_DENOISE = 12  # launches of the denoiser's kernels
 PTX_STAT_REFIT = 13  # launches of ptx_update_vertices' and ptx_skin_vertices' kernels
+PTX_STAT_BUILD = 14  # launches of ptx_build_blas' kernels
 PTX_BUF_GBUFFER, PTX_BUF_RESERVOIR, PTX_BUF_ACCUM, PTX_BUF_COUNTERS, PTX_BUF_RESERVOIR_HIST = 0, 1, 2, 3, 4
 PTX_BUF_DIRECT = 5
 PTX_BUF_DENOISED = 6  # ptx_denoise's output (read-only)
@@ -60,7 +61,7 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_upsample", "ptx_upsample_bands", "ptx_phase_uniform", "ptx_upsample_temporal",
             "ptx_trace_queries", "ptx_upsample_temporal_bands", "ptx_update_scene", "ptx_update_vertices",
             "ptx_read_accel", "ptx_set_skin", "ptx_skin_vertices", "ptx_read_vertices",
-            "ptx_upsample_follow"]
+            "ptx_upsample_follow", "ptx_build_blas"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -96,6 +97,12 @@ class PtxSkinDesc(ctypes.Structure):
                 ("n_joints", ctypes.c_uint32), ("n_targets", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3),
                 ("joints", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("bind", ctypes.c_void_p),
                 ("target_pos", ctypes.c_void_p), ("target_nrm", ctypes.c_void_p)]
+
+
+class PtxBlasDesc(ctypes.Structure):
+    _fields_ = [("positions", ctypes.c_void_p), ("n_vertices", ctypes.c_uint32), ("indices", ctypes.c_void_p),
+                ("n_tris", ctypes.c_uint32), ("groups", ctypes.c_void_p), ("n_groups", ctypes.c_uint32),
+                ("max_leaf", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
 class PtxError(RuntimeError):
@@ -142,6 +149,7 @@ def load(path: str = LIB_PATH):
     lib.ptx_set_skin.argtypes = [H, ctypes.POINTER(PtxSkinDesc)]
     lib.ptx_skin_vertices.argtypes = [H, ctypes.c_uint32, P, P]
     lib.ptx_read_vertices.argtypes = [H, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]
+    lib.ptx_build_blas.argtypes = [H, ctypes.POINTER(PtxBlasDesc), P, ctypes.c_size_t, P, P, P]
     lib.ptx_set_frame.argtypes = [H, P]
     lib.ptx_render.argtypes = [H, P]
     lib.ptx_run_pass.argtypes = [H, ctypes.c_int]

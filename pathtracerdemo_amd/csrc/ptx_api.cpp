@@ -2740,6 +2740,149 @@ int ptx_skin_vertices(ptx_handle *h, uint32_t mesh, const float *palette, const 
     return refit_after_vertices(h, mesh, le, kStaleGeometry | kStaleAccel, what);
 }
 
+// ptx_build_blas: host side.  One arena holds every device array of the call (BuildArgs, ptx_launch.h), the
+// zeroed words first; it is freed before the call returns.
+namespace {
+struct BuildArena {
+    DevBuf buf;
+    size_t used = 0;
+    ~BuildArena() { free_buf(buf); }
+    size_t take(size_t bytes) {
+        const size_t at = used;
+        used += (bytes + 255u) & ~(size_t)255u;
+        return at;
+    }
+    void *at(size_t off) const { return (char *)buf.p + off; }
+};
+}  // namespace
+
+int ptx_build_blas(ptx_handle *h, const ptx_blas_desc *d, uint32_t *nodes_out, size_t n_node_words, uint32_t *indices_out,
+                   uint32_t *group_nodes_out, uint32_t *max_depth_out) {
+    if (!h) return PTX_E_INVALID;
+    const char *what = "ptx_build_blas";
+    if (!d) return fail(h, PTX_E_INVALID, "%s: null descriptor", what);
+    if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return fail(h, PTX_E_INVALID, "%s: a reserved word is not zero", what);
+    const uint32_t T = d->n_tris, V = d->n_vertices, G = d->n_groups;
+    if (T == 0u || T > LEAF_FIRST_MASK + 1u) return fail(h, PTX_E_INVALID, "%s: %u triangles (1..%u)", what, T, LEAF_FIRST_MASK + 1u);
+    if (d->max_leaf > 64u) return fail(h, PTX_E_INVALID, "%s: max_leaf %u (0 = 10, or 1..64)", what, d->max_leaf);
+    if (!d->positions || !d->indices || (!d->groups && G) || !indices_out || (!group_nodes_out && G) || !max_depth_out ||
+        (!nodes_out && G))
+        return fail(h, PTX_E_INVALID, "%s: null array", what);
+    uint64_t worst = 0, next_free = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        const uint64_t first = d->groups[2u * g], count = d->groups[2u * g + 1u];
+        if (count == 0u) return fail(h, PTX_E_INVALID, "%s: group %u is empty", what, g);
+        if (first < next_free) return fail(h, PTX_E_INVALID, "%s: group %u begins at triangle %llu, inside or ahead of group %u", what, g,
+                                           (unsigned long long)first, g - 1u);
+        if (first + count > T) return fail(h, PTX_E_INVALID, "%s: group %u reaches triangle %llu of %u", what, g,
+                                           (unsigned long long)(first + count), T);
+        next_free = first + count;
+        worst += 2u * count - 1u;
+    }
+    if ((uint64_t)n_node_words < 8u * worst)
+        return fail(h, PTX_E_INVALID, "%s: %zu node words, the groups may need %llu", what, n_node_words, (unsigned long long)(8u * worst));
+    for (size_t i = 0; i < 3u * (size_t)T; ++i)
+        if (d->indices[i] >= V) return fail(h, PTX_E_INVALID, "%s: triangle %zu: index %u of %u vertices", what, i / 3u, d->indices[i], V);
+    double unused = 0.0;
+    if (!all_finite(d->positions, 3u * (size_t)V, unused)) return fail(h, PTX_E_INVALID, "%s: a position is not finite", what);
+    if (G == 0u) {  // nothing to build: every triangle keeps its place
+        std::memcpy(indices_out, d->indices, 12u * (size_t)T);
+        *max_depth_out = 0u;
+        return PTX_OK;
+    }
+    // From here on the GPU is touched, but nothing a frame reads or writes.
+    HIP_CHECK(h, hipSetDevice(h->device));
+    const hipStream_t st = h->cur().stream;
+    BuildArgs A{};
+    A.n_tris = T;
+    A.n_groups = G;
+    A.max_leaf = d->max_leaf ? d->max_leaf : 10u;
+    A.n_nodes = (uint32_t)worst;
+    BuildArena ar;
+    const size_t o_cbound = ar.take(24u * (size_t)G), o_done = ar.take(8u * (size_t)T), o_depth = ar.take(4u);
+    const size_t zero_bytes = ar.used;
+    const size_t o_parent = ar.take(8u * (size_t)T);
+    const size_t o_pos = ar.take(12u * (size_t)V), o_idx = ar.take(12u * (size_t)T), o_groups = ar.take(8u * (size_t)G);
+    const size_t o_tbox = ar.take(24u * (size_t)T), o_centre = ar.take(12u * (size_t)T), o_seg = ar.take(4u * (size_t)T);
+    const size_t o_kin = ar.take(8u * (size_t)T), o_kout = ar.take(8u * (size_t)T);
+    const size_t o_vin = ar.take(4u * (size_t)T), o_vout = ar.take(4u * (size_t)T);
+    const size_t o_rng = ar.take(8u * (size_t)T), o_child = ar.take(8u * (size_t)T);
+    const size_t o_nbox = ar.take(48u * (size_t)T), o_esize = ar.take(8u * (size_t)T);
+    const size_t o_gsize = ar.take(4u * (size_t)G), o_goff = ar.take(4u * (size_t)G);
+    const size_t o_nodes = ar.take(32u * (size_t)worst), o_iout = ar.take(12u * (size_t)T);
+    hipError_t le = build_sort_bytes(A, &A.sort_bytes);
+    if (le != hipSuccess) return fail(h, PTX_E_HIP, "%s: sort storage: %s", what, hipGetErrorString(le));
+    const size_t o_sort = ar.take(A.sort_bytes);
+    if (int rc = alloc_buf(h, ar.buf, ar.used)) return rc;
+    A.cbound = (uint32_t *)ar.at(o_cbound);
+    A.done = (uint32_t *)ar.at(o_done);
+    A.max_depth = (uint32_t *)ar.at(o_depth);
+    A.parent = (uint32_t *)ar.at(o_parent);
+    A.pos = (float *)ar.at(o_pos);
+    A.idx = (uint32_t *)ar.at(o_idx);
+    A.groups = (uint2 *)ar.at(o_groups);
+    A.tbox = (float2 *)ar.at(o_tbox);
+    A.centre = (float *)ar.at(o_centre);
+    A.seg = (uint32_t *)ar.at(o_seg);
+    A.key_in = (unsigned long long *)ar.at(o_kin);
+    A.key_out = (unsigned long long *)ar.at(o_kout);
+    A.val_in = (uint32_t *)ar.at(o_vin);
+    A.val_out = (uint32_t *)ar.at(o_vout);
+    A.rng = (uint2 *)ar.at(o_rng);
+    A.child = (uint2 *)ar.at(o_child);
+    A.nbox = (float2 *)ar.at(o_nbox);
+    A.esize = (uint32_t *)ar.at(o_esize);
+    A.gsize = (uint32_t *)ar.at(o_gsize);
+    A.goff = (uint32_t *)ar.at(o_goff);
+    A.nodes_out = (uint32_t *)ar.at(o_nodes);
+    A.idx_out = (uint32_t *)ar.at(o_iout);
+    A.sort_temp = (void *)ar.at(o_sort);
+    le = hipMemsetAsync(ar.buf.p, 0, zero_bytes, st);
+    if (le == hipSuccess) le = hipMemsetAsync(A.parent, 0xFF, 8u * (size_t)T, st);
+    if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_pos), d->positions, 12u * (size_t)V, hipMemcpyHostToDevice);
+    if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_idx), d->indices, 12u * (size_t)T, hipMemcpyHostToDevice);
+    if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_groups), d->groups, 8u * (size_t)G, hipMemcpyHostToDevice);
+    auto step = [&](BuildStep s, uint32_t stamp = 0u) {
+        le = slot_timed(h, PTX_STAT_BUILD, st, le, [&] { return launch_build(A, s, stamp, st); });
+    };
+    step(BuildStep::Tris);
+    step(BuildStep::Keys);
+    step(BuildStep::Sort);
+    step(BuildStep::Tree);
+    step(BuildStep::Leaves);
+    // One launch per height of the emitted tree, which the host does not know: rounds of kRound launches and a
+    // readback of the roots' sizes, until every root is finished.  A key has 62 bits, which bounds a tree's height.
+    constexpr uint32_t kRound = 24u, kMaxHeight = 72u;
+    std::vector<uint32_t> gsize(G), goff(G);
+    uint32_t stamp = 2u;
+    bool finished = false;
+    while (le == hipSuccess && !finished && stamp < 2u + kMaxHeight) {
+        for (uint32_t k = 0; k < kRound; ++k) step(BuildStep::Level, stamp++);
+        step(BuildStep::Roots);
+        if (le != hipSuccess) break;
+        if (int rc = read_to_host(h, gsize.data(), A.gsize, 4u * (size_t)G)) return rc;
+        finished = std::find(gsize.begin(), gsize.end(), 0u) == gsize.end();
+    }
+    if (le != hipSuccess) return fail(h, PTX_E_HIP, "%s: %s", what, hipGetErrorString(le));
+    if (!finished) return fail(h, PTX_E_HIP, "%s: the tree did not finish in %u heights", what, kMaxHeight);
+    uint64_t total = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        goff[g] = (uint32_t)total;
+        total += gsize[g];
+    }
+    if (total > worst) return fail(h, PTX_E_HIP, "%s: %llu nodes, more than the groups can need", what, (unsigned long long)total);
+    A.n_nodes = (uint32_t)total;
+    le = copy_sync(h, (void *)ar.at(o_goff), goff.data(), 4u * (size_t)G, hipMemcpyHostToDevice);
+    step(BuildStep::Emit);
+    step(BuildStep::Gather);
+    if (le != hipSuccess) return fail(h, PTX_E_HIP, "%s: %s", what, hipGetErrorString(le));
+    if (int rc = read_to_host(h, nodes_out, A.nodes_out, 32u * (size_t)total)) return rc;
+    if (int rc = read_to_host(h, indices_out, A.idx_out, 12u * (size_t)T)) return rc;
+    if (int rc = read_to_host(h, max_depth_out, A.max_depth, 4u)) return rc;
+    std::memcpy(group_nodes_out, gsize.data(), 4u * (size_t)G);
+    return PTX_OK;
+}
+
 int ptx_read_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uint32_t n_vertices, uint32_t *records_out) {
     if (!h) return PTX_E_INVALID;
     if (int rc = vertex_range_check(h, "ptx_read_vertices", mesh, first_vertex, n_vertices)) return rc;

@@ -192,6 +192,40 @@ struct SkinArgs {
 };
 hipError_t launch_skin_vertices(const SkinArgs &a, hipStream_t s);
 
+// ptx_build_blas (ptx_build.hip): one mesh's BLAS as an LBVH.  Every pointer is device memory of the call.
+// Radix nodes are numbered by sorted position: the internal node i of a group at first_tri + i (ids [0, T)),
+// the leaf of sorted position p at T + p (ids [T, 2T)).
+struct BuildArgs {
+    const float *pos;            // V x 3
+    const uint32_t *idx;         // 3T, the input index buffer
+    const uint2 *groups;         // n_groups x {first_tri, tri_count}
+    uint32_t n_tris, n_groups, max_leaf;
+    uint32_t n_nodes;            // nodes nodes_out holds (build_emit)
+    float2 *tbox;                // 3 float2 per triangle, input order: {lo.x, lo.y}, {lo.z, hi.x}, {hi.y, hi.z}
+    float *centre;               // 3 per triangle, input order
+    uint32_t *seg;               // per position: 2g + 1 inside group g, 2g in the gap ahead of it
+    uint32_t *cbound;            // 6 per group, zeroed: ~ordered(min) xyz, ordered(max) xyz of the centres
+    unsigned long long *key_in, *key_out;  // segment << 30 | code, before and after the sort
+    uint32_t *val_in, *val_out;  // the triangle's input position
+    void *sort_temp;
+    size_t sort_bytes;
+    uint2 *rng, *child;          // per internal node: its sorted positions [a, b]; its children's ids
+    uint32_t *parent;            // per id, 0xFF-filled: the parent's id (a root keeps 0xFFFFFFFF)
+    float2 *nbox;                // per id: the box of an emitted node, tbox's layout
+    uint32_t *esize;             // per id: emitted nodes of its subtree
+    uint32_t *done;              // per id, zeroed: the stamp of the launch that finished it (build_level)
+    uint32_t *gsize;             // per group: its root's esize, 0 while unfinished
+    const uint32_t *goff;        // per group: its root's node in nodes_out
+    uint32_t *nodes_out;         // 8 words per node
+    uint32_t *idx_out;           // 3T
+    uint32_t *max_depth;         // zeroed
+};
+enum class BuildStep { Tris, Keys, Sort, Tree, Leaves, Level, Roots, Emit, Gather };
+// the sort's temporary storage for A.n_tris keys of A.n_groups groups
+hipError_t build_sort_bytes(const BuildArgs &A, size_t *bytes);
+// one step of the chain; `stamp` is build_level's (2, 3, ...: one launch per height of the emitted tree)
+hipError_t launch_build(const BuildArgs &A, BuildStep step, uint32_t stamp, hipStream_t s);
+
 // closest-hit queries for a ray array (ptx_kernels.hip)
 hipError_t launch_trace_rays(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,
                              uint32_t stack_depth, hipStream_t s);

@@ -11,26 +11,13 @@
 //   refit_roots   one thread per sub-mesh root: its pair's union, or its leaf's box.
 // Launch boundaries are the only ordering: no workgroup waits for another.
 #include "ptx_launch.h"
+#include "ptx_tribox.h"
 
 namespace ptx {
 
 struct Box {
     float lo[3], hi[3];
 };
-
-// The builder's triangle bounds: centre and half-extent in f64 from the f32 positions, the half widened
-// by 2^-24 of the magnitudes, both rounded to f32; the box is their f64 difference and sum rounded to
-// f32.  Every operation is rounded on its own (no fused multiply-add: the expression is the builder's).
-__device__ __forceinline__ void tri_axis_bounds(float a, float b, float c, float &lo, float &hi) {
-#pragma clang fp contract(off)
-    const double mn = (double)fminf(a, fminf(b, c)), mx = (double)fmaxf(a, fmaxf(b, c));
-    const double half = (mx - mn) / 2.0;
-    const float cf = (float)(mn + half);
-    const double wide = (fabs(mn) + half) * 0x1p-24;
-    const float hf = (float)(half + wide);
-    lo = (float)((double)cf - (double)hf);
-    hi = (float)((double)cf + (double)hf);
-}
 
 __device__ __forceinline__ Box box_empty() {
     Box b;

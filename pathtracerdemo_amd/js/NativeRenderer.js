@@ -244,6 +244,35 @@ class NativeRenderer {
   }
 
   /**
+   * A mesh's BLAS built on the GPU (ptx_build_blas: an LBVH), in the shapes bvh.js buildBlas produces:
+   * {roots: one Uint32Array of 8 words per node per group, indices (and index): the reordered Uint32Array,
+   * maxDepth}.  `positions` a Float32Array of 3 per vertex, `indices` a Uint32Array of 3 per triangle, `groups`
+   * an array of [firstTriangle, triangleCount].  Needs no world; changes nothing a frame reads.  Blocking; a
+   * refused call throws.
+   */
+  BuildBlas(positions, indices, groups, maxLeafTris = 10) {
+    if (!(positions instanceof Float32Array) || !(indices instanceof Uint32Array) || !Array.isArray(groups) ||
+        !Number.isInteger(maxLeafTris) || maxLeafTris < 0) {
+      throw new TypeError('BuildBlas: expected (Float32Array, Uint32Array, [[first, count], ...], maxLeafTris)');
+    }
+    const flat = Uint32Array.from(groups.flat());
+    if (flat.length !== 2 * groups.length) throw new TypeError('BuildBlas: a group is [firstTriangle, triangleCount]');
+    let worst = 0;
+    for (let g = 0; g < groups.length; g++) worst += Math.max(0, 2 * flat[2 * g + 1] - 1);
+    const nodes = new Uint32Array(8 * worst);
+    const out = new Uint32Array(indices.length);
+    const counts = new Uint32Array(groups.length);
+    const maxDepth = addon.buildBlas(this.Handle, positions, indices, flat, maxLeafTris, nodes, out, counts);
+    const roots = [];
+    let at = 0;
+    for (const c of counts) {
+      roots.push(nodes.slice(at, at + 8 * c));
+      at += 8 * c;
+    }
+    return { roots, indices: out, index: out, maxDepth };
+  }
+
+  /**
    * Bind a skin to the vertices [first, first + joints.length / 4) of mesh `mesh` (ptx_set_skin): `joints`
    * a Uint32Array and `weights` a Float32Array of four per vertex; optional Float32Arrays `bind` (six per
    * vertex: position, normal; null: the records as the handle holds them now), `targets` (morph position

@@ -143,6 +143,29 @@ class Renderer:
         self._call("ptx_read_accel", self._h, out.ctypes.data if len(out) else None, len(out))
         return out
 
+    def build_blas(self, positions, indices, groups, max_leaf_tris: int = 10):
+        """A mesh's BLAS built on the GPU (ptx_build_blas: an LBVH), with scene.bvh.build_blas' signature and
+        results -- (roots: one u32 node array per group, the reordered indices, the largest depth) -- bit for
+        bit scene.lbvh.build_blas_lbvh's.  Needs no scene; changes nothing a frame reads.
+        compile_scene(name, builder=renderer.build_blas) compiles a scene with these trees."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        grp = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1, 2)
+        if len(idx) % 3:
+            raise ValueError("build_blas: three indices per triangle")
+        n_words = 8 * int((2 * grp[:, 1].astype(np.int64) - 1).clip(min=0).sum())
+        nodes = np.zeros(n_words, np.uint32)
+        out_idx = np.zeros(len(idx), np.uint32)
+        counts = np.zeros(len(grp), np.uint32)
+        depth = ctypes.c_uint32(0)
+        d = N.PtxBlasDesc(positions=pos.ctypes.data, n_vertices=len(pos), indices=idx.ctypes.data, n_tris=len(idx) // 3,
+                          groups=grp.ctypes.data if len(grp) else None, n_groups=len(grp), max_leaf=int(max_leaf_tris))
+        self._call("ptx_build_blas", self._h, ctypes.byref(d), nodes.ctypes.data if n_words else None, n_words,
+                   out_idx.ctypes.data, counts.ctypes.data if len(grp) else None, ctypes.addressof(depth))
+        ends = 8 * np.cumsum(counts.astype(np.int64))
+        roots = [nodes[e - 8 * int(c):e].copy() for e, c in zip(ends, counts)]
+        return roots, out_idx, int(depth.value)
+
     def SetSkin(self, mesh: int, joints, weights, bind=None, targets=None, target_normals=None, first: int = 0) -> None:
         """Bind a skin to vertices [first, first + n) of mesh `mesh` (ptx_set_skin): `joints` (n, 4) integers,
         `weights` (n, 4) f32, `bind` (n, 6) f32 {p, n} (None: the records as the handle holds them now),

@@ -121,13 +121,11 @@ _MESH_CACHE: dict = {}
 _DATA_CACHE: dict = {}
 
 
-def mesh_data(name: str, asset_dir: str | None = None) -> MeshData:
-    """Mesh.Load + constructor (Structs.ts:71-141): GLB primitives merged with one group
-    per primitive (mergeGeometries(geoms, true)), SAH BLAS per group."""
+def merged_geometry(name: str, asset_dir: str | None = None):
+    """A GLB's primitives merged as mergeGeometries(geoms, useGroups=true) does, before any BLAS builder
+    reorders the index buffer: (positions (V, 3) f32, normals (V, 3) f32, uvs (V, 2) f32 or None, indices
+    (3T,) u32, groups [(first_tri, tri_count)] one per primitive, materials)."""
     path = os.path.join(asset_dir or ASSET_DIR, name + ".glb")
-    key = (os.path.abspath(path), os.path.getmtime(path))
-    if key in _DATA_CACHE:
-        return _DATA_CACHE[key]
     prims = Glb(path).primitives()
     has_uv = all(p.uvs is not None for p in prims)
     pos, nrm, uvs, idx, groups, mats = [], [], [], [], [], []
@@ -146,21 +144,38 @@ def mesh_data(name: str, asset_dir: str | None = None) -> MeshData:
     positions = np.concatenate(pos).astype(np.float32)
     normals = np.concatenate(nrm).astype(np.float32)
     indices = np.concatenate(idx).astype(np.uint32)
-    roots, indices, max_depth = build_blas(positions, indices, groups)
-    md = MeshData(positions=positions, normals=normals,
-                  uvs=np.concatenate(uvs).astype(np.float32) if has_uv else None, indices=indices,
+    return (positions, normals, np.concatenate(uvs).astype(np.float32) if has_uv else None, indices, groups, mats)
+
+
+def _cache_key(path: str, builder):
+    """The caches' key: the file, and the BLAS builder where it is not the default one."""
+    key = (os.path.abspath(path), os.path.getmtime(path))
+    return key if builder is None else key + (builder,)
+
+
+def mesh_data(name: str, asset_dir: str | None = None, builder=None) -> MeshData:
+    """Mesh.Load + constructor (Structs.ts:71-141): GLB primitives merged with one group
+    per primitive (mergeGeometries(geoms, true)), SAH BLAS per group.  `builder`: a callable with
+    build_blas' signature and results in its place (lbvh.build_blas_lbvh, Renderer.build_blas)."""
+    path = os.path.join(asset_dir or ASSET_DIR, name + ".glb")
+    key = _cache_key(path, builder)
+    if key in _DATA_CACHE:
+        return _DATA_CACHE[key]
+    positions, normals, uvs, indices, groups, mats = merged_geometry(name, asset_dir)
+    roots, indices, max_depth = (builder or build_blas)(positions, indices, groups)
+    md = MeshData(positions=positions, normals=normals, uvs=uvs, indices=indices,
                   roots=[np.asarray(r, dtype=np.uint32) for r in roots], materials=mats, max_depth=max_depth)
     _DATA_CACHE[key] = md
     return md
 
 
-def load_mesh(name: str, asset_dir: str | None = None) -> SerializedMesh:
+def load_mesh(name: str, asset_dir: str | None = None, builder=None) -> SerializedMesh:
     """Mesh.Load + constructor + Serialize (Structs.ts:71-215)."""
     path = os.path.join(asset_dir or ASSET_DIR, name + ".glb")
-    key = (os.path.abspath(path), os.path.getmtime(path))
+    key = _cache_key(path, builder)
     if key in _MESH_CACHE:
         return _MESH_CACHE[key]
-    md = mesh_data(name, asset_dir)
+    md = mesh_data(name, asset_dir, builder)
     blas, root_offsets = merge_arrays(md.roots)
     vert = np.zeros((md.positions.shape[0], STRIDE_VERTEX), dtype=np.float32)
     vert[:, 0:3] = md.positions
@@ -241,10 +256,11 @@ def euler_degrees_to_quat(e) -> np.ndarray:
 class World:
     """World.ts:36-231."""
 
-    def __init__(self, asset_dir: str | None = None):
+    def __init__(self, asset_dir: str | None = None, builder=None):
         self.instances: dict[str, Instance] = {}
         self.lights: list[Light] = []
         self.asset_dir = asset_dir
+        self.builder = builder  # the meshes' BLAS builder (mesh_data); None: build_blas
 
     def add_instance(self, name, mesh_name, translation=(0, 0, 0), rotation=None, scale=(1, 1, 1)):
         self.instances[name] = Instance(mesh_name, translation, rotation, scale)
@@ -282,7 +298,7 @@ class World:
         inst = list(self.instances.values())
         used: dict[str, SerializedMesh] = {}
         for i in inst:
-            used[i.mesh_id] = load_mesh(i.mesh_id, self.asset_dir)
+            used[i.mesh_id] = load_mesh(i.mesh_id, self.asset_dir, self.builder)
         mesh_index = {name: k for k, name in enumerate(used.keys())}
         return inst, list(used.values()), mesh_index
 
@@ -438,10 +454,11 @@ def scene_from_backend(record) -> dict:
     return rec
 
 
-def compile_scene(name_or_dict, asset_dir: str | None = None) -> CompiledScene:
-    """A scene name (scenes/<name>.json), a Scene dict, or a backend record (scene_from_backend)."""
+def compile_scene(name_or_dict, asset_dir: str | None = None, builder=None) -> CompiledScene:
+    """A scene name (scenes/<name>.json), a Scene dict, or a backend record (scene_from_backend).
+    `builder`: the meshes' BLAS builder (mesh_data); None: the SAH builder, build_blas."""
     if isinstance(name_or_dict, str) and not name_or_dict.lstrip().startswith("{"):
         scene = load_scene_json(name_or_dict)
     else:
         scene = scene_from_backend(name_or_dict)
-    return serialize_world(World(asset_dir).load_from_scene(scene))
+    return serialize_world(World(asset_dir, builder).load_from_scene(scene))

@@ -1,0 +1,184 @@
+#!/usr/bin/env python3
+"""What building a BLAS on the GPU costs, and what its LBVH trees cost a frame.
+
+    python tools/build_cost.py                 # 1920x1080, C3, reuse pipeline
+
+(a) Build cost, per mesh (Chair.glb, TestScene.glb), on one idle handle made with PTX_FLAG_TIME_LAUNCHES:
+    the host wall clock of one ptx_build_blas (blocking: the span ends with the nodes read back), the device
+    time of its kernels (PTX_STAT_BUILD) and their number, each as median, minimum and maximum over --builds
+    calls after --warmup; the Python SAH builder (scene/bvh.py build_blas) and the numpy LBVH rule
+    (scene/lbvh.py) on this host, once each; the two trees' SAH cost (bvh.py's model) and depth.
+(b) The scene's way in: compile_scene with the GPU builder (GLB parse, ptx_build_blas per mesh, serialise) +
+    ptx_upload_scene + ptx_set_frame, against ptx_upload_scene + ptx_set_frame of arrays made beforehand
+    (today's re-upload), each repeated on a handle that already holds a scene of that size and has just rendered
+    two frames; the builds' share is reported on its own.
+(c) Tracing cost: frames of the scene with its SAH trees and with its LBVH trees, one process, one build, two
+    handles alive throughout; the two alternate, --runs runs of --frames frames each (after a warm-up run of
+    each), a run's figure its mean frame time, a scene's the median over its runs.  The frame-time ratio, the
+    SAH-cost ratio and the two max_bvh_depths.
+One JSON line.  No threshold: the tool measures."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def spread(xs):
+    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4)}
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    out = fn()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--pipeline", default="reuse")
+    ap.add_argument("--scene", default="c3_interior_32")
+    ap.add_argument("--builds", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--frames", type=int, default=40)
+    ap.add_argument("--repo", default=ROOT, help="the tree whose package and library are measured")
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.repo))
+    import numpy as np
+    from pathtracerdemo_amd import _native as N
+    from pathtracerdemo_amd.renderer import Renderer
+    from pathtracerdemo_amd.scene import world as world_mod
+    from pathtracerdemo_amd.scene.bvh import build_blas
+    from pathtracerdemo_amd.scene.lbvh import build_blas_lbvh, sah_cost
+
+    out = {"tool": "build_cost", "width": args.width, "height": args.height, "pipeline": args.pipeline,
+           "scene": args.scene, "builds": args.builds, "warmup": args.warmup, "runs": args.runs, "frames": args.frames}
+    r = Renderer(args.width, args.height, device=0, pipeline=args.pipeline, time_launches=True)
+
+    def build_stats():
+        s = r.stats()
+        return s["kernel_ms_total"][N.PTX_STAT_BUILD], s["kernel_launches"][N.PTX_STAT_BUILD]
+
+    # ---------------------------------------------------------------- (a) per mesh
+    for label in ("Chair", "TestScene"):
+        pos, _, _, idx, groups, _ = world_mod.merged_geometry(label)
+        t_call, t_kern, launches = [], [], 0
+        for k in range(args.warmup + args.builds):
+            r.synchronize()
+            ms0, n0 = build_stats()
+            t, built = timed(lambda: r.build_blas(pos, idx, groups))
+            ms1, n1 = build_stats()
+            if k >= args.warmup:
+                t_call.append(t)
+                t_kern.append(ms1 - ms0)
+                launches = n1 - n0
+        t_sah, sah = timed(lambda: build_blas(pos, idx, groups))
+        t_np, lb = timed(lambda: build_blas_lbvh(pos, idx, groups))
+        def fold(w):  # (a zero box word may carry either sign: include/ptx.h)
+            w = np.array(w, np.uint32).reshape(-1, 8)
+            w[:, 0:6][w[:, 0:6] == 0x80000000] = 0
+            return w
+        same = all(np.array_equal(fold(a), fold(b)) for a, b in zip(built[0], lb[0])) and np.array_equal(built[1], lb[1])
+        out[label] = {"triangles": int(len(idx) // 3), "groups": len(groups),
+                      "build_blas_host_ms": spread(t_call), "build_kernels_ms": spread(t_kern), "build_launches": int(launches),
+                      "python_sah_ms": round(t_sah, 1), "numpy_lbvh_ms": round(t_np, 1), "gpu_equals_numpy": bool(same),
+                      "nodes_sah": int(sum(len(x) for x in sah[0]) // 8), "nodes_lbvh": int(sum(len(x) for x in lb[0]) // 8),
+                      "depth_sah": int(sah[2]), "depth_lbvh": int(lb[2]),
+                      "sah_cost_sah": round(sah_cost(sah[0]), 3), "sah_cost_lbvh": round(sah_cost(lb[0]), 3)}
+
+    # ---------------------------------------------------------------- (b) the scene's way in
+    cs_sah = world_mod.compile_scene(args.scene)
+    r.Initialize(cs_sah)
+    r.Update()
+    r.Render()
+    r.synchronize()
+
+    def upload(cs):
+        r.compiled = cs
+        r._call("ptx_upload_scene", r._h, cs.scene.ctypes.data, len(cs.scene), cs.geometry.ctypes.data, len(cs.geometry),
+                cs.accel.ctypes.data, len(cs.accel))
+        r._call("ptx_set_frame", r._h, r.uniform.ctypes.data)  # (the layout is derived here)
+
+    # (each loop keeps its scene's sizes from call to call: a scene of another size also pays for new device tables)
+    t_way, t_builds, t_up = [], [], []
+    def warm():  # two frames and a wait, as tools/refit_cost.py times its calls: an idle handle, not a cold one
+        for _ in range(2):
+            r.Update()
+            r.Render()
+        r.synchronize()
+
+    for k in range(args.warmup + 7):
+        warm()
+        t, _ = timed(lambda: upload(cs_sah))
+        if k >= args.warmup:
+            t_up.append(t)
+    cs_lbvh = None
+    for k in range(args.warmup + 7):
+        spent = [0.0]
+
+        def fresh(p, i, g, m=10):  # (a new callable each time: the mesh caches key on the builder)
+            t, res = timed(lambda: r.build_blas(p, i, g, m))
+            spent[0] += t
+            return res
+        warm()
+
+        def way_in():
+            cs = world_mod.compile_scene(args.scene, builder=fresh)
+            upload(cs)
+            return cs
+        t, cs_lbvh = timed(way_in)
+        if k >= args.warmup:
+            t_way.append(t)
+            t_builds.append(spent[0])
+    out["build_compile_upload_ms"] = spread(t_way)
+    out["builds_within_ms"] = spread(t_builds)
+    out["upload_scene_set_frame_ms"] = spread(t_up)
+
+    # ---------------------------------------------------------------- (c) tracing cost
+    names = []
+    for a in world_mod.load_scene_json(args.scene)["assets"]:
+        if a.get("type") == "object" and a.get("meshName") and a["meshName"] not in names:
+            names.append(a["meshName"])
+    cost_sah = sum(sah_cost(world_mod.mesh_data(n).roots) for n in names)
+    cost_lbvh = sum(sah_cost(world_mod.mesh_data(n, builder=build_blas_lbvh).roots) for n in names)
+    r.close()
+    handles = {}
+    for label, cs in (("sah", cs_sah), ("lbvh", cs_lbvh)):
+        h = Renderer(args.width, args.height, device=0, pipeline=args.pipeline)
+        h.Initialize(cs)
+        handles[label] = h
+
+    def run(h):
+        h.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.frames):
+            h.Update()
+            h.Render()
+        h.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / args.frames
+
+    per = {"sah": [], "lbvh": []}
+    for k in range(1 + args.runs):
+        for label in ("sah", "lbvh") if k % 2 == 0 else ("lbvh", "sah"):
+            t = run(handles[label])
+            if k >= 1:
+                per[label].append(t)
+    out["frame_ms_sah"] = spread(per["sah"])
+    out["frame_ms_lbvh"] = spread(per["lbvh"])
+    out["frame_time_ratio"] = round(statistics.median(per["lbvh"]) / statistics.median(per["sah"]), 4)
+    out["sah_cost_ratio"] = round(cost_lbvh / cost_sah, 4)
+    out["max_bvh_depth_sah"] = int(handles["sah"].stats()["max_bvh_depth"])
+    out["max_bvh_depth_lbvh"] = int(handles["lbvh"].stats()["max_bvh_depth"])
+    for h in handles.values():
+        h.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
