@@ -358,13 +358,58 @@ int ptx_read_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uint3
  * height of the tree in rounds of 24, about 32 for a mesh -- with their time under PTX_FLAG_TIME_LAUNCHES; the
  * host reads one word per group back (the roots' node counts) before the output.
  * Refused with a message before the GPU is touched, PTX_E_INVALID: a null handle, descriptor or array; T = 0
- * or above 2^24; a non-zero reserved word; max_leaf above 64; an index >= V; a position that is not finite;
- * groups that overlap, descend, are empty or reach past T; n_node_words below 8 * sum(2 * tri_count - 1). */
+ * or above 2^24; a builder above 1 or a non-zero reserved word; max_leaf above 64; an index >= V; a position
+ * that is not finite; groups that overlap, descend, are empty or reach past T; n_node_words below
+ * 8 * sum(2 * tri_count - 1).
+ *
+ * reserved[0] selects the builder: PTX_BLAS_LBVH (0, the tree above) or PTX_BLAS_SAH (1).  PTX_BLAS_SAH builds
+ * the host-side SAH builder's tree (pathtracerdemo_amd/scene/bvh.py build_blas: 32 bins, traversal cost 1,
+ * triangle cost 1.25) with a STABLE partition in place of its pairwise swaps.  A split is chosen from bin
+ * counts and bin boxes, functions of the set of triangles in a node, so every node word and the depth are
+ * build_blas'; only the order of the triangles inside a leaf differs.  The tree is a pure function of the input
+ * (pathtracerdemo_amd/scene/sah.py build_blas_sah is the same rule in numpy, bit for bit).  Everything is f64
+ * from f32 inputs unless it says f32; every operation is rounded on its own, no contraction anywhere:
+ *   per triangle   the record above: centre c and half-extent h in f32; tmin = f64(c) - f64(h) and tmax =
+ *                  f64(c) + f64(h) stay unrounded f64 (the bin boxes use these, not the f32 lo / hi)
+ *   node(lo, hi, depth)  covers positions [lo, hi) of the group's current order, count = hi - lo.  Its box
+ *                  (words 0..5) is the f32 rounding of the per-axis min of tmin and max of tmax (= the min of lo
+ *                  and the max of hi); cmin / cmax are the per-axis min / max of its centres, f32.  It is a leaf
+ *                  if count <= max_leaf or depth >= 40
+ *   the split      root_sa = 2 * ((d0*d1 + d1*d2) + d2*d0) on the f64 of the node's f32 box; best = 1.25 * count
+ *                  with no axis chosen; then axis a = 0, 1, 2 in that order:
+ *                    bin_w = (f64(cmax_a) - f64(cmin_a)) / 32; a triangle's bin is clip(floor((f64(c_a) -
+ *                    f64(cmin_a)) / bin_w), 0, 31), or 0 when bin_w is not positive; a bin has a count and a
+ *                    3-axis f64 box (min of tmin, max of tmax);
+ *                    candidates i = 0..30 ascending: lc = the triangles in bins <= i, rc = count - lc; lp =
+ *                    SA(union of bins 0..i) / root_sa if lc > 0 and root_sa > 0, else 0; rp likewise over bins
+ *                    i+1..31 and rc; cost = 1.0 + 1.25 * (lp*lc + rp*rc); if cost < best (strict: the first
+ *                    minimum wins) take axis a, best = cost, pos = f64(f32((f64(cmin_a) + bin_w) + i * bin_w))
+ *                  with no axis chosen the node is a leaf
+ *   partition      a triangle goes left iff f64(c_axis) < pos.  This compare and the bin number can disagree
+ *                  about a triangle on a bin boundary: n_left is counted by the compare, never taken from the
+ *                  bins.  If n_left is 0 or count the node is a leaf.  The order is stable: lefts keep their
+ *                  relative order, then rights theirs
+ *   children       node(lo, lo + n_left, depth + 1) at node + 1, node(lo + n_left, hi, depth + 1) behind the
+ *                  whole left subtree.  Interior words: w6 = 8 * (the right child's index from the root), w7 =
+ *                  axis.  Leaf words: w6 = the leaf's first position in the mesh's index buffer, w7 = 0xFFFF0000
+ *                  | count
+ *   final order    inside a leaf the triangles are in input order; leaves lie in depth-first order
+ *   zeros          the sign of a zero never reaches a decision; a box word that is a zero may carry either sign
+ * max_leaf means what it means to build_blas: a node of at most max_leaf triangles is never split.  A leaf may
+ * be LARGER than max_leaf where the SAH prefers it or no split exists (identical centres); ptx_upload_scene
+ * keeps refusing a leaf past its packed reference.  A leaf of more than 65 535 triangles cannot be serialised:
+ * PTX_E_SCENE with a message, outputs unspecified.  Device memory lives for the call only: about 230 bytes per
+ * triangle (36 per triangle for records and orders, 84 per node of up to 2 T - 1 for tables and output, 24 for
+ * the two index buffers) and 12 per vertex; an arena that cannot be allocated is PTX_E_NOMEM before any launch.  Launches
+ * count in PTX_STAT_BUILD: one per depth going down (the host reads two words back after each to size the
+ * next; 41 bound the loop), one per depth coming up, and three more. */
+#define PTX_BLAS_LBVH 0u
+#define PTX_BLAS_SAH  1u
 typedef struct ptx_blas_desc {
     const float    *positions;  uint32_t n_vertices;   /* V x 3 f32, finite */
     const uint32_t *indices;    uint32_t n_tris;       /* 3T, each < V */
     const uint32_t *groups;     uint32_t n_groups;     /* {first_tri, tri_count} pairs */
-    uint32_t max_leaf;          uint32_t reserved[3];  /* zero */
+    uint32_t max_leaf;          uint32_t reserved[3];  /* [0]: PTX_BLAS_LBVH or PTX_BLAS_SAH; [1], [2]: zero */
 } ptx_blas_desc;
 int ptx_build_blas(ptx_handle *h, const ptx_blas_desc *d,
                    uint32_t *nodes_out, size_t n_node_words,   /* >= 8 * sum(2*tri_count - 1) */

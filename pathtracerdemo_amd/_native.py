@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("PTX_LIB_PATH") or os.path.join(PKG_DIR, "libptx.so")
 
 PTX_OK = 0
 PTX_E_INVALID = -1  # bad argument / state
+PTX_E_SCENE = -3  # scene arrays inconsistent / unsupported
 PTX_E_PENDING = -5  # ptx_present_poll: still in flight
 PTX_ABI_VERSION = 5
 PTX_PIPELINE_RESTIR, PTX_PIPELINE_MCPT, PTX_PIPELINE_RESTIR_REUSE, PTX_PIPELINE_RESTIR_GI = 0, 1, 2, 3
@@ -27,6 +28,7 @@ PTX_STAT_FINAL_FUSED = 11
 PTX_STAT_DENOISE = 12  # launches of the denoiser's kernels
 PTX_STAT_REFIT = 13  # launches of ptx_update_vertices' and ptx_skin_vertices' kernels
 PTX_STAT_BUILD = 14  # launches of ptx_build_blas' kernels
+PTX_BLAS_LBVH, PTX_BLAS_SAH = 0, 1  # ptx_blas_desc.reserved[0]: the builder
 PTX_BUF_GBUFFER, PTX_BUF_RESERVOIR, PTX_BUF_ACCUM, PTX_BUF_COUNTERS, PTX_BUF_RESERVOIR_HIST = 0, 1, 2, 3, 4
 PTX_BUF_DIRECT = 5
 PTX_BUF_DENOISED = 6  # ptx_denoise's output (read-only)

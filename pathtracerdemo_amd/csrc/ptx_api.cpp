@@ -2754,6 +2754,93 @@ struct BuildArena {
     }
     void *at(size_t off) const { return (char *)buf.p + off; }
 };
+
+// PTX_BLAS_SAH, after ptx_build_blas' checks: `worst` = sum(2 * tri_count - 1) bounds the nodes.
+int build_blas_sah(ptx_handle *h, const ptx_blas_desc *d, uint64_t worst, uint32_t *nodes_out, uint32_t *indices_out,
+                   uint32_t *group_nodes_out, uint32_t *max_depth_out) {
+    const char *what = "ptx_build_blas";
+    const uint32_t T = d->n_tris, V = d->n_vertices, G = d->n_groups;
+    HIP_CHECK(h, hipSetDevice(h->device));
+    const hipStream_t st = h->cur().stream;
+    SahArgs A{};
+    A.n_tris = T;
+    A.n_groups = G;
+    A.max_leaf = d->max_leaf ? d->max_leaf : 10u;
+    A.node_cap = (uint32_t)worst;
+    BuildArena ar;
+    const size_t o_counters = ar.take(8u);
+    const size_t zero_bytes = ar.used;
+    const size_t o_pos = ar.take(12u * (size_t)V), o_idx = ar.take(12u * (size_t)T), o_groups = ar.take(8u * (size_t)G);
+    const size_t o_rec = ar.take(24u * (size_t)T), o_order0 = ar.take(4u * (size_t)T), o_order1 = ar.take(4u * (size_t)T);
+    const size_t o_final = ar.take(4u * (size_t)T);
+    const size_t o_range = ar.take(8u * (size_t)worst), o_box = ar.take(24u * (size_t)worst), o_link = ar.take(16u * (size_t)worst);
+    const size_t o_size = ar.take(4u * (size_t)worst), o_goff = ar.take(4u * (size_t)G);
+    const size_t o_nodes = ar.take(32u * (size_t)worst), o_iout = ar.take(12u * (size_t)T);
+    if (int rc = alloc_buf(h, ar.buf, ar.used)) return rc;  // (PTX_E_NOMEM: nothing was launched)
+    A.counters = (uint32_t *)ar.at(o_counters);
+    A.pos = (float *)ar.at(o_pos);
+    A.idx = (uint32_t *)ar.at(o_idx);
+    A.groups = (uint2 *)ar.at(o_groups);
+    A.rec = (float *)ar.at(o_rec);
+    A.order[0] = (uint32_t *)ar.at(o_order0);
+    A.order[1] = (uint32_t *)ar.at(o_order1);
+    A.final_order = (uint32_t *)ar.at(o_final);
+    A.n_range = (uint2 *)ar.at(o_range);
+    A.n_box = (float *)ar.at(o_box);
+    A.n_link = (uint4 *)ar.at(o_link);
+    A.n_size = (uint32_t *)ar.at(o_size);
+    A.goff = (uint32_t *)ar.at(o_goff);
+    A.nodes_out = (uint32_t *)ar.at(o_nodes);
+    A.idx_out = (uint32_t *)ar.at(o_iout);
+    hipError_t le = hipMemsetAsync(ar.buf.p, 0, zero_bytes, st);
+    if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_pos), d->positions, 12u * (size_t)V, hipMemcpyHostToDevice);
+    if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_idx), d->indices, 12u * (size_t)T, hipMemcpyHostToDevice);
+    if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_groups), d->groups, 8u * (size_t)G, hipMemcpyHostToDevice);
+    auto step = [&](SahStep s, uint32_t first, uint32_t n, uint32_t level = 0u) {
+        le = slot_timed(h, PTX_STAT_BUILD, st, le, [&] { return launch_sah(A, s, first, n, level, st); });
+    };
+    step(SahStep::Init, 0u, T);
+    // One launch per depth: the node counter read back after each sizes the next.  At depth 40 every node is a
+    // leaf, so 41 launches end any tree.
+    constexpr uint32_t kLevels = 41u;
+    std::vector<std::pair<uint32_t, uint32_t>> levels;  // {first node, nodes} per depth
+    uint32_t first = 0u, live = G, counters[2] = {0u, 0u};
+    while (le == hipSuccess && live > 0u && levels.size() < kLevels) {
+        step(SahStep::Level, first, live, (uint32_t)levels.size());
+        if (le != hipSuccess) break;
+        if (int rc = read_to_host(h, counters, A.counters, sizeof counters)) return rc;
+        levels.emplace_back(first, live);
+        if (counters[0] < first + live || counters[0] > worst)
+            return fail(h, PTX_E_HIP, "%s: %u nodes after depth %zu, the groups can need %llu", what, counters[0], levels.size() - 1u,
+                        (unsigned long long)worst);
+        first += live;
+        live = counters[0] - first;
+    }
+    if (le != hipSuccess) return fail(h, PTX_E_HIP, "%s: %s", what, hipGetErrorString(le));
+    if (live > 0u) return fail(h, PTX_E_HIP, "%s: the tree did not finish in %u levels", what, kLevels);
+    if (counters[1] > 0xFFFFu)
+        return fail(h, PTX_E_SCENE, "%s: a leaf of %u triangles cannot be serialised (the count field holds 65535)", what, counters[1]);
+    for (size_t l = levels.size(); l-- > 0u;) step(SahStep::Size, levels[l].first, levels[l].second);
+    if (le != hipSuccess) return fail(h, PTX_E_HIP, "%s: %s", what, hipGetErrorString(le));
+    std::vector<uint32_t> gsize(G), goff(G);
+    if (int rc = read_to_host(h, gsize.data(), A.n_size, 4u * (size_t)G)) return rc;  // (the roots are nodes 0 .. G - 1)
+    uint64_t total = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        goff[g] = (uint32_t)total;
+        total += gsize[g];
+    }
+    if (total != first) return fail(h, PTX_E_HIP, "%s: the roots hold %llu nodes of %u made", what, (unsigned long long)total, first);
+    A.n_nodes = first;
+    le = copy_sync(h, (void *)ar.at(o_goff), goff.data(), 4u * (size_t)G, hipMemcpyHostToDevice);
+    step(SahStep::Emit, 0u, A.n_nodes);
+    step(SahStep::Gather, 0u, T);
+    if (le != hipSuccess) return fail(h, PTX_E_HIP, "%s: %s", what, hipGetErrorString(le));
+    if (int rc = read_to_host(h, nodes_out, A.nodes_out, 32u * (size_t)total)) return rc;
+    if (int rc = read_to_host(h, indices_out, A.idx_out, 12u * (size_t)T)) return rc;
+    *max_depth_out = (uint32_t)levels.size() - 1u;
+    std::memcpy(group_nodes_out, gsize.data(), 4u * (size_t)G);
+    return PTX_OK;
+}
 }  // namespace
 
 int ptx_build_blas(ptx_handle *h, const ptx_blas_desc *d, uint32_t *nodes_out, size_t n_node_words, uint32_t *indices_out,
@@ -2761,7 +2848,8 @@ int ptx_build_blas(ptx_handle *h, const ptx_blas_desc *d, uint32_t *nodes_out, s
     if (!h) return PTX_E_INVALID;
     const char *what = "ptx_build_blas";
     if (!d) return fail(h, PTX_E_INVALID, "%s: null descriptor", what);
-    if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return fail(h, PTX_E_INVALID, "%s: a reserved word is not zero", what);
+    if (d->reserved[0] > PTX_BLAS_SAH) return fail(h, PTX_E_INVALID, "%s: builder %u (0 = LBVH, 1 = SAH)", what, d->reserved[0]);
+    if (d->reserved[1] | d->reserved[2]) return fail(h, PTX_E_INVALID, "%s: a reserved word is not zero", what);
     const uint32_t T = d->n_tris, V = d->n_vertices, G = d->n_groups;
     if (T == 0u || T > LEAF_FIRST_MASK + 1u) return fail(h, PTX_E_INVALID, "%s: %u triangles (1..%u)", what, T, LEAF_FIRST_MASK + 1u);
     if (d->max_leaf > 64u) return fail(h, PTX_E_INVALID, "%s: max_leaf %u (0 = 10, or 1..64)", what, d->max_leaf);
@@ -2791,6 +2879,7 @@ int ptx_build_blas(ptx_handle *h, const ptx_blas_desc *d, uint32_t *nodes_out, s
         return PTX_OK;
     }
     // From here on the GPU is touched, but nothing a frame reads or writes.
+    if (d->reserved[0] == PTX_BLAS_SAH) return build_blas_sah(h, d, worst, nodes_out, indices_out, group_nodes_out, max_depth_out);
     HIP_CHECK(h, hipSetDevice(h->device));
     const hipStream_t st = h->cur().stream;
     BuildArgs A{};

@@ -226,6 +226,34 @@ hipError_t build_sort_bytes(const BuildArgs &A, size_t *bytes);
 // one step of the chain; `stamp` is build_level's (2, 3, ...: one launch per height of the emitted tree)
 hipError_t launch_build(const BuildArgs &A, BuildStep step, uint32_t stamp, hipStream_t s);
 
+// ptx_build_blas, PTX_BLAS_SAH (ptx_build_sah.hip): the host builder's binned-SAH tree, top-down, a launch per
+// level.  Every pointer is device memory of the call.  Nodes are numbered as they are made: the roots 0 ..
+// n_groups - 1, a node's two children consecutively from counters[0]; a level's nodes are a contiguous range.
+struct SahArgs {
+    const float *pos;            // V x 3
+    const uint32_t *idx;         // 3T, the input index buffer
+    const uint2 *groups;         // n_groups x {first_tri, tri_count}
+    uint32_t n_tris, n_groups, max_leaf;
+    uint32_t node_cap;           // nodes the tables hold: sum(2 * tri_count - 1)
+    uint32_t n_nodes;            // nodes made (sah_emit)
+    float *rec;                  // 6 per triangle, input order: the centre xyz, the half-extent xyz
+    uint32_t *order[2];          // per position: the triangle there, at even and at odd levels
+    uint32_t *final_order;       // per position: the triangle there once its leaf is made (gaps: itself)
+    uint2 *n_range;              // per node: {first position, count}
+    float *n_box;                // 6 per node
+    uint4 *n_link;               // per node: {parent (a root: 0xFFFFFFFF), left child (right: + 1), the split
+                                 // axis or 3 for a leaf, group}
+    uint32_t *n_size;            // per node: nodes of its subtree
+    uint32_t *counters;          // [0] nodes made, [1] the largest leaf
+    const uint32_t *goff;        // per group: its root's node in nodes_out
+    uint32_t *nodes_out;         // 8 words per node
+    uint32_t *idx_out;           // 3T
+};
+enum class SahStep { Init, Level, Size, Emit, Gather };
+// one step: Init and Gather over n = n_tris, Level over the n nodes from first_node at depth `level` (one
+// workgroup each), Size over the same range, Emit over n = n_nodes
+hipError_t launch_sah(const SahArgs &A, SahStep step, uint32_t first_node, uint32_t n, uint32_t level, hipStream_t s);
+
 // closest-hit queries for a ray array (ptx_kernels.hip)
 hipError_t launch_trace_rays(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,
                              uint32_t stack_depth, hipStream_t s);

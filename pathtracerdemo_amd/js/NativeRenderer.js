@@ -244,16 +244,20 @@ class NativeRenderer {
   }
 
   /**
-   * A mesh's BLAS built on the GPU (ptx_build_blas: an LBVH), in the shapes bvh.js buildBlas produces:
+   * A mesh's BLAS built on the GPU (ptx_build_blas), in the shapes bvh.js buildBlas produces:
    * {roots: one Uint32Array of 8 words per node per group, indices (and index): the reordered Uint32Array,
    * maxDepth}.  `positions` a Float32Array of 3 per vertex, `indices` a Uint32Array of 3 per triangle, `groups`
-   * an array of [firstTriangle, triangleCount].  Needs no world; changes nothing a frame reads.  Blocking; a
-   * refused call throws.
+   * an array of [firstTriangle, triangleCount]; `options.builder` 'lbvh' (the default) or 'sah' (the host SAH
+   * builder's nodes, a leaf's triangles in input order).  Needs no world; changes nothing a frame reads.
+   * Blocking; a refused call throws.
    */
-  BuildBlas(positions, indices, groups, maxLeafTris = 10) {
+  BuildBlas(positions, indices, groups, maxLeafTris = 10, options = {}) {
+    const builders = { lbvh: 0, sah: 1 };
+    const builder = options && options.builder !== undefined ? options.builder : 'lbvh';
     if (!(positions instanceof Float32Array) || !(indices instanceof Uint32Array) || !Array.isArray(groups) ||
-        !Number.isInteger(maxLeafTris) || maxLeafTris < 0) {
-      throw new TypeError('BuildBlas: expected (Float32Array, Uint32Array, [[first, count], ...], maxLeafTris)');
+        !Number.isInteger(maxLeafTris) || maxLeafTris < 0 || !Object.prototype.hasOwnProperty.call(builders, builder)) {
+      throw new TypeError("BuildBlas: expected (Float32Array, Uint32Array, [[first, count], ...], maxLeafTris, " +
+                          "{builder: 'lbvh' | 'sah'})");
     }
     const flat = Uint32Array.from(groups.flat());
     if (flat.length !== 2 * groups.length) throw new TypeError('BuildBlas: a group is [firstTriangle, triangleCount]');
@@ -262,7 +266,7 @@ class NativeRenderer {
     const nodes = new Uint32Array(8 * worst);
     const out = new Uint32Array(indices.length);
     const counts = new Uint32Array(groups.length);
-    const maxDepth = addon.buildBlas(this.Handle, positions, indices, flat, maxLeafTris, nodes, out, counts);
+    const maxDepth = addon.buildBlas(this.Handle, positions, indices, flat, maxLeafTris, nodes, out, counts, builders[builder]);
     const roots = [];
     let at = 0;
     for (const c of counts) {

@@ -289,28 +289,30 @@ static napi_value js_read_accel(napi_env env, napi_callback_info info) {
 }
 
 /* buildBlas(h, Float32Array positions, Uint32Array indices, Uint32Array groups, maxLeaf, Uint32Array nodesOut,
- *           Uint32Array indicesOut, Uint32Array groupNodesOut) -> maxDepth: a mesh's BLAS built on the GPU
- * (ptx_build_blas); groups holds {firstTriangle, triangleCount} pairs, nodesOut 8 * sum(2 * count - 1) words */
+ *           Uint32Array indicesOut, Uint32Array groupNodesOut[, builder]) -> maxDepth: a mesh's BLAS built on the
+ * GPU (ptx_build_blas); groups holds {firstTriangle, triangleCount} pairs, nodesOut 8 * sum(2 * count - 1) words;
+ * builder PTX_BLAS_LBVH (0, the default) or PTX_BLAS_SAH (1) */
 static napi_value js_build_blas(napi_env env, napi_callback_info info) {
-    size_t argc = 8;
-    napi_value argv[8];
+    size_t argc = 9;
+    napi_value argv[9];
     CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
     Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
     if (!H) return NULL;
     void *pos, *idx, *grp, *nodes, *iout, *gout;
     size_t n_pos, n_idx, n_grp, n_nodes, n_iout, n_gout, es;
     napi_typedarray_type t[6];
-    uint32_t max_leaf = 0;
-    if (argc < 8 || typed_view(env, argv[1], &pos, &n_pos, &es, &t[0]) || typed_view(env, argv[2], &idx, &n_idx, &es, &t[1]) ||
+    uint32_t max_leaf = 0, builder = PTX_BLAS_LBVH;
+    if (argc < 8 || (argc >= 9 && napi_get_value_uint32(env, argv[8], &builder) != napi_ok) || typed_view(env, argv[1], &pos, &n_pos, &es, &t[0]) || typed_view(env, argv[2], &idx, &n_idx, &es, &t[1]) ||
         typed_view(env, argv[3], &grp, &n_grp, &es, &t[2]) || napi_get_value_uint32(env, argv[4], &max_leaf) != napi_ok ||
         typed_view(env, argv[5], &nodes, &n_nodes, &es, &t[3]) || typed_view(env, argv[6], &iout, &n_iout, &es, &t[4]) ||
         typed_view(env, argv[7], &gout, &n_gout, &es, &t[5]) || t[0] != napi_float32_array || t[1] != napi_uint32_array ||
         t[2] != napi_uint32_array || t[3] != napi_uint32_array || t[4] != napi_uint32_array || t[5] != napi_uint32_array ||
         n_pos % 3u != 0 || n_idx % 3u != 0 || n_grp % 2u != 0 || n_pos / 3u > 0xffffffffu || n_idx / 3u > 0xffffffffu ||
         n_iout != n_idx || n_gout != n_grp / 2u) {
-        napi_throw_type_error(env, NULL, "buildBlas(h, positions, indices, groups, maxLeaf, nodesOut, indicesOut, groupNodesOut) takes a "
-                                         "Float32Array of 3 per vertex, Uint32Arrays of 3 per triangle and 2 per group, an integer and "
-                                         "three Uint32Array outputs (indicesOut as long as indices, groupNodesOut one word per group)");
+        napi_throw_type_error(env, NULL, "buildBlas(h, positions, indices, groups, maxLeaf, nodesOut, indicesOut, groupNodesOut[, builder]) "
+                                         "takes a Float32Array of 3 per vertex, Uint32Arrays of 3 per triangle and 2 per group, an integer, "
+                                         "three Uint32Array outputs (indicesOut as long as indices, groupNodesOut one word per group) and "
+                                         "an optional integer");
         return NULL;
     }
     ptx_blas_desc d;
@@ -322,6 +324,7 @@ static napi_value js_build_blas(napi_env env, napi_callback_info info) {
     d.groups = (const uint32_t *)grp;
     d.n_groups = (uint32_t)(n_grp / 2u);
     d.max_leaf = max_leaf;
+    d.reserved[0] = builder;
     uint32_t depth = 0;
     int rc = ptx_build_blas(H->h, &d, (uint32_t *)nodes, n_nodes, (uint32_t *)iout, (uint32_t *)gout, &depth);
     if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_build_blas");

@@ -143,11 +143,14 @@ class Renderer:
         self._call("ptx_read_accel", self._h, out.ctypes.data if len(out) else None, len(out))
         return out
 
-    def build_blas(self, positions, indices, groups, max_leaf_tris: int = 10):
-        """A mesh's BLAS built on the GPU (ptx_build_blas: an LBVH), with scene.bvh.build_blas' signature and
-        results -- (roots: one u32 node array per group, the reordered indices, the largest depth) -- bit for
-        bit scene.lbvh.build_blas_lbvh's.  Needs no scene; changes nothing a frame reads.
-        compile_scene(name, builder=renderer.build_blas) compiles a scene with these trees."""
+    def build_blas(self, positions, indices, groups, max_leaf_tris: int = 10, builder: str = "lbvh"):
+        """A mesh's BLAS built on the GPU (ptx_build_blas), with scene.bvh.build_blas' signature and results --
+        (roots: one u32 node array per group, the reordered indices, the largest depth).  `builder`: "lbvh"
+        (bit for bit scene.lbvh.build_blas_lbvh's tree) or "sah" (bit for bit scene.sah.build_blas_sah's: the
+        host SAH builder's nodes, a leaf's triangles in input order).  Needs no scene; changes nothing a frame
+        reads.  compile_scene(name, builder=renderer.build_blas) compiles a scene with these trees."""
+        if builder not in self._BLAS_BUILDERS:
+            raise ValueError(f"build_blas: builder {builder!r} (one of {sorted(self._BLAS_BUILDERS)})")
         pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
         idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
         grp = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1, 2)
@@ -160,11 +163,19 @@ class Renderer:
         depth = ctypes.c_uint32(0)
         d = N.PtxBlasDesc(positions=pos.ctypes.data, n_vertices=len(pos), indices=idx.ctypes.data, n_tris=len(idx) // 3,
                           groups=grp.ctypes.data if len(grp) else None, n_groups=len(grp), max_leaf=int(max_leaf_tris))
+        d.reserved[0] = self._BLAS_BUILDERS[builder]
         self._call("ptx_build_blas", self._h, ctypes.byref(d), nodes.ctypes.data if n_words else None, n_words,
                    out_idx.ctypes.data, counts.ctypes.data if len(grp) else None, ctypes.addressof(depth))
         ends = 8 * np.cumsum(counts.astype(np.int64))
         roots = [nodes[e - 8 * int(c):e].copy() for e, c in zip(ends, counts)]
         return roots, out_idx, int(depth.value)
+
+    _BLAS_BUILDERS = {"lbvh": N.PTX_BLAS_LBVH, "sah": N.PTX_BLAS_SAH}
+
+    def build_blas_sah(self, positions, indices, groups, max_leaf_tris: int = 10):
+        """build_blas with the SAH builder, in build_blas' own signature:
+        compile_scene(name, builder=renderer.build_blas_sah)."""
+        return self.build_blas(positions, indices, groups, max_leaf_tris, builder="sah")
 
     def SetSkin(self, mesh: int, joints, weights, bind=None, targets=None, target_normals=None, first: int = 0) -> None:
         """Bind a skin to vertices [first, first + n) of mesh `mesh` (ptx_set_skin): `joints` (n, 4) integers,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What building a BLAS on the GPU costs, and what its LBVH trees cost a frame.
+"""What building a BLAS on the GPU costs, with either builder, and what its trees cost a frame.
 
     python tools/build_cost.py                 # 1920x1080, C3, reuse pipeline
 
@@ -7,15 +7,18 @@
     the host wall clock of one ptx_build_blas (blocking: the span ends with the nodes read back), the device
     time of its kernels (PTX_STAT_BUILD) and their number, each as median, minimum and maximum over --builds
     calls after --warmup; the Python SAH builder (scene/bvh.py build_blas) and the numpy LBVH rule
-    (scene/lbvh.py) on this host, once each; the two trees' SAH cost (bvh.py's model) and depth.
+    (scene/lbvh.py) on this host, once each; the two trees' SAH cost (bvh.py's model) and depth.  The same three
+    figures for the GPU's SAH builder (builder="sah"), measured in the same loop, call by call in turn with the
+    LBVH's, and whether its result is the numpy rule's (scene/sah.py).
 (b) The scene's way in: compile_scene with the GPU builder (GLB parse, ptx_build_blas per mesh, serialise) +
     ptx_upload_scene + ptx_set_frame, against ptx_upload_scene + ptx_set_frame of arrays made beforehand
     (today's re-upload), each repeated on a handle that already holds a scene of that size and has just rendered
     two frames; the builds' share is reported on its own.
-(c) Tracing cost: frames of the scene with its SAH trees and with its LBVH trees, one process, one build, two
-    handles alive throughout; the two alternate, --runs runs of --frames frames each (after a warm-up run of
-    each), a run's figure its mean frame time, a scene's the median over its runs.  The frame-time ratio, the
-    SAH-cost ratio and the two max_bvh_depths.
+(c) Tracing cost: frames of the scene with its host-SAH trees, with its LBVH trees and with the GPU's SAH trees
+    (the host builder's nodes, another order inside a leaf), one process, one build, three handles alive
+    throughout; they take turns, --runs runs of --frames frames each (after a warm-up run of each), a run's
+    figure its mean frame time, a scene's the median over its runs.  The frame-time ratios against the host-SAH
+    trees, the SAH-cost ratio and the max_bvh_depths.
 One JSON line.  No threshold: the tool measures."""
 import argparse
 import json
@@ -56,6 +59,7 @@ def main():
     from pathtracerdemo_amd.scene import world as world_mod
     from pathtracerdemo_amd.scene.bvh import build_blas
     from pathtracerdemo_amd.scene.lbvh import build_blas_lbvh, sah_cost
+    from pathtracerdemo_amd.scene.sah import build_blas_sah
 
     out = {"tool": "build_cost", "width": args.width, "height": args.height, "pipeline": args.pipeline,
            "scene": args.scene, "builds": args.builds, "warmup": args.warmup, "runs": args.runs, "frames": args.frames}
@@ -69,15 +73,22 @@ def main():
     for label in ("Chair", "TestScene"):
         pos, _, _, idx, groups, _ = world_mod.merged_geometry(label)
         t_call, t_kern, launches = [], [], 0
+        s_call, s_kern, s_launches = [], [], 0
         for k in range(args.warmup + args.builds):
             r.synchronize()
             ms0, n0 = build_stats()
             t, built = timed(lambda: r.build_blas(pos, idx, groups))
             ms1, n1 = build_stats()
+            r.synchronize()
+            ts, built_sah = timed(lambda: r.build_blas_sah(pos, idx, groups))
+            ms2, n2 = build_stats()
             if k >= args.warmup:
                 t_call.append(t)
                 t_kern.append(ms1 - ms0)
                 launches = n1 - n0
+                s_call.append(ts)
+                s_kern.append(ms2 - ms1)
+                s_launches = n2 - n1
         t_sah, sah = timed(lambda: build_blas(pos, idx, groups))
         t_np, lb = timed(lambda: build_blas_lbvh(pos, idx, groups))
         def fold(w):  # (a zero box word may carry either sign: include/ptx.h)
@@ -85,6 +96,14 @@ def main():
             w[:, 0:6][w[:, 0:6] == 0x80000000] = 0
             return w
         same = all(np.array_equal(fold(a), fold(b)) for a, b in zip(built[0], lb[0])) and np.array_equal(built[1], lb[1])
+        t_rule, rule = timed(lambda: build_blas_sah(pos, idx, groups))
+        same_sah = (all(np.array_equal(fold(a), fold(b)) for a, b in zip(built_sah[0], rule[0]))
+                    and np.array_equal(built_sah[1], rule[1]) and built_sah[2] == rule[2])
+        nodes_are_hosts = all(np.array_equal(fold(a), fold(b)) for a, b in zip(built_sah[0], sah[0]))
+        out[label + "_gpu_sah"] = {"build_blas_host_ms": spread(s_call), "build_kernels_ms": spread(s_kern),
+                                   "build_launches": int(s_launches), "numpy_rule_ms": round(t_rule, 1),
+                                   "gpu_equals_numpy": bool(same_sah), "nodes_equal_host_sah": bool(nodes_are_hosts),
+                                   "depth": int(built_sah[2])}
         out[label] = {"triangles": int(len(idx) // 3), "groups": len(groups),
                       "build_blas_host_ms": spread(t_call), "build_kernels_ms": spread(t_kern), "build_launches": int(launches),
                       "python_sah_ms": round(t_sah, 1), "numpy_lbvh_ms": round(t_np, 1), "gpu_equals_numpy": bool(same),
@@ -147,9 +166,10 @@ def main():
             names.append(a["meshName"])
     cost_sah = sum(sah_cost(world_mod.mesh_data(n).roots) for n in names)
     cost_lbvh = sum(sah_cost(world_mod.mesh_data(n, builder=build_blas_lbvh).roots) for n in names)
+    cs_gpu_sah = world_mod.compile_scene(args.scene, builder=r.build_blas_sah)
     r.close()
     handles = {}
-    for label, cs in (("sah", cs_sah), ("lbvh", cs_lbvh)):
+    for label, cs in (("sah", cs_sah), ("lbvh", cs_lbvh), ("gpu_sah", cs_gpu_sah)):
         h = Renderer(args.width, args.height, device=0, pipeline=args.pipeline)
         h.Initialize(cs)
         handles[label] = h
@@ -163,18 +183,22 @@ def main():
         h.synchronize()
         return (time.perf_counter() - t0) * 1e3 / args.frames
 
-    per = {"sah": [], "lbvh": []}
+    per = {"sah": [], "lbvh": [], "gpu_sah": []}
+    turns = ("sah", "lbvh", "gpu_sah")
     for k in range(1 + args.runs):
-        for label in ("sah", "lbvh") if k % 2 == 0 else ("lbvh", "sah"):
+        for label in turns[k % 3:] + turns[:k % 3]:
             t = run(handles[label])
             if k >= 1:
                 per[label].append(t)
     out["frame_ms_sah"] = spread(per["sah"])
     out["frame_ms_lbvh"] = spread(per["lbvh"])
+    out["frame_ms_gpu_sah"] = spread(per["gpu_sah"])
     out["frame_time_ratio"] = round(statistics.median(per["lbvh"]) / statistics.median(per["sah"]), 4)
+    out["frame_time_ratio_gpu_sah"] = round(statistics.median(per["gpu_sah"]) / statistics.median(per["sah"]), 4)
     out["sah_cost_ratio"] = round(cost_lbvh / cost_sah, 4)
     out["max_bvh_depth_sah"] = int(handles["sah"].stats()["max_bvh_depth"])
     out["max_bvh_depth_lbvh"] = int(handles["lbvh"].stats()["max_bvh_depth"])
+    out["max_bvh_depth_gpu_sah"] = int(handles["gpu_sah"].stats()["max_bvh_depth"])
     for h in handles.values():
         h.close()
     print(json.dumps(out))
