@@ -83,8 +83,8 @@ extern "C" {
 #define PTX_STAT_DENOISE 12  /* launches of the denoiser's kernels (ms with PTX_FLAG_TIME_LAUNCHES) */
 #define PTX_STAT_REFIT 13    /* launches of ptx_update_vertices' and ptx_skin_vertices' kernels (ms with
                                 PTX_FLAG_TIME_LAUNCHES) */
-#define PTX_STAT_BUILD 14    /* launches of ptx_build_blas' kernels, the library's sort as one (ms with
-                                PTX_FLAG_TIME_LAUNCHES) */
+#define PTX_STAT_BUILD 14    /* launches of ptx_build_blas' kernels, the library's sort as one, and of
+                                ptx_rebuild_mesh's and ptx_blas_cost's (ms with PTX_FLAG_TIME_LAUNCHES) */
 
 /* buffers for ptx_read_buffer / ptx_write_buffer / ptx_device_pointer */
 #define PTX_BUF_GBUFFER 0    /* band_h * W * 4 u32   */
@@ -253,8 +253,9 @@ int ptx_update_vertices(ptx_handle *h, uint32_t mesh, uint32_t first_vertex, uin
 /* The accel array as the handle traces it now: the uploaded array with words 0..5 of every node
  * reachable from a sub-mesh root taken from the device's tables.  Before any ptx_update_vertices it is
  * the uploaded array bit for bit, after one the refit -- what a host without a refit of its own keeps
- * to serialise the scene.  Blocking; n_accel must be the uploaded length (PTX_E_INVALID otherwise, and
- * without a scene, a frame or a layout). */
+ * to serialise the scene.  Blocking; n_accel must be the uploaded length -- after a ptx_rebuild_mesh the
+ * handle's current length (ptx_scene_sizes) -- (PTX_E_INVALID otherwise, and without a scene, a frame or a
+ * layout). */
 int ptx_read_accel(ptx_handle *h, uint32_t *accel_out, size_t n_accel);
 /* Skinning and morph targets on the GPU.  ptx_set_skin binds the bind pose, the joint indices, the
  * weights and the morph deltas of a range of one mesh's vertices into device tables the handle owns
@@ -416,6 +417,76 @@ int ptx_build_blas(ptx_handle *h, const ptx_blas_desc *d,
                    uint32_t *indices_out,                       /* 3T */
                    uint32_t *group_nodes_out,                   /* n_groups: nodes per root, packed in order */
                    uint32_t *max_depth_out);
+/* Rebuild a loaded mesh's BLAS in place.  A refit (ptx_update_vertices, ptx_skin_vertices) keeps the topology,
+ * so a mesh posed far from the shape it was built for is traced through that shape's tree with inflated
+ * boxes; this call builds the tree again from the shape the device holds now and puts it into the handle
+ * without an upload (pathtracerdemo_amd/scene/world.py rebuild_mesh is the same rule in numpy):
+ *   positions      words 0..2 of the mesh's vertex records on the device -- what the vertex calls left there,
+ *                  finite by their own guarantees
+ *   indices        the mesh's index block on the device (it ends at the next larger index offset among the
+ *                  descriptors, or at the sub-root block)
+ *   groups         one per sub-mesh root, from the handle's accel copy: first = the smallest w6 of the leaves
+ *                  reachable from the root, end = the largest w6 + count (world.py mesh_groups)
+ *   tree           ptx_build_blas' for `builder` (PTX_BLAS_LBVH or PTX_BLAS_SAH) and max_leaf (0 = 10, else
+ *                  1..64), by the same kernels; a box word that is a zero may carry either sign, as there
+ *   splice         the roots, concatenated in group order, replace the mesh's block of the accel array (from
+ *                  offset blas + d[4] to the next larger block start or the array's end); later blocks shift and
+ *                  word 4 of every descriptor whose block lay behind moves by the difference; the mesh's sub-root
+ *                  words become the running sum of its roots' lengths (in words); its index block becomes the
+ *                  reordered indices.  Vertex records, every other scene word and the uniform's offsets stay
+ * Blocking.  The call waits for frames in flight, brings the handle's host copies up to date with the device
+ * (posed vertex blocks, refitted boxes), validates, builds on the handle's stream, reads nodes and indices
+ * back as ptx_build_blas does, validates the tree, and only then commits: it splices the handle's copies,
+ * uploads the changed descriptor words, the index block and the sub-root words, and derives the layout again.
+ * Everything that can be refused is refused before the commit, the next frame being the unedited one:
+ * PTX_E_INVALID -- a null handle, no scene, no frame set or no layout, a builder above 1, max_leaf above 64;
+ * PTX_E_SCENE -- `mesh` is not a loaded mesh, roots whose leaf ranges do not ascend, overlap, reach past the
+ * index block or do not tile their range, an index at or past the mesh's vertex count, a BLAS, index or
+ * sub-root block shared with another descriptor, a built leaf of more than 127 triangles (PTX_BLAS_SAH makes
+ * one where no split exists; the layout's packed reference holds 127), a depth whose traversal stack would
+ * not fit LDS.  A HIP error after the commit began leaves the handle without a scene: ptx_upload_scene next.
+ * Kept: the vertex records and every skin (ptx_skin_vertices works right after, with no ptx_set_skin), the
+ * accumulation (not reset), the temporal denoiser's history (keyed by instance and sub-mesh; the instance
+ * block is unchanged).  Dropped: the kept G-buffers, surface records, neighbour summaries and init state, so
+ * ptx_denoise / ptx_upsample* are PTX_E_INVALID until a frame has run; the reuse / GI history outright, as for
+ * a switched mesh under ptx_update_scene (its reservoirs name triangle numbers, and the index buffer was
+ * reordered); ptx_upsample_temporal's history unless the handle follows (ptx_upsample_follow), then the edit
+ * is pending.  A rebuild is a derivation of the layout: a mesh marked as deformed gets flag 2 for one call of
+ * either follower ("layout derived again", ptx_denoise "Vertex motion"), because a snapshot in the old
+ * triangle numbering must never be read with new numbers.  Band handles, ranks and paired hi / lo handles
+ * each make the same call; the tree is a pure function of the input, so they agree.
+ * Launches count in PTX_STAT_BUILD: the builder's, plus one (the positions).  The builder's arena lives for
+ * the call only; the handle's tables change size with the node count (64 B + 4 B per pair). */
+typedef struct ptx_rebuild_info {
+    uint32_t n_accel;        /* the accel array's length now */
+    uint32_t mesh_nodes;     /* nodes of the mesh's roots together */
+    uint32_t max_depth;      /* of the mesh's new roots */
+    uint32_t scene_words;    /* scene words that changed (descriptor word 4 of later meshes) */
+    uint32_t reserved[4];
+} ptx_rebuild_info;
+int ptx_rebuild_mesh(ptx_handle *h, uint32_t mesh, uint32_t builder /* PTX_BLAS_LBVH | PTX_BLAS_SAH */,
+                     uint32_t max_leaf /* 0 = 10, else 1..64 */, ptx_rebuild_info *info_out /* NULL ok */);
+/* The lengths of the handle's three arrays now (a rebuild changes the accel array's); a NULL pointer is
+ * skipped.  PTX_E_INVALID without a handle or a scene. */
+int ptx_scene_sizes(ptx_handle *h, size_t *n_scene, size_t *n_geometry, size_t *n_accel);
+/* The three arrays as the handle renders them now: scene -- the handle's copy (edits and shifted descriptors
+ * included); geometry -- with every posed vertex block read from the device; accel -- as ptx_read_accel
+ * returns it.  Blocking.  Each length must be ptx_scene_sizes' (PTX_E_INVALID otherwise, and without a scene,
+ * a frame or a layout); a NULL array with length 0 is skipped. */
+int ptx_read_scene(ptx_handle *h, uint32_t *scene_out, size_t n_scene, uint32_t *geometry_out, size_t n_geometry,
+                   uint32_t *accel_out, size_t n_accel);   /* a NULL array with length 0 is skipped */
+/* The surface-area cost of a mesh's trees as the device holds them now (after refits), summed over its roots
+ * -- the number that tells a host when a rebuild pays (pathtracerdemo_amd/scene/lbvh.py sah_cost, traversal 1,
+ * triangle 1.25).  Everything is f64 from the tables' f32 boxes, every operation rounded on its own, no
+ * contraction: d = f64(hi) - f64(lo); area = 2.0 * ((d.x*d.y + d.y*d.z) + d.z*d.x); rel = area / area_root
+ * where area_root > 0, else 0; a root or child that is interior adds rel, a leaf (rel * 1.25) * count.
+ * Deterministic: a workgroup adds its terms in a fixed order (shuffles, then LDS) and writes one partial, the
+ * host adds the partials in index order, nothing is atomic -- two calls on the same tables return the same
+ * bits; against another summation order the result differs by rounding (at most nodes * 2^-52 relative).
+ * Blocking; reads nothing a frame writes and changes nothing.  One launch, counted in PTX_STAT_BUILD; 8 bytes
+ * per workgroup for the call, and 4 bytes per node pair (each pair's sub-mesh) uploaded with the layout and
+ * counted in device_bytes.  Refusals are ptx_read_vertices', plus a null cost_out (PTX_E_INVALID). */
+int ptx_blas_cost(ptx_handle *h, uint32_t mesh, double *cost_out);
 int ptx_set_frame(ptx_handle *h, const uint32_t uniform[PTX_UNIFORM_WORDS]);
 /* Run the configured pipeline for the current frame; if rgba_out != NULL copy the band's
  * accumulated RGBA f32 image (band_h * W * 4) into it (blocking). Otherwise asynchronous.

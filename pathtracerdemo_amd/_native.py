@@ -63,7 +63,8 @@ EXPORTED = ["ptx_abi_version", "ptx_create", "ptx_upload_scene", "ptx_set_frame"
             "ptx_upsample", "ptx_upsample_bands", "ptx_phase_uniform", "ptx_upsample_temporal",
             "ptx_trace_queries", "ptx_upsample_temporal_bands", "ptx_update_scene", "ptx_update_vertices",
             "ptx_read_accel", "ptx_set_skin", "ptx_skin_vertices", "ptx_read_vertices",
-            "ptx_upsample_follow", "ptx_build_blas"]
+            "ptx_upsample_follow", "ptx_build_blas", "ptx_rebuild_mesh", "ptx_scene_sizes", "ptx_read_scene",
+            "ptx_blas_cost"]
 
 
 class PtxConfig(ctypes.Structure):
@@ -105,6 +106,11 @@ class PtxBlasDesc(ctypes.Structure):
     _fields_ = [("positions", ctypes.c_void_p), ("n_vertices", ctypes.c_uint32), ("indices", ctypes.c_void_p),
                 ("n_tris", ctypes.c_uint32), ("groups", ctypes.c_void_p), ("n_groups", ctypes.c_uint32),
                 ("max_leaf", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class PtxRebuildInfo(ctypes.Structure):
+    _fields_ = [("n_accel", ctypes.c_uint32), ("mesh_nodes", ctypes.c_uint32), ("max_depth", ctypes.c_uint32),
+                ("scene_words", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
 
 
 class PtxError(RuntimeError):
@@ -152,6 +158,11 @@ def load(path: str = LIB_PATH):
     lib.ptx_skin_vertices.argtypes = [H, ctypes.c_uint32, P, P]
     lib.ptx_read_vertices.argtypes = [H, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P]
     lib.ptx_build_blas.argtypes = [H, ctypes.POINTER(PtxBlasDesc), P, ctypes.c_size_t, P, P, P]
+    lib.ptx_rebuild_mesh.argtypes = [H, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(PtxRebuildInfo)]
+    lib.ptx_scene_sizes.argtypes = [H, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t),
+                                    ctypes.POINTER(ctypes.c_size_t)]
+    lib.ptx_read_scene.argtypes = [H, P, ctypes.c_size_t, P, ctypes.c_size_t, P, ctypes.c_size_t]
+    lib.ptx_blas_cost.argtypes = [H, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double)]
     lib.ptx_set_frame.argtypes = [H, P]
     lib.ptx_render.argtypes = [H, P]
     lib.ptx_run_pass.argtypes = [H, ctypes.c_int]

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <unordered_map>
@@ -420,6 +421,7 @@ int build_layout(ptx_handle *h) {
     std::vector<uint32_t> mesh_ntris(n_mesh), mesh_vertex(n_mesh), mesh_nverts(n_mesh), mesh_node_base(n_mesh), mesh_nnodes(n_mesh);
     std::vector<std::vector<uint32_t>> mesh_levels(n_mesh);
     std::vector<uint32_t> order, pair_words, root_word;
+    std::vector<uint32_t> pair_sub;  // per pair: its sub-mesh's SubRoot (ptx_blas_cost)
     if (A.size() > 0xffffffffull) return fail(h, PTX_E_SCENE, "accel array too long");
     uint32_t max_depth = 0;
 
@@ -501,6 +503,7 @@ int build_layout(ptx_handle *h) {
                 if (int rc = ref_of(L, np.lref)) return rc;
                 if (int rc = ref_of(R, np.rref)) return rc;
                 nodes.push_back(np);
+                pair_sub.push_back((uint32_t)subs.size() - 1u);
                 pair_words.push_back((uint32_t)wl);
                 pair_words.push_back((uint32_t)wr);
             }
@@ -573,6 +576,7 @@ int build_layout(ptx_handle *h) {
     h->lay_pair_words = std::move(pair_words);
     h->lay_root_word = std::move(root_word);
     if (int rc = upload(h, h->d_refit_order, order.data(), order.size() * sizeof(uint32_t))) return rc;
+    if (int rc = upload(h, h->d_pair_sub, pair_sub.data(), pair_sub.size() * sizeof(uint32_t))) return rc;
     {
         uint32_t most = 1;
         for (const uint32_t t : h->lay_mesh_ntris) most = std::max(most, t);
@@ -2755,10 +2759,17 @@ struct BuildArena {
     void *at(size_t off) const { return (char *)buf.p + off; }
 };
 
-// PTX_BLAS_SAH, after ptx_build_blas' checks: `worst` = sum(2 * tri_count - 1) bounds the nodes.
-int build_blas_sah(ptx_handle *h, const ptx_blas_desc *d, uint64_t worst, uint32_t *nodes_out, uint32_t *indices_out,
-                   uint32_t *group_nodes_out, uint32_t *max_depth_out) {
-    const char *what = "ptx_build_blas";
+// How a builder's core gets its input onto the device: the packed positions (V x 3 f32) and the index
+// buffer (3T), both in the call's arena, written and waited for or enqueued on the handle's stream.
+// ptx_build_blas copies the caller's host arrays in; ptx_rebuild_mesh takes them from the handle's geometry.
+using BlasFill = std::function<hipError_t(float *pos, uint32_t *idx)>;
+
+// The cores of ptx_build_blas and ptx_rebuild_mesh, after the caller's checks.  Of `d` they read the counts,
+// max_leaf and the groups (host memory); positions and indices come through `fill`.  `worst` =
+// sum(2 * tri_count - 1) bounds the nodes; nodes_out holds 8 * worst words.
+// PTX_BLAS_SAH:
+int build_blas_sah(ptx_handle *h, const char *what, const ptx_blas_desc *d, const BlasFill &fill, uint64_t worst,
+                   uint32_t *nodes_out, uint32_t *indices_out, uint32_t *group_nodes_out, uint32_t *max_depth_out) {
     const uint32_t T = d->n_tris, V = d->n_vertices, G = d->n_groups;
     HIP_CHECK(h, hipSetDevice(h->device));
     const hipStream_t st = h->cur().stream;
@@ -2793,8 +2804,7 @@ int build_blas_sah(ptx_handle *h, const ptx_blas_desc *d, uint64_t worst, uint32
     A.nodes_out = (uint32_t *)ar.at(o_nodes);
     A.idx_out = (uint32_t *)ar.at(o_iout);
     hipError_t le = hipMemsetAsync(ar.buf.p, 0, zero_bytes, st);
-    if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_pos), d->positions, 12u * (size_t)V, hipMemcpyHostToDevice);
-    if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_idx), d->indices, 12u * (size_t)T, hipMemcpyHostToDevice);
+    if (le == hipSuccess) le = fill((float *)ar.at(o_pos), (uint32_t *)ar.at(o_idx));
     if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_groups), d->groups, 8u * (size_t)G, hipMemcpyHostToDevice);
     auto step = [&](SahStep s, uint32_t first, uint32_t n, uint32_t level = 0u) {
         le = slot_timed(h, PTX_STAT_BUILD, st, le, [&] { return launch_sah(A, s, first, n, level, st); });
@@ -2841,45 +2851,11 @@ int build_blas_sah(ptx_handle *h, const ptx_blas_desc *d, uint64_t worst, uint32
     std::memcpy(group_nodes_out, gsize.data(), 4u * (size_t)G);
     return PTX_OK;
 }
-}  // namespace
 
-int ptx_build_blas(ptx_handle *h, const ptx_blas_desc *d, uint32_t *nodes_out, size_t n_node_words, uint32_t *indices_out,
-                   uint32_t *group_nodes_out, uint32_t *max_depth_out) {
-    if (!h) return PTX_E_INVALID;
-    const char *what = "ptx_build_blas";
-    if (!d) return fail(h, PTX_E_INVALID, "%s: null descriptor", what);
-    if (d->reserved[0] > PTX_BLAS_SAH) return fail(h, PTX_E_INVALID, "%s: builder %u (0 = LBVH, 1 = SAH)", what, d->reserved[0]);
-    if (d->reserved[1] | d->reserved[2]) return fail(h, PTX_E_INVALID, "%s: a reserved word is not zero", what);
+// PTX_BLAS_LBVH:
+int build_blas_lbvh(ptx_handle *h, const char *what, const ptx_blas_desc *d, const BlasFill &fill, uint64_t worst,
+                    uint32_t *nodes_out, uint32_t *indices_out, uint32_t *group_nodes_out, uint32_t *max_depth_out) {
     const uint32_t T = d->n_tris, V = d->n_vertices, G = d->n_groups;
-    if (T == 0u || T > LEAF_FIRST_MASK + 1u) return fail(h, PTX_E_INVALID, "%s: %u triangles (1..%u)", what, T, LEAF_FIRST_MASK + 1u);
-    if (d->max_leaf > 64u) return fail(h, PTX_E_INVALID, "%s: max_leaf %u (0 = 10, or 1..64)", what, d->max_leaf);
-    if (!d->positions || !d->indices || (!d->groups && G) || !indices_out || (!group_nodes_out && G) || !max_depth_out ||
-        (!nodes_out && G))
-        return fail(h, PTX_E_INVALID, "%s: null array", what);
-    uint64_t worst = 0, next_free = 0;
-    for (uint32_t g = 0; g < G; ++g) {
-        const uint64_t first = d->groups[2u * g], count = d->groups[2u * g + 1u];
-        if (count == 0u) return fail(h, PTX_E_INVALID, "%s: group %u is empty", what, g);
-        if (first < next_free) return fail(h, PTX_E_INVALID, "%s: group %u begins at triangle %llu, inside or ahead of group %u", what, g,
-                                           (unsigned long long)first, g - 1u);
-        if (first + count > T) return fail(h, PTX_E_INVALID, "%s: group %u reaches triangle %llu of %u", what, g,
-                                           (unsigned long long)(first + count), T);
-        next_free = first + count;
-        worst += 2u * count - 1u;
-    }
-    if ((uint64_t)n_node_words < 8u * worst)
-        return fail(h, PTX_E_INVALID, "%s: %zu node words, the groups may need %llu", what, n_node_words, (unsigned long long)(8u * worst));
-    for (size_t i = 0; i < 3u * (size_t)T; ++i)
-        if (d->indices[i] >= V) return fail(h, PTX_E_INVALID, "%s: triangle %zu: index %u of %u vertices", what, i / 3u, d->indices[i], V);
-    double unused = 0.0;
-    if (!all_finite(d->positions, 3u * (size_t)V, unused)) return fail(h, PTX_E_INVALID, "%s: a position is not finite", what);
-    if (G == 0u) {  // nothing to build: every triangle keeps its place
-        std::memcpy(indices_out, d->indices, 12u * (size_t)T);
-        *max_depth_out = 0u;
-        return PTX_OK;
-    }
-    // From here on the GPU is touched, but nothing a frame reads or writes.
-    if (d->reserved[0] == PTX_BLAS_SAH) return build_blas_sah(h, d, worst, nodes_out, indices_out, group_nodes_out, max_depth_out);
     HIP_CHECK(h, hipSetDevice(h->device));
     const hipStream_t st = h->cur().stream;
     BuildArgs A{};
@@ -2928,8 +2904,7 @@ int ptx_build_blas(ptx_handle *h, const ptx_blas_desc *d, uint32_t *nodes_out, s
     A.sort_temp = (void *)ar.at(o_sort);
     le = hipMemsetAsync(ar.buf.p, 0, zero_bytes, st);
     if (le == hipSuccess) le = hipMemsetAsync(A.parent, 0xFF, 8u * (size_t)T, st);
-    if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_pos), d->positions, 12u * (size_t)V, hipMemcpyHostToDevice);
-    if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_idx), d->indices, 12u * (size_t)T, hipMemcpyHostToDevice);
+    if (le == hipSuccess) le = fill((float *)ar.at(o_pos), (uint32_t *)ar.at(o_idx));
     if (le == hipSuccess) le = copy_sync(h, (void *)ar.at(o_groups), d->groups, 8u * (size_t)G, hipMemcpyHostToDevice);
     auto step = [&](BuildStep s, uint32_t stamp = 0u) {
         le = slot_timed(h, PTX_STAT_BUILD, st, le, [&] { return launch_build(A, s, stamp, st); });
@@ -2969,6 +2944,323 @@ int ptx_build_blas(ptx_handle *h, const ptx_blas_desc *d, uint32_t *nodes_out, s
     if (int rc = read_to_host(h, indices_out, A.idx_out, 12u * (size_t)T)) return rc;
     if (int rc = read_to_host(h, max_depth_out, A.max_depth, 4u)) return rc;
     std::memcpy(group_nodes_out, gsize.data(), 4u * (size_t)G);
+    return PTX_OK;
+}
+
+int build_blas_core(ptx_handle *h, const char *what, const ptx_blas_desc *d, const BlasFill &fill, uint64_t worst,
+                    uint32_t *nodes_out, uint32_t *indices_out, uint32_t *group_nodes_out, uint32_t *max_depth_out) {
+    return (d->reserved[0] == PTX_BLAS_SAH ? build_blas_sah : build_blas_lbvh)(h, what, d, fill, worst, nodes_out, indices_out,
+                                                                               group_nodes_out, max_depth_out);
+}
+}  // namespace
+
+int ptx_build_blas(ptx_handle *h, const ptx_blas_desc *d, uint32_t *nodes_out, size_t n_node_words, uint32_t *indices_out,
+                   uint32_t *group_nodes_out, uint32_t *max_depth_out) {
+    if (!h) return PTX_E_INVALID;
+    const char *what = "ptx_build_blas";
+    if (!d) return fail(h, PTX_E_INVALID, "%s: null descriptor", what);
+    if (d->reserved[0] > PTX_BLAS_SAH) return fail(h, PTX_E_INVALID, "%s: builder %u (0 = LBVH, 1 = SAH)", what, d->reserved[0]);
+    if (d->reserved[1] | d->reserved[2]) return fail(h, PTX_E_INVALID, "%s: a reserved word is not zero", what);
+    const uint32_t T = d->n_tris, V = d->n_vertices, G = d->n_groups;
+    if (T == 0u || T > LEAF_FIRST_MASK + 1u) return fail(h, PTX_E_INVALID, "%s: %u triangles (1..%u)", what, T, LEAF_FIRST_MASK + 1u);
+    if (d->max_leaf > 64u) return fail(h, PTX_E_INVALID, "%s: max_leaf %u (0 = 10, or 1..64)", what, d->max_leaf);
+    if (!d->positions || !d->indices || (!d->groups && G) || !indices_out || (!group_nodes_out && G) || !max_depth_out ||
+        (!nodes_out && G))
+        return fail(h, PTX_E_INVALID, "%s: null array", what);
+    uint64_t worst = 0, next_free = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        const uint64_t first = d->groups[2u * g], count = d->groups[2u * g + 1u];
+        if (count == 0u) return fail(h, PTX_E_INVALID, "%s: group %u is empty", what, g);
+        if (first < next_free) return fail(h, PTX_E_INVALID, "%s: group %u begins at triangle %llu, inside or ahead of group %u", what, g,
+                                           (unsigned long long)first, g - 1u);
+        if (first + count > T) return fail(h, PTX_E_INVALID, "%s: group %u reaches triangle %llu of %u", what, g,
+                                           (unsigned long long)(first + count), T);
+        next_free = first + count;
+        worst += 2u * count - 1u;
+    }
+    if ((uint64_t)n_node_words < 8u * worst)
+        return fail(h, PTX_E_INVALID, "%s: %zu node words, the groups may need %llu", what, n_node_words, (unsigned long long)(8u * worst));
+    for (size_t i = 0; i < 3u * (size_t)T; ++i)
+        if (d->indices[i] >= V) return fail(h, PTX_E_INVALID, "%s: triangle %zu: index %u of %u vertices", what, i / 3u, d->indices[i], V);
+    double unused = 0.0;
+    if (!all_finite(d->positions, 3u * (size_t)V, unused)) return fail(h, PTX_E_INVALID, "%s: a position is not finite", what);
+    if (G == 0u) {  // nothing to build: every triangle keeps its place
+        std::memcpy(indices_out, d->indices, 12u * (size_t)T);
+        *max_depth_out = 0u;
+        return PTX_OK;
+    }
+    // From here on the GPU is touched, but nothing a frame reads or writes.
+    const BlasFill fill = [&](float *pos, uint32_t *idx) {
+        hipError_t e = copy_sync(h, pos, d->positions, 12u * (size_t)V, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = copy_sync(h, idx, d->indices, 12u * (size_t)T, hipMemcpyHostToDevice);
+        return e;
+    };
+    return build_blas_core(h, what, d, fill, worst, nodes_out, indices_out, group_nodes_out, max_depth_out);
+}
+
+// ptx_rebuild_mesh: a loaded mesh's BLAS built again from the device's vertex records and spliced into the
+// handle's arrays (include/ptx.h states the rule; scene/world.py rebuild_mesh is the same in numpy).
+// Everything that can be refused is refused before the commit; the commit ends in build_layout.
+int ptx_rebuild_mesh(ptx_handle *h, uint32_t mesh, uint32_t builder, uint32_t max_leaf, ptx_rebuild_info *info_out) {
+    if (!h) return PTX_E_INVALID;
+    const char *what = "ptx_rebuild_mesh";
+    if (!h->scene_loaded || !h->frame_set || !h->layout_valid)
+        return fail(h, PTX_E_INVALID, "%s: upload a scene and set a frame first", what);
+    if (builder > PTX_BLAS_SAH) return fail(h, PTX_E_INVALID, "%s: builder %u (0 = LBVH, 1 = SAH)", what, builder);
+    if (max_leaf > 64u) return fail(h, PTX_E_INVALID, "%s: max_leaf %u (0 = 10, or 1..64)", what, max_leaf);
+    const uint32_t n_mesh = (uint32_t)h->lay_mesh_nsub.size();
+    if (mesh >= n_mesh) return fail(h, PTX_E_SCENE, "%s: mesh %u of %u", what, mesh, n_mesh);
+    HIP_CHECK(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;  // frames in flight still read the geometry and the tables
+    // the host's copies first: build_layout would otherwise bring them up to date over the splice
+    if (!h->mesh_stale.empty())
+        if (int rc = sync_host_mirror(h)) return rc;
+    const uint32_t *U = h->uniform;
+    const uint32_t off_desc = U[U_OFF_DESC], off_index = U[U_OFF_INDEX], off_subroot = U[U_OFF_SUBROOT], off_blas = U[U_OFF_BLAS];
+    const auto &S = h->scene, &Gm = h->geometry, &A = h->accel;
+    const uint32_t *d = S.data() + off_desc + STRIDE_DESCRIPTOR * mesh;
+    const uint32_t nsub = d[5], V = h->lay_mesh_nverts[mesh];
+    // the mesh's blocks: each ends at the next larger start among the descriptors, or at its array's end
+    size_t index0 = (size_t)off_index + d[1], index_end = off_subroot, blas0 = (size_t)off_blas + d[4], blas_end = A.size();
+    for (uint32_t o = 0; o < n_mesh; ++o) {
+        const uint32_t *e = S.data() + off_desc + STRIDE_DESCRIPTOR * o;
+        if (o != mesh && (e[1] == d[1] || e[3] == d[3] || e[4] == d[4]))
+            return fail(h, PTX_E_SCENE, "%s: mesh %u shares a block with mesh %u", what, mesh, o);
+        if (e[1] > d[1]) index_end = std::min(index_end, (size_t)off_index + e[1]);
+        if (e[4] > d[4]) blas_end = std::min(blas_end, (size_t)off_blas + e[4]);
+    }
+    if (index_end < index0 || index_end > Gm.size() || blas_end < blas0 || blas_end > A.size() ||
+        (size_t)off_subroot + d[3] + nsub > Gm.size() || h->d_geometry.bytes < Gm.size() * 4u)
+        return fail(h, PTX_E_SCENE, "%s: mesh %u's blocks lie past the arrays", what, mesh);
+    const size_t T64 = (index_end - index0) / 3u;
+    if (T64 == 0u || T64 > LEAF_FIRST_MASK + 1u || nsub == 0u)
+        return fail(h, PTX_E_SCENE, "%s: mesh %u has %zu triangles in %u sub-meshes", what, mesh, T64, nsub);
+    const uint32_t T = (uint32_t)T64;
+    // the groups: per root the range of the leaves reachable from it (scene/world.py mesh_groups)
+    std::vector<uint32_t> groups(2u * (size_t)nsub);
+    uint64_t worst = 0, end_before = 0;
+    for (uint32_t s = 0; s < nsub; ++s) {
+        const size_t base = blas0 + Gm[(size_t)off_subroot + d[3] + s];
+        uint64_t first = ~0ull, end = 0, sum = 0;
+        bool empty_leaf = false;
+        std::vector<uint32_t> st{0u};
+        size_t visited = 0;
+        while (!st.empty()) {
+            const uint32_t n = st.back();
+            st.pop_back();
+            const size_t w = base + 8u * (size_t)n;
+            if (w + 8u > blas_end || ++visited > (blas_end - blas0) / 8u)
+                return fail(h, PTX_E_SCENE, "%s: mesh %u, root %u: node %u lies outside the mesh's block", what, mesh, s, n);
+            if (A[w + 7] & 0xffff0000u) {
+                const uint64_t lf = A[w + 6], lc = A[w + 7] & 0xffffu;
+                first = std::min(first, lf);
+                end = std::max(end, lf + lc);
+                sum += lc;
+                empty_leaf = empty_leaf || lc == 0u;
+                continue;
+            }
+            st.push_back(A[w + 6] / 8u);
+            st.push_back(n + 1u);
+        }
+        if (first < end_before || end > T || first >= end)
+            return fail(h, PTX_E_SCENE, "%s: mesh %u, root %u covers triangles [%llu, %llu) of %u, the root before it ends at %llu", what,
+                        mesh, s, (unsigned long long)first, (unsigned long long)end, T, (unsigned long long)end_before);
+        if (sum != end - first || empty_leaf)
+            return fail(h, PTX_E_SCENE, "%s: mesh %u, root %u: its leaves hold %llu triangles of [%llu, %llu)", what, mesh, s,
+                        (unsigned long long)sum, (unsigned long long)first, (unsigned long long)end);
+        groups[2u * s] = (uint32_t)first;
+        groups[2u * s + 1u] = (uint32_t)(end - first);
+        end_before = end;
+        worst += 2u * (end - first) - 1u;
+    }
+    for (size_t i = 0; i < 3u * (size_t)T; ++i)
+        if (Gm[index0 + i] >= V)
+            return fail(h, PTX_E_SCENE, "%s: mesh %u, triangle %zu: index %u of %u vertices", what, mesh, i / 3u, Gm[index0 + i], V);
+    // the positions as the host's copy holds them (it is the device's: sync_host_mirror above).  The vertex calls
+    // keep them finite; an uploaded array is not looked at until here, and the builders' kernels assume it
+    const size_t vertex0 = h->lay_mesh_vertex[mesh];
+    if (vertex0 + (size_t)STRIDE_VERTEX * V > Gm.size())
+        return fail(h, PTX_E_SCENE, "%s: mesh %u's vertex block lies past the geometry array", what, mesh);
+    for (uint32_t v = 0; v < V; ++v)
+        for (uint32_t k = 0; k < 3u; ++k)
+            if ((Gm[vertex0 + (size_t)STRIDE_VERTEX * v + k] & 0x7f800000u) == 0x7f800000u)
+                return fail(h, PTX_E_SCENE, "%s: mesh %u, vertex %u: position word %u is not finite", what, mesh, v, k);
+    // the build, on the handle's stream: nothing a frame reads is written
+    ptx_blas_desc bd{};
+    bd.n_vertices = V;
+    bd.n_tris = T;
+    bd.groups = groups.data();
+    bd.n_groups = nsub;
+    bd.max_leaf = max_leaf;
+    bd.reserved[0] = builder;
+    const hipStream_t stream = h->cur().stream;
+    const uint32_t *dG = (const uint32_t *)h->d_geometry.p;
+    const uint32_t vertex_word = h->lay_mesh_vertex[mesh];
+    const BlasFill fill = [&](float *pos, uint32_t *idx) {
+        hipError_t e = slot_timed(h, PTX_STAT_BUILD, stream, hipSuccess,
+                                  [&] { return launch_build_positions(dG, vertex_word, V, pos, stream); });
+        if (e == hipSuccess) e = hipMemcpyAsync(idx, dG + index0, 12u * (size_t)T, hipMemcpyDeviceToDevice, stream);
+        return e;
+    };
+    std::vector<uint32_t> nodes(8u * (size_t)worst), new_idx(3u * (size_t)T), gsize(nsub);
+    uint32_t depth = 0;
+    if (int rc = build_blas_core(h, what, &bd, fill, worst, nodes.data(), new_idx.data(), gsize.data(), &depth)) return rc;
+    // the tree against what build_layout can hold
+    uint64_t total = 0;
+    for (const uint32_t g : gsize) total += g;
+    if (total == 0u || total > worst) return fail(h, PTX_E_HIP, "%s: the builder returned %llu nodes", what, (unsigned long long)total);
+    nodes.resize(8u * (size_t)total);
+    for (size_t n = 0; n < total; ++n) {
+        const uint32_t w7 = nodes[8u * n + 7u];
+        if ((w7 & 0xffff0000u) && (w7 & 0xffffu) > 127u)
+            return fail(h, PTX_E_SCENE, "%s: mesh %u: a leaf of %u triangles (no split exists); the layout's packed reference holds 127",
+                        what, mesh, w7 & 0xffffu);
+    }
+    if (((size_t)depth + 2u) * kBlock * 4u > 160u * 1024u)
+        return fail(h, PTX_E_SCENE, "%s: BLAS depth %u needs more LDS than a CU has", what, depth);
+    const int64_t delta = (int64_t)nodes.size() - (int64_t)(blas_end - blas0);
+    if ((uint64_t)((int64_t)A.size() + delta) > 0xffffffffull) return fail(h, PTX_E_SCENE, "%s: accel array too long", what);
+    // From here on the handle changes.  A HIP error part-way would leave the device's arrays between the
+    // two trees: the handle then holds no scene until the next ptx_upload_scene.
+    {
+        std::vector<uint32_t> accel;
+        accel.reserve((size_t)((int64_t)A.size() + delta));
+        accel.insert(accel.end(), A.begin(), A.begin() + (ptrdiff_t)blas0);
+        accel.insert(accel.end(), nodes.begin(), nodes.end());
+        accel.insert(accel.end(), A.begin() + (ptrdiff_t)blas_end, A.end());
+        h->accel = std::move(accel);
+    }
+    uint32_t scene_words = 0;
+    if (delta != 0)
+        for (uint32_t o = 0; o < n_mesh; ++o) {
+            uint32_t *e = h->scene.data() + off_desc + STRIDE_DESCRIPTOR * o;
+            if (e[4] > d[4]) {
+                e[4] = (uint32_t)((int64_t)e[4] + delta);
+                scene_words += 1u;
+            }
+        }
+    std::memcpy(h->geometry.data() + index0, new_idx.data(), 12u * (size_t)T);
+    {
+        uint32_t at = 0;
+        for (uint32_t s = 0; s < nsub; ++s) {
+            h->geometry[(size_t)off_subroot + d[3] + s] = at;
+            at += 8u * gsize[s];
+        }
+    }
+    hipError_t le = hipSuccess;
+    if (scene_words)
+        le = copy_sync(h, (uint32_t *)h->d_scene.p + off_desc, h->scene.data() + off_desc, (size_t)STRIDE_DESCRIPTOR * n_mesh * 4u,
+                       hipMemcpyHostToDevice);
+    if (le == hipSuccess)
+        le = copy_sync(h, (uint32_t *)h->d_geometry.p + index0, h->geometry.data() + index0, 12u * (size_t)T, hipMemcpyHostToDevice);
+    if (le == hipSuccess)
+        le = copy_sync(h, (uint32_t *)h->d_geometry.p + off_subroot + d[3], h->geometry.data() + off_subroot + d[3], 4u * (size_t)nsub,
+                       hipMemcpyHostToDevice);
+    int rc = le == hipSuccess ? PTX_OK : fail(h, PTX_E_HIP, "%s: %s", what, hipGetErrorString(le));
+    if (rc == PTX_OK) rc = build_layout(h);
+    if (rc != PTX_OK) {
+        h->scene_loaded = h->layout_valid = false;
+        h->hist_valid = h->dn_hist_valid = h->drawn = h->rendered = false;
+        ut_drop(h);
+        for (auto &c : h->ctx) c.surf_valid = c.init_state_valid = c.nbr_valid = false;
+        gbuf_key_drop_all(h);
+        h->mesh_stale.clear();
+        return rc;
+    }
+    // kept: the vertex records, the skins, the accumulation, the denoiser's history (keyed by instance and
+    // sub-mesh; build_layout bumped layout_gen, so a snapshot in the old triangle numbering is not read).
+    // dropped: what build_layout drops (G-buffers, surface records), the neighbour summaries and init state, and
+    // the reuse / GI history outright, as for a switched mesh: its reservoirs name triangle numbers of the
+    // index buffer that was just reordered
+    for (auto &c : h->ctx) c.surf_valid = c.init_state_valid = c.nbr_valid = false;
+    h->drawn = h->rendered = false;
+    h->hist_valid = false;
+    if (h->ut_track && h->ut_valid) h->ut_pending = true;
+    else ut_drop(h);
+    if (info_out) {
+        std::memset(info_out, 0, sizeof *info_out);
+        info_out->n_accel = (uint32_t)h->accel.size();
+        info_out->mesh_nodes = (uint32_t)total;
+        info_out->max_depth = depth;
+        info_out->scene_words = scene_words;
+    }
+    return PTX_OK;
+}
+
+int ptx_scene_sizes(ptx_handle *h, size_t *n_scene, size_t *n_geometry, size_t *n_accel) {
+    if (!h) return PTX_E_INVALID;
+    if (!h->scene_loaded) return fail(h, PTX_E_INVALID, "ptx_scene_sizes: upload a scene first");
+    if (n_scene) *n_scene = h->scene.size();
+    if (n_geometry) *n_geometry = h->geometry.size();
+    if (n_accel) *n_accel = h->accel.size();
+    return PTX_OK;
+}
+
+int ptx_read_scene(ptx_handle *h, uint32_t *scene_out, size_t n_scene, uint32_t *geometry_out, size_t n_geometry,
+                   uint32_t *accel_out, size_t n_accel) {
+    if (!h) return PTX_E_INVALID;
+    const char *what = "ptx_read_scene";
+    if (!h->scene_loaded || !h->frame_set || !h->layout_valid)
+        return fail(h, PTX_E_INVALID, "%s: upload a scene and set a frame first", what);
+    const bool skip_s = !scene_out && !n_scene, skip_g = !geometry_out && !n_geometry, skip_a = !accel_out && !n_accel;
+    if ((!skip_s && (!scene_out || n_scene != h->scene.size())) || (!skip_g && (!geometry_out || n_geometry != h->geometry.size())) ||
+        (!skip_a && (!accel_out || n_accel != h->accel.size())))
+        return fail(h, PTX_E_INVALID, "%s: (%zu, %zu, %zu) words, the handle's arrays have (%zu, %zu, %zu)", what, n_scene, n_geometry,
+                    n_accel, h->scene.size(), h->geometry.size(), h->accel.size());
+    HIP_CHECK(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;
+    if (!skip_s) std::memcpy(scene_out, h->scene.data(), n_scene * 4u);
+    if (!skip_g) {
+        std::memcpy(geometry_out, h->geometry.data(), n_geometry * 4u);
+        for (size_t m = 0; m < h->mesh_stale.size() && m < h->lay_mesh_vertex.size(); ++m) {  // the posed vertex blocks
+            if (!(h->mesh_stale[m] & kStaleGeometry)) continue;
+            const size_t w0 = h->lay_mesh_vertex[m], n = (size_t)STRIDE_VERTEX * h->lay_mesh_nverts[m];
+            if (!n || w0 + n > n_geometry || h->d_geometry.bytes < (w0 + n) * 4u) continue;
+            if (int rc = read_to_host(h, geometry_out + w0, (const uint32_t *)h->d_geometry.p + w0, n * 4u)) return rc;
+        }
+    }
+    if (!skip_a) {
+        std::memcpy(accel_out, h->accel.data(), n_accel * 4u);
+        if (int rc = device_boxes_into(h, accel_out)) return rc;
+    }
+    return PTX_OK;
+}
+
+int ptx_blas_cost(ptx_handle *h, uint32_t mesh, double *cost_out) {
+    if (!h) return PTX_E_INVALID;
+    const char *what = "ptx_blas_cost";
+    if (int rc = vertex_range_check(h, what, mesh, 0u, 0u)) return rc;
+    if (!cost_out) return fail(h, PTX_E_INVALID, "%s: null cost_out", what);
+    HIP_CHECK(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;
+    CostArgs a{};
+    a.nodes = (const NodePair *)h->d_nodes.p;
+    a.subs = (const SubRoot *)h->d_subs.p;
+    a.pair_sub = (const uint32_t *)h->d_pair_sub.p;
+    a.pair_base = h->lay_mesh_node_base[mesh];
+    a.n_pairs = h->lay_mesh_nnodes[mesh];
+    a.sub_base = h->lay_mesh_sub_base[mesh];
+    a.n_subs = h->lay_mesh_nsub[mesh];
+    const uint32_t blocks = cost_blocks(a.n_pairs, a.n_subs);
+    *cost_out = 0.0;
+    if (blocks == 0u) return PTX_OK;
+    const size_t pair_end = (size_t)a.pair_base + a.n_pairs;
+    if ((a.n_pairs && (pair_end * sizeof(NodePair) > h->d_nodes.bytes || pair_end * 4u > h->d_pair_sub.bytes)) ||
+        ((size_t)a.sub_base + a.n_subs) * sizeof(SubRoot) > h->d_subs.bytes)
+        return fail(h, PTX_E_INVALID, "%s: the mesh's tables lie past the layout", what);
+    DevBuf partial;
+    if (int rc = alloc_buf(h, partial, (size_t)blocks * sizeof(double))) return rc;
+    a.partial = (double *)partial.p;
+    const hipStream_t st = h->cur().stream;
+    const hipError_t le = slot_timed(h, PTX_STAT_BUILD, st, hipSuccess, [&] { return launch_blas_cost(a, st); });
+    std::vector<double> sums(blocks);
+    int rc = le == hipSuccess ? PTX_OK : fail(h, PTX_E_HIP, "%s: %s", what, hipGetErrorString(le));
+    if (rc == PTX_OK) rc = read_to_host(h, sums.data(), partial.p, (size_t)blocks * sizeof(double));
+    free_buf(partial);
+    if (rc != PTX_OK) return rc;
+    double total = 0.0;
+    for (const double s : sums) total += s;  // in index order
+    *cost_out = total;
     return PTX_OK;
 }
 
@@ -3199,7 +3491,8 @@ int ptx_get_stats(ptx_handle *h, ptx_stats *out) {
                         h->d_denoised.bytes + h->d_frame_color.bytes + h->d_dn_guide_prev.bytes + h->d_dn_hist[0].bytes +
                         h->d_dn_hist[1].bytes + h->d_dn_mom[0].bytes + h->d_dn_mom[1].bytes + h->d_dn_halo_g.bytes +
                         h->d_dn_halo_c.bytes + h->d_dn_obj.bytes + h->d_dn_snap.bytes + h->d_up_halo.bytes + h->d_ut_guide[0].bytes + h->d_ut_guide[1].bytes +
-                        h->d_ut_hist[0].bytes + h->d_ut_hist[1].bytes + h->d_ut_snap.bytes + h->d_ut_obj.bytes + h->d_refit_order.bytes + h->d_refit_box.bytes;
+                        h->d_ut_hist[0].bytes + h->d_ut_hist[1].bytes + h->d_ut_snap.bytes + h->d_ut_obj.bytes + h->d_refit_order.bytes + h->d_refit_box.bytes +
+                        h->d_pair_sub.bytes;
     for (const auto &k : h->skins) out->device_bytes += k.bind.bytes + k.target_pos.bytes + k.target_nrm.bytes + k.pose.bytes;
     return PTX_OK;
 }
@@ -3613,7 +3906,7 @@ int ptx_destroy(ptx_handle *h) {
                       &h->d_jstate, &h->d_jres, &h->d_replay, &h->d_psurf, &h->d_census, &h->d_wgt, &h->d_dn_guide, &h->d_dn_work,
                       &h->d_denoised, &h->d_frame_color, &h->d_dn_guide_prev, &h->d_dn_hist[0], &h->d_dn_hist[1], &h->d_dn_mom[0],
                       &h->d_dn_mom[1], &h->d_dn_halo_g, &h->d_dn_halo_c, &h->d_dn_obj, &h->d_dn_snap, &h->d_up_halo, &h->d_ut_guide[0], &h->d_ut_guide[1],
-                      &h->d_ut_hist[0], &h->d_ut_hist[1], &h->d_ut_snap, &h->d_ut_obj, &h->d_refit_order, &h->d_refit_box})
+                      &h->d_ut_hist[0], &h->d_ut_hist[1], &h->d_ut_snap, &h->d_ut_obj, &h->d_refit_order, &h->d_refit_box, &h->d_pair_sub})
         free_buf(*b);
     drop_skins(h);
     for (auto &c : h->ctx) {

@@ -21,6 +21,9 @@
 //                  walking its parent chain (1 per ancestor, plus the left sibling's emitted size where it is
 //                  a right child) and writes its 8 words;
 //   build_gather   one thread per triangle: the reordered index buffer.
+//
+//   build_positions   (ptx_rebuild_mesh, either builder) one thread per vertex: words 0..2 of a loaded mesh's
+//                  8-word records in the geometry array to the packed positions the chains above read.
 #include <hipcub/hipcub.hpp>
 
 #include "ptx_launch.h"
@@ -298,7 +301,21 @@ __global__ __launch_bounds__(kBlock) void build_gather(BuildArgs A) {
     for (int k = 0; k < 3; ++k) A.idx_out[3u * (size_t)p + k] = A.idx[3u * (size_t)src + k];
 }
 
+// ptx_rebuild_mesh's way in: one thread per vertex, words 0..2 of its 8-word record to the packed positions.
+__global__ __launch_bounds__(kBlock) void build_positions(const uint32_t *__restrict__ G, uint32_t vertex_word, uint32_t n_vertices,
+                                                          float *__restrict__ pos) {
+    const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
+    if (v >= n_vertices) return;
+    const uint32_t *rec = G + vertex_word + 8u * (size_t)v;
+    for (int k = 0; k < 3; ++k) pos[3u * (size_t)v + k] = __uint_as_float(rec[k]);
+}
+
 static dim3 build_grid(uint32_t threads) { return dim3((threads + kBlock - 1) / kBlock); }
+
+hipError_t launch_build_positions(const uint32_t *G, uint32_t vertex_word, uint32_t n_vertices, float *pos, hipStream_t s) {
+    hipLaunchKernelGGL(build_positions, build_grid(n_vertices), dim3(kBlock), 0, s, G, vertex_word, n_vertices, pos);
+    return hipGetLastError();
+}
 
 static uint32_t key_bits(const BuildArgs &A) {
     uint32_t bits = kCodeBits + 1u;

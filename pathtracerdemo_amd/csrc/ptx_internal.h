@@ -75,6 +75,9 @@ struct ptx_handle {
     // the order table on the device (4 B per pair) and the triangle boxes of one mesh's refit (24 B per
     // triangle of the largest mesh): allocated with the layout
     DevBuf d_refit_order, d_refit_box;
+    // per pair its sub-mesh (a SubRoot index; a mesh's pairs are numbered sub-mesh by sub-mesh), 4 B per
+    // pair, uploaded with the layout: how ptx_blas_cost reaches a node's root box
+    DevBuf d_pair_sub;
     // ptx_set_skin's tables, one skin per mesh (indexed by mesh; n == 0: none): the 48-byte bind records,
     // the target-major delta tables, a call's palette + target weights; the three maxima of the
     // overflow bound (ptx_skin_vertices).  Dropped by ptx_upload_scene, freed by ptx_destroy.

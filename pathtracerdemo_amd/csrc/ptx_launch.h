@@ -254,6 +254,24 @@ enum class SahStep { Init, Level, Size, Emit, Gather };
 // workgroup each), Size over the same range, Emit over n = n_nodes
 hipError_t launch_sah(const SahArgs &A, SahStep step, uint32_t first_node, uint32_t n, uint32_t level, hipStream_t s);
 
+// ptx_rebuild_mesh (ptx_build.hip): the packed positions (n_vertices x 3, device) of the vertex records that
+// begin at word `vertex_word` of the device's geometry array G
+hipError_t launch_build_positions(const uint32_t *G, uint32_t vertex_word, uint32_t n_vertices, float *pos, hipStream_t s);
+
+// ptx_blas_cost (ptx_cost.hip): the surface-area cost of one mesh's trees from the device's tables.  One thread
+// per child of the mesh's n_pairs pairs (from pair `pair_base`) and one per root record (n_subs from `sub_base`);
+// pair_sub[p] is pair p's sub-mesh (a global SubRoot index).  `partial` takes one f64 per workgroup
+// (cost_blocks(n_pairs, n_subs) of them), reduced in a fixed order; the host adds them in index order.
+struct CostArgs {
+    const NodePair *nodes;
+    const SubRoot *subs;
+    const uint32_t *pair_sub;
+    uint32_t pair_base, n_pairs, sub_base, n_subs;
+    double *partial;
+};
+uint32_t cost_blocks(uint32_t n_pairs, uint32_t n_subs);
+hipError_t launch_blas_cost(const CostArgs &a, hipStream_t s);
+
 // closest-hit queries for a ray array (ptx_kernels.hip)
 hipError_t launch_trace_rays(const Scene &sc, const float4 *rays, float4 *hits, uint32_t n, int eps_mode,
                              uint32_t stack_depth, hipStream_t s);

@@ -277,6 +277,42 @@ class NativeRenderer {
   }
 
   /**
+   * Build mesh `mesh`'s BLAS again from the vertex records the device holds now and splice it into the handle
+   * (ptx_rebuild_mesh): after a pose far from the one the tree was built for, where a refit leaves inflated
+   * boxes.  `options.builder` 'sah' (the default) or 'lbvh', `options.maxLeafTris` (10).  Skins, the
+   * accumulation and the denoiser's history stay; the reuse history is dropped.  Returns {nAccel, meshNodes,
+   * maxDepth, sceneWords}; this.World is afterwards what the handle renders -- its scene, geometry and accel
+   * replaced by new arrays (ptx_read_scene; the accel array's length and later meshes' descriptors may have
+   * moved).  After Update(); band renderers make the same call on every band.  A refused call throws and
+   * changes nothing.
+   */
+  RebuildMesh(mesh, options = {}) {
+    const builders = { lbvh: 0, sah: 1 };
+    const builder = options && options.builder !== undefined ? options.builder : 'sah';
+    const maxLeafTris = options && options.maxLeafTris !== undefined ? options.maxLeafTris : 10;
+    if (!Number.isInteger(mesh) || mesh < 0 || !Number.isInteger(maxLeafTris) || maxLeafTris < 0 ||
+        !Object.prototype.hasOwnProperty.call(builders, builder)) {
+      throw new TypeError("RebuildMesh: expected (mesh, {builder: 'sah' | 'lbvh', maxLeafTris})");
+    }
+    if (!this.World) throw new Error('RebuildMesh: Initialize first');
+    const info = addon.rebuildMesh(this.Handle, mesh, builders[builder], maxLeafTris);
+    const { scene, geometry, accel } = addon.readScene(this.Handle);
+    this.World = Object.assign({}, this.World, { scene, geometry, accel });
+    return info;
+  }
+
+  /**
+   * The surface-area cost of mesh `mesh`'s trees as the device holds them now (ptx_blas_cost; traversal 1,
+   * triangle 1.25, each node's area relative to its root's): it grows as refits inflate the boxes and tells
+   * when RebuildMesh pays.  Blocking; changes nothing.
+   */
+  BlasCost(mesh) {
+    if (!Number.isInteger(mesh) || mesh < 0) throw new TypeError('BlasCost: expected a mesh index');
+    if (!this.World) throw new Error('BlasCost: Initialize first');
+    return addon.blasCost(this.Handle, mesh);
+  }
+
+  /**
    * Bind a skin to the vertices [first, first + joints.length / 4) of mesh `mesh` (ptx_set_skin): `joints`
    * a Uint32Array and `weights` a Float32Array of four per vertex; optional Float32Arrays `bind` (six per
    * vertex: position, normal; null: the records as the handle holds them now), `targets` (morph position

@@ -333,6 +333,81 @@ static napi_value js_build_blas(napi_env env, napi_callback_info info) {
     return r;
 }
 
+/* rebuildMesh(h, mesh, builder, maxLeaf) -> {nAccel, meshNodes, maxDepth, sceneWords}: the mesh's BLAS built again
+ * from the device's vertex records and spliced into the handle (ptx_rebuild_mesh); builder PTX_BLAS_LBVH (0) or
+ * PTX_BLAS_SAH (1), maxLeaf 0 = 10 */
+static napi_value js_rebuild_mesh(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    uint32_t mesh = 0, builder = 0, max_leaf = 0;
+    if (argc < 4 || napi_get_value_uint32(env, argv[1], &mesh) != napi_ok || napi_get_value_uint32(env, argv[2], &builder) != napi_ok ||
+        napi_get_value_uint32(env, argv[3], &max_leaf) != napi_ok) {
+        napi_throw_type_error(env, NULL, "rebuildMesh(h, mesh, builder, maxLeaf) takes three integers");
+        return NULL;
+    }
+    ptx_rebuild_info ri;
+    int rc = ptx_rebuild_mesh(H->h, mesh, builder, max_leaf, &ri);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_rebuild_mesh");
+    napi_value o, v;
+    CHECK_NAPI(env, napi_create_object(env, &o));
+    const char *names[4] = {"nAccel", "meshNodes", "maxDepth", "sceneWords"};
+    const uint32_t values[4] = {ri.n_accel, ri.mesh_nodes, ri.max_depth, ri.scene_words};
+    for (int k = 0; k < 4; ++k) {
+        CHECK_NAPI(env, napi_create_uint32(env, values[k], &v));
+        CHECK_NAPI(env, napi_set_named_property(env, o, names[k], v));
+    }
+    return o;
+}
+
+/* readScene(h) -> {scene, geometry, accel}: new Uint32Arrays of the three arrays as the handle renders them now
+ * (ptx_scene_sizes + ptx_read_scene) */
+static napi_value js_read_scene(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    size_t n[3] = {0, 0, 0};
+    int rc = ptx_scene_sizes(H->h, &n[0], &n[1], &n[2]);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_scene_sizes");
+    napi_value o, ab, ta[3];
+    void *data[3] = {NULL, NULL, NULL};
+    CHECK_NAPI(env, napi_create_object(env, &o));
+    for (int k = 0; k < 3; ++k) {
+        CHECK_NAPI(env, napi_create_arraybuffer(env, n[k] * 4u, &data[k], &ab));
+        CHECK_NAPI(env, napi_create_typedarray(env, napi_uint32_array, n[k], ab, 0, &ta[k]));
+    }
+    rc = ptx_read_scene(H->h, n[0] ? (uint32_t *)data[0] : NULL, n[0], n[1] ? (uint32_t *)data[1] : NULL, n[1],
+                        n[2] ? (uint32_t *)data[2] : NULL, n[2]);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_read_scene");
+    const char *names[3] = {"scene", "geometry", "accel"};
+    for (int k = 0; k < 3; ++k) CHECK_NAPI(env, napi_set_named_property(env, o, names[k], ta[k]));
+    return o;
+}
+
+/* blasCost(h, mesh) -> number: the surface-area cost of the mesh's trees as the device holds them (ptx_blas_cost) */
+static napi_value js_blas_cost(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    CHECK_NAPI(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    Handle *H = argc >= 1 ? get_handle(env, argv[0]) : NULL;
+    if (!H) return NULL;
+    uint32_t mesh = 0;
+    if (argc < 2 || napi_get_value_uint32(env, argv[1], &mesh) != napi_ok) {
+        napi_throw_type_error(env, NULL, "blasCost(h, mesh) takes an integer");
+        return NULL;
+    }
+    double cost = 0.0;
+    int rc = ptx_blas_cost(H->h, mesh, &cost);
+    if (rc != PTX_OK) return throw_ptx(env, H, rc, "ptx_blas_cost");
+    napi_value r;
+    CHECK_NAPI(env, napi_create_double(env, cost, &r));
+    return r;
+}
+
 /* A typed array of type `want` (0), or null / undefined (0, *p = NULL, *n = 0); anything else: -1. */
 static int opt_view(napi_env env, napi_value v, napi_typedarray_type want, void **p, size_t *n) {
     napi_valuetype vt;
@@ -1169,6 +1244,9 @@ static napi_value init(napi_env env, napi_value exports) {
         {"phaseUniform", NULL, js_phase_uniform, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"upsampleFollow", NULL, js_upsample_follow, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
         {"buildBlas", NULL, js_build_blas, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"rebuildMesh", NULL, js_rebuild_mesh, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"readScene", NULL, js_read_scene, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
+        {"blasCost", NULL, js_blas_cost, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_configurable), NULL},
     };
     if (napi_define_properties(env, exports, sizeof later / sizeof later[0], later) != napi_ok) return NULL;
     return exports;

@@ -177,6 +177,44 @@ class Renderer:
         compile_scene(name, builder=renderer.build_blas_sah)."""
         return self.build_blas(positions, indices, groups, max_leaf_tris, builder="sah")
 
+    def RebuildMesh(self, mesh: int, builder: str = "sah", max_leaf_tris: int = 10) -> dict:
+        """Build mesh `mesh`'s BLAS again from the vertex records the device holds now and splice it into the
+        handle (ptx_rebuild_mesh; scene.world.rebuild_mesh is the rule): after a pose far from the one the tree
+        was built for, where a refit leaves inflated boxes.  Skins, the accumulation and the denoiser's history
+        stay, the reuse history is dropped (include/ptx.h).  Returns the call's info (n_accel, mesh_nodes,
+        max_depth, scene_words); `compiled` is afterwards read_scene()'s arrays with max_bvh_depth updated.
+        A refused call (PtxError) changes nothing."""
+        if builder not in self._BLAS_BUILDERS:
+            raise ValueError(f"RebuildMesh: builder {builder!r} (one of {sorted(self._BLAS_BUILDERS)})")
+        if self.compiled is None or self.uniform is None:
+            raise ValueError("RebuildMesh: Initialize and Update first")
+        info = N.PtxRebuildInfo()
+        self._call("ptx_rebuild_mesh", self._h, int(mesh), self._BLAS_BUILDERS[builder], int(max_leaf_tris), ctypes.byref(info))
+        scene, geometry, accel = self.read_scene()
+        self.compiled = dataclasses.replace(self.compiled, scene=scene, geometry=geometry, accel=accel,
+                                            max_bvh_depth=self.stats()["max_bvh_depth"])
+        return {k: int(getattr(info, k)) for k in ("n_accel", "mesh_nodes", "max_depth", "scene_words")}
+
+    def read_scene(self):
+        """(scene, geometry, accel) u32 arrays as the handle renders them now (ptx_read_scene): the scene array
+        with edits and shifted descriptors, the geometry with every posed vertex block read from the device,
+        the accel array as read_accel() returns it."""
+        n = [ctypes.c_size_t(0) for _ in range(3)]
+        self._call("ptx_scene_sizes", self._h, *[ctypes.byref(k) for k in n])
+        out = [np.zeros(int(k.value), dtype=np.uint32) for k in n]
+        args = []
+        for a in out:
+            args += [a.ctypes.data if len(a) else None, len(a)]
+        self._call("ptx_read_scene", self._h, *args)
+        return tuple(out)
+
+    def blas_cost(self, mesh: int) -> float:
+        """The surface-area cost of mesh `mesh`'s trees as the device holds them now (ptx_blas_cost;
+        scene.world.mesh_cost is the rule): it grows as refits inflate the boxes, and tells when RebuildMesh pays."""
+        cost = ctypes.c_double(0.0)
+        self._call("ptx_blas_cost", self._h, int(mesh), ctypes.byref(cost))
+        return float(cost.value)
+
     def SetSkin(self, mesh: int, joints, weights, bind=None, targets=None, target_normals=None, first: int = 0) -> None:
         """Bind a skin to vertices [first, first + n) of mesh `mesh` (ptx_set_skin): `joints` (n, 4) integers,
         `weights` (n, 4) f32, `bind` (n, 6) f32 {p, n} (None: the records as the handle holds them now),

@@ -436,6 +436,135 @@ def skin_mesh(cs: CompiledScene, mesh: int, skin, palette, target_weights=None, 
     return refit_mesh(cs, mesh, pos, nrm, first=first)
 
 
+def _descriptors(cs: CompiledScene) -> np.ndarray:
+    o = cs.offsets
+    n_mesh = (o["material"] - o["mesh_descriptor"]) // STRIDE_DESCRIPTOR
+    return cs.scene[o["mesh_descriptor"]:o["material"]].reshape(n_mesh, STRIDE_DESCRIPTOR)
+
+
+def _root_leaves(root: np.ndarray):
+    """The leaves reachable from node 0 of one root's words: (first, count) arrays, and the tree's depth.
+    ValueError for a child that lies outside the root or not behind its parent."""
+    n = np.asarray(root, dtype=np.uint32).reshape(-1, 8)
+    firsts, counts = [], []
+    depth_max = 0
+    stack = [(0, 0)]
+    while stack:
+        node, depth = stack.pop()
+        depth_max = max(depth_max, depth)
+        if n[node, 7] & 0xFFFF0000:
+            firsts.append(int(n[node, 6]))
+            counts.append(int(n[node, 7] & 0xFFFF))
+            continue
+        right = int(n[node, 6]) // 8
+        if int(n[node, 6]) % 8 or not node + 1 < right < len(n):
+            raise ValueError(f"node {node}: right child {int(n[node, 6])} of {len(n)} nodes")
+        stack.append((right, depth + 1))
+        stack.append((node + 1, depth + 1))
+    return np.asarray(firsts, np.int64), np.asarray(counts, np.int64), depth_max
+
+
+def mesh_groups(cs: CompiledScene, mesh: int) -> list:
+    """A loaded mesh's groups [(first_tri, tri_count)], one per sub-BLAS root, read back from its trees:
+    first = the smallest w6 of the leaves reachable from the root, end = the largest w6 + count.  ValueError
+    unless the ranges ascend, are disjoint, lie in the mesh's index block, and each root's leaf counts sum
+    to its range's length (the leaves tile the range)."""
+    b = mesh_blocks(cs, mesh)
+    n_tris = (b["index_end"] - b["index"]) // 3
+    groups = []
+    end_before = 0
+    for k, (s, e) in enumerate(b["roots"]):
+        if e <= s:
+            raise ValueError(f"mesh {mesh}: root {k} is empty")
+        firsts, counts, _ = _root_leaves(cs.accel[s:e])
+        first, end = int(firsts.min()), int((firsts + counts).max())
+        if first < end_before or end > n_tris:
+            raise ValueError(f"mesh {mesh}: root {k} covers triangles [{first}, {end}) of {n_tris}, "
+                             f"the root before it ends at {end_before}")
+        if int(counts.sum()) != end - first or not counts.all():
+            raise ValueError(f"mesh {mesh}: root {k}'s leaves hold {int(counts.sum())} triangles of [{first}, {end})")
+        groups.append((first, end - first))
+        end_before = end
+    return groups
+
+
+def scene_depth(cs: CompiledScene) -> int:
+    """The largest depth of any root of any mesh, from the arrays."""
+    depth = 0
+    seen = set()
+    for mesh in range(len(_descriptors(cs))):
+        for s, e in mesh_blocks(cs, mesh)["roots"]:
+            if (s, e) not in seen:
+                seen.add((s, e))
+                depth = max(depth, _root_leaves(cs.accel[s:e])[2])
+    return depth
+
+
+def rebuild_mesh(cs: CompiledScene, mesh: int, builder: str = "sah", max_leaf_tris: int = 10) -> CompiledScene:
+    """The compiled scene with mesh `mesh`'s BLAS built again from its vertex records as they stand (the
+    rule of ptx_rebuild_mesh, include/ptx.h): what serialize_world would have produced had the mesh been
+    compiled with this tree.  Positions are words 0..2 of its records, indices its index block, groups
+    mesh_groups; the tree is sah.build_blas_sah ("sah") or lbvh.build_blas_lbvh ("lbvh").  Its roots replace
+    its block of `accel`, later blocks shift and word 4 of their descriptors with them, its sub-root words
+    become the running sum of the roots' lengths, its index block the reordered indices; max_bvh_depth is
+    recomputed from the arrays.  Vertex records, every other scene word, offsets and counts stay; nothing of
+    `cs` is written.  ValueError for a mesh that shares its BLAS or index block with another descriptor."""
+    from .lbvh import build_blas_lbvh
+    from .sah import build_blas_sah
+    build = {"sah": build_blas_sah, "lbvh": build_blas_lbvh}[builder]
+    if not 1 <= int(max_leaf_tris) <= 64:
+        raise ValueError("max_leaf_tris must be 1..64")
+    o = cs.offsets
+    desc = _descriptors(cs)
+    b = mesh_blocks(cs, mesh)
+    d = desc[mesh]
+    for k, other in enumerate(desc):
+        if k != mesh and (other[4] == d[4] or other[1] == d[1] or other[3] == d[3]):
+            raise ValueError(f"mesh {mesh} shares a block with mesh {k}")
+    groups = mesh_groups(cs, mesh)
+    n_vert = (b["vertex_end"] - b["vertex"]) // STRIDE_VERTEX
+    rec = cs.geometry[b["vertex"]:b["vertex_end"]].reshape(n_vert, STRIDE_VERTEX)
+    indices = np.array(cs.geometry[b["index"]:b["index_end"]], dtype=np.uint32)
+    if len(indices) and int(indices.max()) >= n_vert:
+        raise ValueError(f"mesh {mesh}: index {int(indices.max())} of {n_vert} vertices")
+    roots, new_idx, _ = build(rec[:, 0:3].copy().view(np.float32), indices, groups, int(max_leaf_tris))
+    blas, root_off = merge_arrays(roots)
+    start = o["blas"] + int(d[4])
+    end = _block_end(o["blas"] + desc[:, 4].astype(np.int64), start, len(cs.accel))
+    delta = len(blas) - (end - start)
+    accel = np.concatenate([cs.accel[:start], blas, cs.accel[end:]]).astype(np.uint32)
+    scene = np.array(cs.scene, dtype=np.uint32)
+    new_desc = scene[o["mesh_descriptor"]:o["material"]].reshape(len(desc), STRIDE_DESCRIPTOR)  # (a view of the copy)
+    behind = desc[:, 4].astype(np.int64) > int(d[4])
+    new_desc[behind, 4] = (desc[behind, 4].astype(np.int64) + delta).astype(np.uint32)
+    geometry = np.array(cs.geometry, dtype=np.uint32)
+    geometry[b["index"]:b["index_end"]] = new_idx
+    r0 = o["sub_blas_root"] + int(d[3])
+    geometry[r0:r0 + int(d[5])] = root_off
+    import dataclasses
+    out = dataclasses.replace(cs, scene=scene, geometry=geometry, accel=accel)
+    out.max_bvh_depth = scene_depth(out)
+    return out
+
+
+def mesh_cost(cs: CompiledScene, mesh: int) -> float:
+    """lbvh.sah_cost of the mesh's roots as they stand in `accel` (the rule of ptx_blas_cost)."""
+    from .lbvh import sah_cost
+    return sah_cost([cs.accel[s:e] for s, e in mesh_blocks(cs, mesh)["roots"]])
+
+
+def edit_blocks(cs: CompiledScene, edited: CompiledScene) -> CompiledScene:
+    """`cs` with the instance, material and light / CDF blocks of `edited.scene`: the descriptors stay, which
+    after a rebuild differ from a freshly serialised world's (ptx_update_scene refuses a differing one)."""
+    o = cs.offsets
+    if edited.offsets != o or len(edited.scene) != len(cs.scene):
+        raise ValueError("the edited scene has another layout")
+    scene = np.array(edited.scene, dtype=np.uint32)
+    scene[o["mesh_descriptor"]:o["material"]] = cs.scene[o["mesh_descriptor"]:o["material"]]
+    import dataclasses
+    return dataclasses.replace(cs, scene=scene, instance_count=edited.instance_count, light_count=edited.light_count)
+
+
 def load_scene_json(name: str) -> dict:
     with open(os.path.join(SCENE_DIR, name + ".json")) as fh:
         return json.load(fh)
