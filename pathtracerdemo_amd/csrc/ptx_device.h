@@ -5,7 +5,7 @@
 // compiled with -ffp-contract=off so that ray setup, slab tests, Moller-Trumbore and
 // barycentrics are bit-identical to the CPU oracle.
 //
-// MI355X layout (built once per scene by ptx_api.cpp from the reference arrays):
+// MI355X layout (built once per scene by ptx_scene.cpp from the reference arrays):
 //   * tris:  per triangle 3 x float4 = {v0.xyz, e1.x} {e1.yz, e2.xy} {e2.z, -, -, -}
 //            (local space, leaf order; e1 = v1 - v0, e2 = v2 - v0 exactly as
 //            GetRayTriangleHitDistance computes them, SH/PT_1_InitPass.wgsl:522-523)

@@ -1,6 +1,7 @@
 // ptx_internal.h -- the handle behind the C ABI (include/ptx.h) and the host helpers shared
-// by ptx_api.cpp (single-handle entry points) and ptx_comm.cpp (RCCL communicator, halo
-// exchange and multi-band frames).  Not installed; not part of the ABI.
+// by ptx_api.cpp (frames, passes, denoise / upsample, present), ptx_scene.cpp (scene arrays, layout,
+// scene and mesh edits) and ptx_comm.cpp (RCCL communicator, halo exchange and multi-band frames).
+// Not installed; not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -336,13 +337,30 @@ void free_buf(DevBuf &b);
 int alloc_buf(ptx_handle *h, DevBuf &b, size_t bytes);
 // device -> caller memory after the work enqueued on the current context's stream (pinned staging, blocking)
 int read_to_host(ptx_handle *h, void *dst, const void *src, size_t bytes);
+// a copy on the current context's stream, waited for there; a host array into a buffer of its size
+hipError_t copy_sync(ptx_handle *h, void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
+int upload(ptx_handle *h, DevBuf &b, const void *src, size_t bytes);
 // first band row of the halo-extended G-buffer / reservoir allocations
 uint4 *gbuf_band(ptx_handle *h);
 uint4 *res_band(ptx_handle *h);
 bool has_reuse(const ptx_handle *h);
+// ptx_scene.cpp: the layout from the handle's arrays and uniform; ptx_set_skin's tables freed (ptx_destroy)
 int build_layout(ptx_handle *h);
+void drop_skins(ptx_handle *h);
 Scene make_scene(ptx_handle *h);
 void resolve_event(TimedLaunch &t, ptx_handle *h);
+// event pair around one launch in stats slot `slot` (nullptr: untimed); one launch with its pair, unless `le_in` failed
+TimedLaunch *event_begin(ptx_handle *h, int slot, hipStream_t st);
+void event_end(TimedLaunch *t, hipStream_t st);
+template <class F>
+hipError_t slot_timed(ptx_handle *h, int slot, hipStream_t st, hipError_t le_in, F &&launch) {
+    if (le_in != hipSuccess) return le_in;
+    TimedLaunch *t = event_begin(h, slot, st);
+    const hipError_t le = launch();
+    event_end(t, st);
+    if (!t && le == hipSuccess) h->launches[slot] += 1;  // (untimed handles: the count alone)
+    return le;
+}
 int wave_buffers(ptx_handle *h, WaveBufs &w);
 int reuse_buffers(ptx_handle *h);
 // Passes over the launch's segments as K independent sequences on K streams, joined on

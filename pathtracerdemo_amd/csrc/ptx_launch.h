@@ -1,4 +1,4 @@
-// ptx_launch.h -- host-side launch wrappers exported by ptx_kernels.hip to ptx_api.cpp.
+// ptx_launch.h -- host-side launch wrappers exported by ptx_kernels.hip to ptx_api.cpp and ptx_scene.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>

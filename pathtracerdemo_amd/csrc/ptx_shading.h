@@ -10,7 +10,7 @@ struct Material { f3 albedo; float metal, rough, trans, ior; };
 struct Surface { f3 pos, nrm; Material mat; };
 
 // GetMaterial (SH/PT_1_InitPass.wgsl:285-314): transmissive -> yellow albedo, roughness >= 0.01.
-// Applied once per sub-mesh on the host (ptx_api.cpp build_layout) into Scene::mats, indexed
+// Applied once per sub-mesh on the host (ptx_scene.cpp build_layout) into Scene::mats, indexed
 // by the flat sub-mesh number Inst::sub_base + sub: one load instead of inst -> desc -> material.
 __device__ __forceinline__ uint32_t mat_index(const Scene &sc, uint32_t inst, uint32_t sub) {
     return sc.insts[inst].sub_base + sub;
@@ -29,7 +29,7 @@ __device__ __forceinline__ float get_transmission(const Scene &sc, uint32_t inst
     return sc.mats[2u * mat_index(sc, inst, mid) + 1u].y;
 }
 // The same value from the root and instance tables (the trace kernels' LDS copies): each root
-// record carries its sub-mesh's transmission (SubRoot::pad, ptx_api.cpp build_layout), so a
+// record carries its sub-mesh's transmission (SubRoot::pad, ptx_scene.cpp build_layout), so a
 // Visibility restart test costs two LDS reads instead of two dependent global loads.
 __device__ __forceinline__ float subs_transmission(const SubRoot *subs, const Inst *insts, uint32_t inst, uint32_t mid) {
     return asf(subs[insts[inst].sub_base + mid].pad);
